@@ -2,6 +2,7 @@
 """bench.py -- poses/s of the corner-heatmap inference path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--prec bf16|fp16|bf16x3|fp8] [--batch B] [--views T]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input already resident in HBM:
 DINOv2 ViT-B/14-reg encoder on all B*T crops -> BETR decoder -> corner decode (top-20 mean), plus for
@@ -15,9 +16,11 @@ by torch.distributed.run directly (the driver's form) it reads RANK / LOCAL_RANK
 asserts WORLD_SIZE == --gpus.  `--backend gloo --cpu-plumbing` runs ONLY the launcher / barrier /
 gather plumbing on CPU (tests/test_bench_launcher.py) -- the data path itself has no CPU form.
 
-Rank 0 prints ONE JSON line.  `value` is the headline mode (--prec, default bf16 = BASELINE.json's metric); the same
-invocation also times the STRICT mode (the mode that meets north_star's 1e-3 heatmap-logit tolerance) and reports it
-under `strict`, each with its own roofline and parity block.
+Rank 0 prints ONE JSON line.  `value` is the headline mode (--prec, default: the package default f16c8_qk16, the mode
+that meets north_star's 1e-3 heatmap-logit tolerance).  A plain run sets up, warms up, times the K steps and reports
+them, nothing else.  `--full` adds everything else the line has carried: the other mode of record, rooflines, parity
+against the CPU oracle, the one-lane record, side measurements, other batch sizes / view counts / precisions, the CPU
+baseline and the in-run counters.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -889,6 +892,17 @@ class ModeRun:
         ln["free"].record(ln["s"])
         return kp
 
+    def last_outputs(self, out) -> dict:
+        """What a caller received from the last step, as host fp32 arrays: the corners the step returned (`out`, all ranks' when they
+        are gathered) and, when the step replays a captured graph, that graph's heat maps and normalised corners (this rank's batch)."""
+        o = {"corners_px": out}
+        g = self.lanes[(self.k - 1) % len(self.lanes)]["g"] if len(self.lanes) > 1 else self.graphed
+        if g is not None:
+            heat, _, kn, _ = g.out
+            o.update(heat=heat, corners_norm=kn)
+        torch.cuda.synchronize(self.device)
+        return {k: v.detach().float().cpu().numpy() for k, v in o.items()}
+
     def close(self):
         self.graphed = None          # lifts the modules' freeze (graph.py) and releases the capture pool
         self.lanes = []
@@ -987,7 +1001,9 @@ def calibration_summary(rep: dict) -> dict:
             "reference": rep["reference"]}
 
 
-def measure_mode(prec, args, device, world, rank, dist, images, bbox, mask, weights: str = "plain"):
+def measure_mode(prec, args, device, world, rank, dist, images, bbox, mask, weights: str = "plain", keep_outputs: bool = False):
+    """Times K steps of one mode.  With --full also the one-lane / one-stream record of the same K steps and (rank 0) the roofline
+    block from a launch trace; `keep_outputs`: the last timed step's outputs as host arrays (res["outputs"], rank 0)."""
     from boxdreamer_amd import _lib
     lib = _lib.load()
     run = ModeRun(prec, args, device, world, rank, dist, images, bbox, mask, weights)
@@ -995,7 +1011,7 @@ def measure_mode(prec, args, device, world, rank, dist, images, bbox, mask, weig
     B, T = run.B, run.T
     sub_lanes = run.effective_lanes()
     one_lane = None
-    if sub_lanes > 1 and run.graphed is not None and len(run.lanes) == 1:
+    if args.full and sub_lanes > 1 and run.graphed is not None and len(run.lanes) == 1:
         # for the record, first: the same K steps with the batch as ONE lane on one stream (the form of rounds 1-3), then the laned form
         run.recapture(1)
         dt1, _, out1 = timed_steps(run.step_single, args.steps, args.warmup, world, dist, sync, device)
@@ -1003,31 +1019,54 @@ def measure_mode(prec, args, device, world, rank, dist, images, bbox, mask, weig
         run.recapture(run.lane_setting)
     dt, per_rank, out = timed_steps(run.step, args.steps, args.warmup, world, dist, sync, device)
     assert out.shape[0] == B * world and torch.isfinite(out).all()
-    if one_lane is not None:
-        assert torch.equal(out, out1), "sub-batch lanes changed the corners (they must be bit-identical to the one-lane form)"
     res = {"dt": dt, "per_rank": per_rank, "out": out, "run": run, "in_flight": max(1, len(run.lanes)), "sub_lanes": sub_lanes,
            "calibration": calibration_summary(run.calibration)}
+    if keep_outputs and rank == 0:
+        res["outputs"] = run.last_outputs(out)
     if one_lane is not None:
+        assert torch.equal(out, out1), "sub-batch lanes changed the corners (they must be bit-identical to the one-lane form)"
         res["single_stream"] = one_lane
-    if len(run.lanes) > 1:        # the same K steps one batch at a time on one stream, for the record
+    if args.full and len(run.lanes) > 1:        # the same K steps one batch at a time on one stream, for the record
         dt1, _, out1 = timed_steps(run.step_single, args.steps, 1, world, dist, sync, device)
         assert out1.shape == out.shape and torch.isfinite(out1).all()     # (lanes hold different batches: values differ by design)
         res["single_stream"] = {"value": round(B * world * args.steps / dt1, 2), "ms_per_step": round(dt1 / args.steps * 1e3, 3)}
     if rank == 0:
+        value = B * world * args.steps / dt
+        fpp = flops_per_pose(T) if not args.cache_refs else DINO_FLOP_PER_IMAGE + betr_flops(T)
+        res.update(value=value, fpp=fpp, ms_per_step=dt / args.steps * 1e3)
+    if rank == 0 and args.full:
         TRACE = 3
         run.set_lanes(1)             # per-launch durations are only defined with one launch at a time: the trace runs the one-lane form
         recs, _ = trace_launches(lib, _lib, run.eager, TRACE)
         run.set_lanes(run.lane_setting)
-        value = B * world * args.steps / dt
-        fpp = flops_per_pose(T) if not args.cache_refs else DINO_FLOP_PER_IMAGE + betr_flops(T)
         counters, why = (None, "reference features cached: other algorithmic traffic") if args.cache_refs else load_counters(prec, B, T)
         if weights != "plain" and run.calibration.get("promoted"):
             counters, why = None, "promoted Linears: the counter file describes the unpromoted mode"
-        res.update(value=value, fpp=fpp, ms_per_step=dt / args.steps * 1e3,
-                   # (kernel-time fractions are of the ONE-LANE step the trace executes, where there is one)
-                   roofline=roofline_block(prec, recs, one_lane["ms_per_step"] if one_lane else dt / args.steps * 1e3, TRACE, value / world,
-                                           fpp, counters, why))
+        # (kernel-time fractions are of the ONE-LANE step the trace executes, where there is one)
+        res["roofline"] = roofline_block(prec, recs, one_lane["ms_per_step"] if one_lane else dt / args.steps * 1e3, TRACE, value / world,
+                                         fpp, counters, why)
     return res
+
+
+# at most this many bytes in all under --dump-outputs (np.save's headers stay far inside the margin to 64 MB)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 64 * 1024
+
+
+def dump_outputs(path: str, arrays: dict) -> list:
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32, smallest first.  An array that would take the set past
+    DUMP_LIMIT_BYTES keeps a fixed, seeded sample of its leading-axis entries (in order), the same entries for the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, written = DUMP_LIMIT_BYTES, []
+    for name, a in sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0])):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > left:
+            keep = min(a.shape[0], left // max(1, a.nbytes // max(1, a.shape[0])))
+            a = np.ascontiguousarray(a[np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))])
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+        written.append(name + ".npy")
+    return written
 
 
 def h2d_inclusive(run: "ModeRun", steps: int) -> dict:
@@ -1410,8 +1449,15 @@ def main():
                     help="do not re-measure MFMA-busy / HBM traffic with rocprofv3 inside this run (single GPU; ~45 s); the stamped "
                          "profiles/counters_<mode>.json is then the source, if it matches the kernel sources")
     ap.add_argument("--counter-budget", type=float, default=75.0, help="seconds the in-run counter passes may take before they are abandoned")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, measure and check everything else the line reports (the other mode of record, rooflines, "
+                         "parity, side measurements, the other configs, CPU baseline, in-run counters); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs (corners; heat maps and normalised corners of a graphed step) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all")
     ap.add_argument("--config3", action="store_true",
-                    help="also time BASELINE configs[3]'s per-GPU shard (1 query + 16 refs, batch 32/GPU) in the same line (default for --gpus > 1)")
+                    help="with --full: also time BASELINE configs[3]'s per-GPU shard (1 query + 16 refs, batch 32/GPU) in the same line "
+                         "(default for --gpus > 1)")
     ap.add_argument("--measure-counters", action="store_true",
                     help="run the rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE, MFMA busy: one pass each) over this script for --prec and "
                          "write profiles/counters_<prec>.json, which later default runs report as roofline.traffic / mfma_busy")
@@ -1484,7 +1530,10 @@ def run(args):
                             steps=args.steps, warmup=args.warmup)
     PROGRESS["stage"] = "timed steps"
 
-    main_res = measure_mode(prec, args, device, world, rank, dist, images, bbox, mask)
+    main_res = measure_mode(prec, args, device, world, rank, dist, images, bbox, mask, keep_outputs=bool(args.dump_outputs))
+    if rank == 0 and args.dump_outputs:
+        files = dump_outputs(args.dump_outputs, main_res.pop("outputs"))
+        print(f"bench: wrote {', '.join(files)} to {args.dump_outputs}", file=sys.stderr, flush=True)
     line = None
     rank_devices = None
     if dist is not None:       # every rank reports the device it ran on (an object collective: all ranks take part)
@@ -1509,12 +1558,14 @@ def run(args):
                            "batches_in_flight": main_res["in_flight"], "sub_batch_lanes": main_res["sub_lanes"],
                            "sub_batch_lanes_note": "ONE batch at a time; inside the captured step the batch runs as this many contiguous sub-batches "
                                                    "on as many streams (bd_*_forward_lanes, ABI v6; outputs bit-identical to the one-lane form, "
-                                                   "asserted here on the corners); `single_stream` is the same K steps as one lane on one stream"},
+                                                   "asserted on the corners by --full runs); `single_stream` (--full) is the same K steps as one lane "
+                                                   "on one stream"},
                 "poses_per_s_per_gpu": round(value / world, 2),
                 "value_is": "whole-job aggregate over n_gpus (bench contract); the per-GPU figure of the metric is poses_per_s_per_gpu",
                 "per_rank_ms_per_step": [round(t / args.steps * 1e3, 3) for t in main_res["per_rank"]],
-                "value_mode": prec, "package_default_mode": STRICT_PREC,
-                "roofline": main_res["roofline"]}
+                "value_mode": prec, "package_default_mode": STRICT_PREC}
+        if "roofline" in main_res:
+            line["roofline"] = main_res["roofline"]
         if main_res["calibration"].get("applicable"):
             line["calibration"] = main_res["calibration"]
         if "single_stream" in main_res:
@@ -1526,6 +1577,9 @@ def run(args):
                                    "nccl_version": ".".join(str(v) for v in torch.cuda.nccl.version()) if args.backend == "nccl" else None,
                                    "devices": names}
         PROGRESS["line"] = dict(line)
+    if not args.full:                # a plain run ends with its headline figure
+        main_res["run"].close()
+        return report(line, rank, dist)
     PROGRESS["stage"] = "corner all-gather latency"
     if dist is not None:
         lat = gather_latency_ms(main_res["run"].kp_all, world, dist, main_res["run"].gather, sync=interruptible_sync(device))
@@ -1769,6 +1823,12 @@ def run(args):
                                     parity_mode_passes_per_flop=srf["mfma_passes_per_algorithmic_flop"],
                                     parity_mode_traffic_over_algorithmic=srf.get("traffic_over_algorithmic"),
                                     parity_mode_counters_measured_in_this_run=srf.get("counters_measured_in_this_run"))
+    report(line, rank, dist)
+
+
+def report(line, rank, dist):
+    """Rank 0 prints the line; every rank leaves the process group."""
+    if rank == 0:
         PROGRESS["printed"] = True
         print(json.dumps(line), flush=True)
     if dist is not None:

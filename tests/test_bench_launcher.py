@@ -126,7 +126,7 @@ def test_two_rank_flow_with_the_real_kernels_on_one_gpu():
     (`--single-device-test`: collectives through gloo, since RCCL refuses two ranks on one device).  Not a measurement and not RCCL;
     it is the only multi-rank GPU execution a 1-GPU box allows, and what the driver's multi-GPU sweep runs except for the backend."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device-test",
-                        "--steps", "2", "--warmup", "1", "--no-strict", "--no-fp8", "--no-cpu-baseline", "--no-h2d", "--no-pnp", "--no-parity",
+                        "--steps", "2", "--warmup", "1", "--full", "--no-strict", "--no-fp8", "--no-cpu-baseline", "--no-h2d", "--no-pnp", "--no-parity",
                         "--dist-timeout", "300"], capture_output=True, text=True, env=_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _one_line(r)
@@ -147,7 +147,7 @@ def test_single_gpu_line_carries_the_parity_mode_and_counters_of_this_run():
     the `bf16_opt_in` block + flat `config.bf16_*` scalars, and MFMA-busy / traffic come from counters measured in THIS run when rocprofv3
     is on the box -- else from the stamped file, and the line says which.  The facade and the RCCL world-1 probe ride in the same line."""
     import shutil
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-fp8", "--no-trained-like",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-fp8", "--no-trained-like",
                         "--no-cpu-baseline", "--no-h2d", "--no-pnp", "--no-power", "--sustained", "6"], capture_output=True, text=True, env=_env(), timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _one_line(r)
@@ -180,6 +180,46 @@ def test_single_gpu_line_carries_the_parity_mode_and_counters_of_this_run():
     else:       # no rocprofv3 on this box, or its passes failed / ran out of their time budget: the line must say why (and falls back to the stamped file)
         print("in-run counters skipped:", rf.get("counters_in_this_run_skipped"))
         assert isinstance(rf.get("counters_in_this_run_skipped"), str) and rf["counters_in_this_run_skipped"]
+
+
+@pytest.mark.gpu
+def test_plain_run_reports_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """A run without --full times the K steps of the headline mode and nothing else; --dump-outputs writes the last timed step's
+    corners and (graphed step) heat maps as float32 .npy files."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=_env(), timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = _one_line(r)
+    assert j["steps"] == 3 and j["value"] > 0 and j["unit"] == "poses/s" and j["higher_is_better"] is True
+    assert j["dtype"] and j["metric"].startswith("poses/s/GPU (5-ref") and 0 < j["ms_per_step"] == j["per_rank_ms_per_step"][0]
+    assert abs(j["value"] - 32 * 1e3 / j["ms_per_step"]) < 0.01 * j["value"]
+    for k in ("roofline", "parity", "bf16_opt_in", "strict", "facade", "one_pose_latency", "cpu_baseline", "sustained", "single_stream"):
+        assert k not in j, k
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["corners_norm", "corners_px", "heat"]
+    assert out["corners_px"].shape == out["corners_norm"].shape == (32, 8, 2) and out["heat"].shape == (32, 8, 224, 224)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+    assert np.abs(out["heat"]).max() <= 1.0 and (out["corners_px"] >= 0).all() and (out["corners_px"] < 224).all()
+
+
+def test_dump_outputs_float32_under_the_size_limit(tmp_path):
+    """--dump-outputs: float32 files, at most 64 MB in all; an array that does not fit keeps the same seeded sample of its rows."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    rng = np.random.default_rng(5)
+    arrays = {"heat": rng.standard_normal((48, 8, 224, 224), dtype=np.float32), "corners_px": rng.uniform(0, 224, (48, 8, 2))}
+    for d in ("a", "b"):
+        assert b.dump_outputs(str(tmp_path / d), arrays) == ["corners_px.npy", "heat.npy"]
+    files = [tmp_path / d / f for d in ("a", "b") for f in ("corners_px.npy", "heat.npy")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 64e6
+    a = [np.load(f) for f in files]
+    assert all(x.dtype == np.float32 for x in a) and np.array_equal(a[0], arrays["corners_px"].astype(np.float32))
+    assert 0 < a[1].shape[0] < 48 and a[1].shape[1:] == (8, 224, 224) and np.array_equal(a[1], a[3])
+    rows = [i for i in range(48) if any(np.array_equal(arrays["heat"][i], h) for h in a[1][:3])]
+    assert len(rows) == 3 and rows == sorted(rows)
 
 
 @pytest.mark.gpu

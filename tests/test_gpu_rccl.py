@@ -60,7 +60,7 @@ def test_bench_sweep_flow_on_rccl_world1(hip):
     port = str(m.free_port())
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--config3", "--steps", "3", "--warmup", "1",
-           "--no-strict", "--no-fp8", "--no-latency", "--no-cpu-baseline", "--no-inline-counters", "--no-h2d", "--no-pnp", "--no-power",
+           "--full", "--no-strict", "--no-fp8", "--no-latency", "--no-cpu-baseline", "--no-inline-counters", "--no-h2d", "--no-pnp", "--no-power",
            "--no-rccl-probe", "--no-parity", "--dist-timeout", "300"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=_env(), timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

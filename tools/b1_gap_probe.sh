@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 R=$(pwd); out=gpurun_out/b1gap; rm -rf $out; mkdir -p $out
 for pr in ${1:-f16c8_qk16}; do
-( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$out/$pr -- python $R/bench.py --prec $pr --batch 1 --in-flight 1 --lanes 1 --steps 40 --warmup 10 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-trained-like --no-latency > /dev/null 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && timeout 300 rocprofv3 --kernel-trace --output-format csv -d $R/$out/$pr -- python $R/bench.py --full --prec $pr --batch 1 --in-flight 1 --lanes 1 --steps 40 --warmup 10 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-trained-like --no-latency > /dev/null 2>&1 )
 f=$(find $out/$pr -name "*kernel_trace.csv" | head -1)
 python - "$f" $pr <<'PY'
 import csv, sys

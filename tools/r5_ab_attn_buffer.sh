@@ -14,10 +14,10 @@ done
 for rep in 1 2; do
   for v in preattn default; do
     if [ $v = default ]; then unset BOXDREAMER_HIP_LIB; else export BOXDREAMER_HIP_LIB=tools/_probe/libbd_$v.so; fi
-    timeout 600 python bench.py --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
+    timeout 600 python bench.py --full --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
     python -c "
 import json; j=json.load(open('/tmp/ab.json')); s=j['strict']; print('$v rep $rep: bf16', j['value'], 'one lane', j.get('value_single_stream'), 'attn TF/s', j['roofline']['attention_achieved'], '| default', s['value'], 'one lane', s['single_stream']['value'], 'attn', s['roofline']['attention_achieved'], 'err', s['parity']['logits_max_abs_err'])"
-    timeout 600 python bench.py --views 17 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --no-parity --steps 6 --warmup 2 2>/dev/null | grep '^{' > /tmp/ab.json
+    timeout 600 python bench.py --full --views 17 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --no-parity --steps 6 --warmup 2 2>/dev/null | grep '^{' > /tmp/ab.json
     python -c "
 import json; j=json.load(open('/tmp/ab.json')); print('$v rep $rep: T=17 bf16', j['value'], 'attn TF/s', j['roofline']['attention_achieved'])"
   done

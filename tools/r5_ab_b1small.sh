@@ -10,7 +10,7 @@ for rep in 1 2; do
   for v in base new; do
     if [ $v = new ]; then unset BOXDREAMER_HIP_LIB; else export BOXDREAMER_HIP_LIB=tools/_probe/libbd_b1base.so; fi
     for B in 1 2 4 8; do
-      timeout 300 python bench.py --prec f16c8_qk16 --batch $B --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 40 --warmup 10 2>/dev/null | grep '^{' > /tmp/ab.json
+      timeout 300 python bench.py --full --prec f16c8_qk16 --batch $B --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 40 --warmup 10 2>/dev/null | grep '^{' > /tmp/ab.json
       python -c "
 import json; j=json.load(open('/tmp/ab.json')); print('$v rep $rep default mode B=$B: ms/step', j['ms_per_step'], 'poses/s', j['value'], 'err', (j.get('parity') or {}).get('logits_max_abs_err'))"
     done
@@ -18,7 +18,7 @@ import json; j=json.load(open('/tmp/ab.json')); print('$v rep $rep default mode 
 done
 for v in base new; do
   if [ $v = new ]; then unset BOXDREAMER_HIP_LIB; else export BOXDREAMER_HIP_LIB=tools/_probe/libbd_b1base.so; fi
-  timeout 600 python bench.py --prec f16c8_qk16 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
+  timeout 600 python bench.py --full --prec f16c8_qk16 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
   python -c "
 import json; j=json.load(open('/tmp/ab.json')); print('$v default mode B=32: poses/s', j['value'], 'one lane', j.get('value_single_stream'))"
 done

@@ -17,7 +17,7 @@ for rep in 1 2; do
   for v in default $V; do
     if [ $v = default ]; then unset BOXDREAMER_HIP_LIB; else export BOXDREAMER_HIP_LIB=tools/_probe/libbd_$v.so; fi
     for pr in bf16 f16c8_qk16; do
-    timeout 600 python bench.py --prec $pr --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
+    timeout 600 python bench.py --full --prec $pr --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
     python -c "
 import json; j=json.load(open('/tmp/ab.json')); p=j.get('power') or {}; print('$v rep $rep $pr step: poses/s', j['value'], 'ms', j['ms_per_step'], 'one lane', j.get('value_single_stream'), 'gemm TF/s', j['roofline']['achieved'], 'err', (j.get('parity') or {}).get('logits_max_abs_err'), 'W', p.get('avg_w'))"
     done

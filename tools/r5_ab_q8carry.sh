@@ -12,7 +12,7 @@ done
 for rep in 1 2; do
   for v in base new; do
     if [ $v = new ]; then unset BOXDREAMER_HIP_LIB; else export BOXDREAMER_HIP_LIB=tools/_probe/libbd_base.so; fi
-    timeout 600 python bench.py --prec f16c8_qk16 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-latency --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
+    timeout 600 python bench.py --full --prec f16c8_qk16 --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-latency --steps 10 --warmup 3 2>/dev/null | grep '^{' > /tmp/ab.json
     python -c "
 import json; j=json.load(open('/tmp/ab.json')); print('$v rep $rep default step: poses/s', j['value'], 'one lane', j.get('value_single_stream'), 'err', (j.get('parity') or {}).get('logits_max_abs_err'))"
   done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6: kernel stats of the default mode one pose at a time WITH the opt-in latency forms (bench.py --latency-forms), un-graphed, 20 steps.
 R=$(cd "$(dirname "$0")/.." && pwd); out=$R/gpurun_out/r6_b1_latency; mkdir -p $out
-COMMON="--no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe --no-facade --no-trained-like --sustained 0"
+COMMON="--full --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe --no-facade --no-trained-like --sustained 0"
 cd /tmp && export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python $R/bench.py --latency-forms --prec f16c8_qk16 --batch 1 --in-flight 1 --lanes 1 --steps 20 --warmup 5 --no-graph $COMMON > /dev/null 2>&1
 echo "rocprof rc $?"

@@ -6,7 +6,7 @@ tag=${1:-r6}; skip=",${2:-},"
 out=gpurun_out/final_$tag; mkdir -p $out
 R=$(pwd)
 has() { case "$skip" in *",$1,"*) return 0;; esac; return 1; }
-COMMON="--no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe --no-facade --no-trained-like --sustained 0"
+COMMON="--full --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe --no-facade --no-trained-like --sustained 0"
 if ! has suite; then
   timeout 1800 python -m pytest tests -m gpu -q --durations=30 > $out/pytest.log 2>&1; echo "pytest rc $?" | tee $out/status; tail -3 $out/pytest.log
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee -a $out/status
@@ -38,7 +38,7 @@ if ! has counters; then
   cp profiles/counters_*.json $out/ 2>/dev/null
 fi
 if ! has bench; then
-  ( time python bench.py --gpus 1 --steps 20 --warmup 5 ) > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc $?" | tee -a $out/status
+  ( time python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc $?" | tee -a $out/status
   python - <<PY
 import json
 j=json.loads(open('$out/bench_default.json').read().strip().splitlines()[-1]); c=j['config']

@@ -4,7 +4,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 out=$R/gpurun_out/r6_lnfold_kstats; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for f in 0 1; do
-  BOXDREAMER_HIP_LNFOLD=$f timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$f -- python $R/bench.py --prec f16c8_qk16 --batch 32 --in-flight 1 --lanes 1 --steps 5 --warmup 2 --no-graph --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe > /dev/null 2>&1
+  BOXDREAMER_HIP_LNFOLD=$f timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$f -- python $R/bench.py --full --prec f16c8_qk16 --batch 32 --in-flight 1 --lanes 1 --steps 5 --warmup 2 --no-graph --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-parity --no-inline-counters --no-power --no-latency --no-rccl-probe > /dev/null 2>&1
   echo "rocprof fold=$f rc $?"
   src=$(find $out/prof_$f -name "*kernel_stats.csv" | head -1); [ -n "$src" ] && cp $src $out/kernel_stats_fold$f.csv
   rm -rf $out/prof_$f

@@ -4,7 +4,7 @@
 # environment switches, so every row now measures the library's own rule.)
 cd "$(dirname "$0")/.."
 out=gpurun_out/r6_splitk; mkdir -p $out
-COMMON="--no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --no-latency --no-rccl-probe --no-facade --sustained 0"
+COMMON="--full --no-strict --no-fp8 --no-cpu-baseline --no-pnp --no-h2d --no-inline-counters --no-trained-like --no-power --no-latency --no-rccl-probe --no-facade --sustained 0"
 for b in ${BATCHES:-1 2 4}; do
   for cfg in ${CFGS:-"1 1" "2 1" "3 1" "4 1" "3 2" "4 2" "4 3" "4 4" "0 0"}; do
     set -- $cfg
