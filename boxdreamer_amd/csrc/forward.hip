@@ -1,7 +1,9 @@
 // Whole-path entry points: the DINOv2 encoder (DinoV2Wrapper.predict) and the BETR decoder
 // (BETR.forward) as straight-line sequences of kernel launches on the caller's stream.
-// No allocation, no synchronisation, no state: the caller provides one workspace blob that is
+// No device allocation, no synchronisation, no state: the caller provides one workspace blob that is
 // carved here (256-byte aligned slices).
+#include <vector>
+
 #include "bd_common.h"
 
 namespace {
@@ -75,19 +77,52 @@ inline int handoff_kind(int from, int to) {
     return from == to ? 0 : (to == BD_PREC_BF16 ? 3 /* e4m3 GEMM -> bf16 plane */ : 5 /* F16C8 GEMM -> split-f16 planes */);
 }
 
-// How one transformer block runs: the operand class of each Linear (F16C8 family: per-Linear promotion to split-f16; e4m3: to bf16), the attention
-// form, and the 16-bit kinds in which producers hand their results on.
+// One transformer stack of one call: its weights, buffers and geometry (M = batch x seq rows of the residual stream).
+struct Stack {
+    const bd_block_weights* blocks;
+    int depth, M, batch, seq, D, heads;
+    float ln_eps, rms_eps;
+    BlockBufs b;
+    bool lat;                        // latency forms (bd_betr_weights.latency_mode at one or two poses): attention's, and the QK16 swap (plan_stack)
+    int n_prefix;                    // DINOv2: cls + registers lead every image's tokens
+    const int32_t* query_idx;        // BETR: the last block runs the query view's P rows per sample past K / V ...
+    int P;
+    float* xc;                       // ... on this compact fp32 stream [batch * P, D]
+};
+
+// Attention forms.  PREFIX_SKIP (last DINOv2 block): the prefix rows are never read again, so their attention is skipped
+// (bd_attention_prefix) -- proj and the MLP then run on stale attention rows there, whose results nobody consumes (row-wise operators:
+// nothing leaks into the patch rows).  QUERY_ONLY (last BETR block): its output is consumed for the query view only (betr.py:303), so
+// only K / V need every token: LN1 + QKV (+ q/k RMSNorm) run on all rows, attention takes queries from the query view's P rows and
+// writes a compact [B*P, D] result, proj, LN2 and the MLP run on those B*P rows (1/T of the work).  Row-wise arithmetic is unchanged,
+// so the result is bit-identical to the full-width block.
+enum { ATTN_FULL, ATTN_PREFIX_SKIP, ATTN_QUERY_ONLY };
+
+// How one transformer block runs: its entry in the stack's schedule (plan_stack), complete before the first launch of the call.
 struct BlockPlan {
+    const bd_block_weights* w;
+    int prec;                        // the block's precision (wprec after the latency-forms swap)
     int base;                        // operand class of the un-promoted Linears
-    int c_qkv, c_proj, c_fc1, c_fc2; // operand class per Linear
+    int c_qkv, c_proj, c_fc1, c_fc2; // operand class per Linear (F16C8 family: per-Linear promotion to split-f16; e4m3: to bf16)
     bool hyb;                        // attention as ONE f16 pass on a single f16 q, k, v plane (q, k RMS-normalised)
     bool qk16;                       // BETR's QKV Linear split by column (q, k one f16 pass on the f16 plane, v the full F16C8 product)
     int qkv_out;                     // output kind of the QKV GEMM
     int aprec_in;                    // class of the attention input (for the stand-alone q/k RMSNorm)
     int aprec;                       // bd_attention precision code (input form x class of proj's A operand)
+    int attn;                        // ATTN_*
+    int Mr;                          // rows of the residual side: the stream's M, or the query view's B*P rows (ATTN_QUERY_ONLY)
+    float* x;                        // fp32 stream of the residual side: BlockBufs.x, or Stack.xc
+    bool rms_fused;                  // q/k RMSNorm in the QKV launch's epilogue
+    bool ln1_folded;                 // LayerNorm 1 folded behind the previous block's fc2
+    bool emit_next;                  // fc2 emits the operand copy / row statistics for the next block's folded LayerNorm 1
+    bool fold2;                      // LayerNorm 2 folded between proj and fc1
+    bool proj_c8, proj_f32, fc2_c8, fc2_f32;    // the 3-byte residual stream (plan_resid)
+    bool sk;                         // split-K scratch lent to proj and fc2
 };
 inline BlockPlan plan_block(const bd_block_weights& w, int wprec) {
     BlockPlan p{};
+    p.w = &w;
+    p.prec = wprec;
     p.base = gemm_prec(wprec);
     const bool c8 = p.base == BD_PREC_F16C8, f8 = p.base == BD_PREC_FP8, normed = w.q_norm_w != nullptr;
     const int pm = (c8 || f8) ? norm_promote(w.promote) : 0;
@@ -111,219 +146,175 @@ inline BlockPlan plan_block(const bd_block_weights& w, int wprec) {
     return p;
 }
 
-// ---- LayerNorm fold (ABI 8, include/boxdreamer_hip.h bd_gemm_args.ln_*): between a residual Linear (proj, fc2) and the Linear(s) behind the
+// ---- The Linear launches of a block, built from its schedule entry.  The planner hands candidate entries to bd_gemm_takes_ln_fold /
+// bd_gemm_fuses_qk_rmsnorm, run_block hands the final entry to bd_gemm: both see the same arguments.
+struct Lin { bd_gemm_args g; int cls; };
+inline int launch(const Lin& l, void* stream) { return bd_gemm(&l.g, l.cls, stream); }
+inline bool takes_fold(const Lin& l) { return bd_gemm_takes_ln_fold(&l.g, l.cls) != 0; }
+inline void ln_consumer(bd_gemm_args& g, const BlockBufs& b, const float* colsum, float eps) { g.ln_stats_in = b.st; g.ln_colsum = colsum; g.ln_eps = eps; }
+
+// The QKV Linear on the stream's M rows, leaving q, k, v in b.qkv in the form the entry's attention reads.
+// BD_PREC_F16C8_QK16: the QKV Linear of a block whose q, k are RMS-normalised, split by output column (include/boxdreamer_hip.h):
+// LayerNorm 1 emits the F16C8 operand; launch 1 (this one) multiplies its f16 plane with the f16 copy of the q, k weight rows (one MFMA
+// pass), launch 2 (qk16_v_lin) is the full F16C8 product for the v rows.  q, k, v land in one f16 [M, 3D] buffer exactly as the
+// single-launch forms lay them out.
+Lin qkv_lin(const BlockPlan& e, const Stack& s) {
+    const bd_block_weights& w = *e.w;
+    const int D = s.D;
+    const int64_t pD = (int64_t)s.M * D;
+    Lin l;
+    if (e.qk16) {      // rows [0, 2D) of the f16 copy
+        l = {gemm_args(s.b.xn, D, 0, e.ln1_folded ? w.qkv16_f : w.qkv16, D, 2 * D, s.b.qkv, 3 * D, 0, 0, s.M, D, BD_ACT_NONE), BD_PREC_F16};
+        if (e.rms_fused) l.g.rms_parts = 2;
+    } else
+        l = {gemm_args(s.b.xn, D, pD, e.ln1_folded ? w.qkv_f : w.qkv, D, 3 * D, s.b.qkv, 3 * D, 3 * pD, e.qkv_out, s.M, D, BD_ACT_NONE), e.c_qkv};
+    if (e.rms_fused) { l.g.rms_wq = w.q_norm_w; l.g.rms_wk = w.k_norm_w; l.g.rms_eps = s.rms_eps; }
+    if (e.ln1_folded) ln_consumer(l.g, s.b, e.qk16 ? w.qkv16_s : w.qkv_s, s.ln_eps);
+    return l;
+}
+Lin qk16_v_lin(const BlockPlan& e, const Stack& s) {
+    const int D = s.D;
+    bd_linear v = e.ln1_folded ? e.w->qkv_f : e.w->qkv;       // rows [2D, 3D) of the F16C8 weight: both planes advance by 2D rows
+    v.w = (const unsigned short*)v.w + (int64_t)2 * D * D;
+    v.b = v.b + 2 * D;
+    Lin l{gemm_args(s.b.xn, D, (int64_t)s.M * D, v, D, D, (unsigned short*)s.b.qkv + 2 * D, 3 * D, 0, 2 /* f16 plane */, s.M, D, BD_ACT_NONE),
+          BD_PREC_F16C8};
+    l.g.w_plane = (int64_t)3 * D * D;                           // plane 1 still lies one FULL weight plane behind plane 0
+    if (e.ln1_folded) ln_consumer(l.g, s.b, e.w->qkv_s + 2 * D, s.ln_eps);
+    return l;
+}
+// does the QKV launch of this entry take the q/k RMSNorm into its epilogue?
+inline bool qkv_fuses_rms(BlockPlan e, const Stack& s) {
+    e.rms_fused = true;
+    const Lin l = qkv_lin(e, s);
+    return bd_gemm_fuses_qk_rmsnorm(&l.g, l.cls) != 0;
+}
+
+// A residual Linear (proj, fc2): e.x += A W^T + b on e.Mr rows.  LayerNorm fold, producer side: the epilogue also emits the raw row as
+// the F16C8 operand (b.xn) + its row statistics (b.st) for the LayerNorm behind it.  from_copy (3-byte stream): the residual rows are
+// read from that operand copy and the sum is written back there, as fp32 rows too only if f32_too.
+// Split-K scratch: lent on at most as many rows as the region was carved for (the stream's M; the last decoder block's compact rows are fewer).
+Lin resid_lin(const BlockPlan& e, const Stack& s, const void* A, const bd_linear& lin, int K, int cls, bool emit, bool from_copy, bool f32_too) {
+    const int D = s.D;
+    Lin l{gemm_args(A, K, (int64_t)e.Mr * K, lin, K, D, e.x, D, 0, 1, e.Mr, K, BD_ACT_NONE), cls};
+    l.g.resid = e.x; l.g.ldr = D;
+    if (e.sk) l.g.sk_ws = s.b.sk;
+    if (emit || from_copy) { l.g.ln_stats_out = s.b.st; l.g.ln_op_out = s.b.xn; l.g.ln_op_plane = (int64_t)e.Mr * D; l.g.ln_op_ld = D; }
+    if (from_copy) { l.g.ln_resid_in_op = 1; l.g.resid = nullptr; l.g.ldr = 0; l.g.out_f32 = f32_too ? 1 : 0; }
+    return l;
+}
+Lin proj_lin(const BlockPlan& e, const Stack& s) { return resid_lin(e, s, s.b.ao, e.w->proj, s.D, e.c_proj, e.fold2, e.proj_c8, e.proj_f32); }
+Lin fc2_lin(const BlockPlan& e, const Stack& s) { return resid_lin(e, s, s.b.h, e.w->fc2, 4 * s.D, e.c_fc2, e.emit_next, e.fc2_c8, e.fc2_f32); }
+Lin fc1_lin(const BlockPlan& e, const Stack& s) {
+    const int D = s.D;
+    Lin l{gemm_args(s.b.xn, D, (int64_t)e.Mr * D, e.fold2 ? e.w->fc1_f : e.w->fc1, D, 4 * D, s.b.h, 4 * D, (int64_t)e.Mr * 4 * D,
+                    handoff_kind(e.c_fc1, e.c_fc2), e.Mr, D, BD_ACT_GELU), e.c_fc1};
+    if (e.fold2) ln_consumer(l.g, s.b, e.w->fc1_s, s.ln_eps);
+    return l;
+}
+
+// ---- The 3-byte residual stream (bd_gemm_args.ln_resid_in_op, bd_block_weights.ln_resid3): between FOLDED LayerNorms nobody reads the
+// stream as fp32 -- the next reader is a Linear that multiplies the operand copy -- so a residual Linear may read its residual rows from
+// that copy (b.xn) and write the sum back there only.  What decides, per residual Linear:
+//   reads the copy   iff b.xn IS the stream (the LayerNorm in front of it was folded) and the launch has the form (un-promoted F16C8);
+//   writes fp32 too  iff someone reads b.x before the next residual Linear: a LayerNorm kernel, a residual Linear without that form, the
+//                    stack's final norm / the last decoder block's row gather.
+// plan_resid decides the stream between block e and the block behind it (next; its LayerNorms are planned): whether next's proj reads
+// the copy, whether e's fc2 writes the copy and whether fp32 rows too; e's proj writes fp32 rows unless e's fc2 reads the copy.
+void plan_resid(BlockPlan& e, BlockPlan* next, const Stack& s) {
+    if (next && next->ln1_folded && next->fold2 && next->x == s.b.x && next->w->ln_resid3) {
+        BlockPlan c = *next;
+        c.proj_c8 = true;
+        next->proj_c8 = takes_fold(proj_lin(c, s));
+    }
+    if (e.fold2 && e.emit_next && e.w->ln_resid3) {
+        BlockPlan c = e;
+        c.fc2_c8 = true;
+        e.fc2_c8 = takes_fold(fc2_lin(c, s));
+    }
+    e.proj_f32 = !e.fc2_c8;                  // (LayerNorm 2 as a kernel implies !fold2, hence !fc2_c8)
+    e.fc2_f32 = !next || !next->proj_c8;
+}
+
+// ---- The schedule of a stack: one entry per block, every decision taken before the first launch.
+// LayerNorm fold (ABI 8, include/boxdreamer_hip.h bd_gemm_args.ln_*): between a residual Linear (proj, fc2) and the Linear(s) behind the
 // next LayerNorm (fc1; the next block's QKV) of the F16C8 family the LayerNorm launch is replaced by (a) the residual Linear's epilogue
 // emitting the raw row as the F16C8 operand + per-wave-tile (mean, M2) pairs and (b) the consumer's epilogue applying the row statistics to a
 // product with the gain-folded weight (bd_block_weights.qkv_f / fc1_f / qkv16_f).  A hand-off folds only when EVERY launch on both sides has a
 // kernel form for it (bd_gemm_takes_ln_fold) -- un-promoted F16C8 Linears, D = 768; everything else keeps the bd_layernorm launch.  The
 // first LayerNorm of a stack (no residual Linear in front of it) and the stacks' final norms stay kernels.
-inline void ln_consumer(bd_gemm_args& g, const BlockBufs& b, const float* colsum, float eps) { g.ln_stats_in = b.st; g.ln_colsum = colsum; g.ln_eps = eps; }
-inline void ln_producer(bd_gemm_args& g, const BlockBufs& b, int64_t plane, int D) { g.ln_stats_out = b.st; g.ln_op_out = b.xn; g.ln_op_plane = plane; g.ln_op_ld = D; }
-// launch, or (check) only ask whether the launch's kernel form takes the fold fields that are set
-inline int gemm_or_check(bd_gemm_args& g, int cls, void* stream, bool check) {
-    if (check) return bd_gemm_takes_ln_fold(&g, cls) ? BD_OK : BD_ERR_SHAPE;
-    return bd_gemm(&g, cls, stream);
-}
-
-// LayerNorm 1 + QKV Linear (+ q/k RMSNorm) of a block on M rows: leaves q, k, v in b.qkv in the form the plan's attention reads.
-// BD_PREC_F16C8_QK16: the QKV Linear of a block whose q, k are RMS-normalised, split by output column (include/boxdreamer_hip.h):
-// LayerNorm 1 emits the F16C8 operand; launch 1 multiplies its f16 plane with the f16 copy of the q, k weight rows (one MFMA pass,
-// q/k RMSNorm fused where the launch allows it), launch 2 is the full F16C8 product for the v rows.  q, k, v land in one f16
-// [M, 3D] buffer exactly as the single-launch forms lay them out.
-// folded: LayerNorm 1 is folded -- b.xn / b.st already hold the raw operand copy and the row statistics of b.x (the previous block's fc2
-// wrote them); check: launch nothing, return BD_OK iff every launch of the folded form has a kernel form.
-int qkv_stage(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, int M, int D, int heads, float ln_eps, float rms_eps,
-              void* stream, bool folded = false, bool check = false) {
-    const int hd = D / heads;
-    const int64_t pD = (int64_t)M * D, p3D = (int64_t)M * 3 * D;
-    bool rms_fused = false;
-    if (p.qk16) {
-        if (!folded) BD_TRY(bd_layernorm(b.x, D, w.ln1_w, w.ln1_b, ln_eps, b.xn, pD, nullptr, 0, M, D, 0, 0, 0, BD_PREC_F16C8, stream));
-        {
-            bd_gemm_args g = gemm_args(b.xn, D, 0, folded ? w.qkv16_f : w.qkv16, D, 2 * D, b.qkv, 3 * D, 0, 0, M, D, BD_ACT_NONE);      // rows [0, 2D) of the f16 copy
-            g.rms_wq = w.q_norm_w; g.rms_wk = w.k_norm_w; g.rms_eps = rms_eps; g.rms_parts = 2;
-            rms_fused = hd == 96 && bd_gemm_fuses_qk_rmsnorm(&g, BD_PREC_F16);
-            if (!rms_fused) { g.rms_wq = g.rms_wk = nullptr; g.rms_parts = 0; }
-            if (folded) ln_consumer(g, b, w.qkv16_s, ln_eps);
-            BD_TRY(gemm_or_check(g, BD_PREC_F16, stream, check));
+int plan_stack(const Stack& s, int wprec, std::vector<BlockPlan>& sched) {
+    // (latency forms, one or two poses per call: the q, k / v column split of BD_PREC_F16C8_QK16 is two launches of ~20 us each where one
+    // F16C8 QKV launch takes ~26 us -- at these sizes a launch costs its fixed part, not its passes; q, k then carry the full F16C8 product)
+    const int bprec = (s.lat && wprec == BD_PREC_F16C8_QK16) ? BD_PREC_F16C8 : wprec;
+    const int D = s.D;
+    sched.assign(s.depth > 0 ? s.depth : 0, BlockPlan{});
+    for (int i = 0; i < s.depth; ++i) {
+        const bd_block_weights& w = s.blocks[i];
+        BlockPlan& e = sched[i];
+        BlockPlan* prev = i > 0 ? &sched[i - 1] : nullptr;
+        e = plan_block(w, bprec);
+        const bool last = i + 1 == s.depth;
+        e.attn = !last ? ATTN_FULL : (s.query_idx ? ATTN_QUERY_ONLY : (s.n_prefix > 0 && s.seq > s.n_prefix ? ATTN_PREFIX_SKIP : ATTN_FULL));
+        e.Mr = e.attn == ATTN_QUERY_ONLY ? s.batch * s.P : s.M;
+        e.x = e.attn == ATTN_QUERY_ONLY ? s.xc : s.b.x;
+        e.sk = s.b.sk && e.Mr <= BD_SPLITK_MAX_ROWS;
+        // LayerNorm 1 folds behind the previous block's fc2 when both sides have the fold form; the q/k RMSNorm (head_dim 96) fuses
+        // into the QKV launch where that launch, folded or not, allows it
+        const bool rms = w.q_norm_w && D / s.heads == 96;
+        if (prev && prev->c_fc2 == BD_PREC_F16C8 && e.c_qkv == BD_PREC_F16C8 && D == 768 && w.qkv_f.w && w.qkv_s &&
+            (!e.qk16 || (w.qkv16_f.w && w.qkv16_s))) {
+            BlockPlan c = e, cp = *prev;
+            c.ln1_folded = cp.emit_next = true;
+            c.rms_fused = rms && qkv_fuses_rms(c, s);
+            if (takes_fold(fc2_lin(cp, s)) && takes_fold(qkv_lin(c, s)) && (!c.qk16 || takes_fold(qk16_v_lin(c, s)))) {
+                e = c;
+                prev->emit_next = true;
+            }
         }
-        {
-            bd_linear v = folded ? w.qkv_f : w.qkv;                   // rows [2D, 3D) of the F16C8 weight: both planes advance by 2D rows
-            v.w = (const unsigned short*)v.w + (int64_t)2 * D * D;
-            v.b = v.b + 2 * D;
-            bd_gemm_args g = gemm_args(b.xn, D, pD, v, D, D, (unsigned short*)b.qkv + 2 * D, 3 * D, 0, 2 /* f16 plane */, M, D, BD_ACT_NONE);
-            g.w_plane = (int64_t)3 * D * D;                           // plane 1 still lies one FULL weight plane behind plane 0
-            if (folded) ln_consumer(g, b, w.qkv_s + 2 * D, ln_eps);
-            BD_TRY(gemm_or_check(g, BD_PREC_F16C8, stream, check));
+        if (!e.ln1_folded) e.rms_fused = rms && qkv_fuses_rms(e, s);
+        // LayerNorm 2 folds between proj and fc1
+        if (w.fc1_f.w && w.fc1_s && e.c_proj == BD_PREC_F16C8 && e.c_fc1 == BD_PREC_F16C8 && e.c_fc2 == BD_PREC_F16C8 && D == 768) {
+            BlockPlan c = e;
+            c.fold2 = true;
+            e.fold2 = takes_fold(proj_lin(c, s)) && takes_fold(fc1_lin(c, s));
         }
-    } else {
-        if (!folded) BD_TRY(bd_layernorm(b.x, D, w.ln1_w, w.ln1_b, ln_eps, b.xn, pD, nullptr, 0, M, D, 0, 0, 0, p.c_qkv, stream));
-        bd_gemm_args g = gemm_args(b.xn, D, pD, folded ? w.qkv_f : w.qkv, D, 3 * D, b.qkv, 3 * D, p3D, p.qkv_out, M, D, BD_ACT_NONE);
-        if (w.q_norm_w && hd == 96) {            // q/k RMSNorm in the QKV epilogue where the launch allows it
-            g.rms_wq = w.q_norm_w; g.rms_wk = w.k_norm_w; g.rms_eps = rms_eps;
-            rms_fused = bd_gemm_fuses_qk_rmsnorm(&g, p.c_qkv);
-            if (!rms_fused) g.rms_wq = g.rms_wk = nullptr;
-        }
-        if (folded) ln_consumer(g, b, w.qkv_s, ln_eps);
-        BD_TRY(gemm_or_check(g, p.c_qkv, stream, check));
+        if (prev) plan_resid(*prev, &e, s);
     }
-    if (check) return BD_OK;
-    if (w.q_norm_w && !rms_fused) BD_TRY(bd_qk_rmsnorm(b.qkv, p3D, w.q_norm_w, w.k_norm_w, rms_eps, M, heads, hd, p.aprec_in, stream));
-    return BD_OK;
-}
-
-// may LayerNorm 1 of block `w` be folded (its QKV launches on M rows)?
-inline bool ln1_foldable(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, int M, int D, int heads, float ln_eps, float rms_eps) {
-    if (!w.qkv_f.w || !w.qkv_s || p.c_qkv != BD_PREC_F16C8 || D != 768) return false;
-    if (p.qk16 && (!w.qkv16_f.w || !w.qkv16_s)) return false;
-    return qkv_stage(w, p, b, M, D, heads, ln_eps, rms_eps, nullptr, true, true) == BD_OK;
-}
-
-// The residual side of a block as bd_gemm launches.  3-byte residual stream (bd_gemm_args.ln_resid_in_op, bd_block_weights.ln_resid3): between
-// FOLDED LayerNorms nobody reads the stream as fp32 -- the next reader is a Linear that multiplies the operand copy -- so a residual Linear
-// may read its residual rows from that copy (b.xn) and write the sum back there only.  What decides, per residual Linear:
-//   reads the copy   iff b.xn IS the stream (the LayerNorm in front of it was folded) and the launch has the form (un-promoted F16C8);
-//   writes fp32 too  iff someone reads b.x before the next residual Linear: a LayerNorm kernel, a residual Linear without that form, the
-//                    stack's final norm / the last decoder block's row gather (need_f32_out).
-// x_stale (in / out): b.x does not hold the stream (the previous residual Linear wrote the copy only).
-struct ResidPlan { bool fold2, proj_c8, proj_f32, fc2_c8, fc2_f32; };
-
-// split-K scratch: lent to a residual Linear on at most as many rows as the region was carved for (the stream's M; the last decoder
-// block's compact rows are fewer)
-inline void lend_sk(bd_gemm_args& g, const BlockBufs& b) { if (b.sk && g.M <= BD_SPLITK_MAX_ROWS) g.sk_ws = b.sk; }
-inline bd_gemm_args proj_args(const bd_block_weights& w, const BlockBufs& b, float* x, int Mr, int D) {
-    bd_gemm_args g = gemm_args(b.ao, D, (int64_t)Mr * D, w.proj, D, D, x, D, 0, 1, Mr, D, BD_ACT_NONE);
-    g.resid = x; g.ldr = D;
-    lend_sk(g, b);
-    return g;
-}
-inline bd_gemm_args fc2_args(const bd_block_weights& w, const BlockBufs& b, float* x, int Mr, int D) {
-    bd_gemm_args g = gemm_args(b.h, 4 * D, (int64_t)Mr * 4 * D, w.fc2, 4 * D, D, x, D, 0, 1, Mr, 4 * D, BD_ACT_NONE);
-    g.resid = x; g.ldr = D;
-    lend_sk(g, b);
-    return g;
-}
-// the same launch reading its residual from the operand copy (and writing fp32 rows only if asked)
-inline void resid_from_copy(bd_gemm_args& g, const BlockBufs& b, int64_t plane, int D, bool f32_too) {
-    ln_producer(g, b, plane, D);
-    g.ln_resid_in_op = 1; g.resid = nullptr; g.ldr = 0;
-    g.out_f32 = f32_too ? 1 : 0;
-}
-inline bool fold2_possible(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, float* x, int Mr, int D, float ln_eps) {
-    if (!(w.fc1_f.w && w.fc1_s && p.c_proj == BD_PREC_F16C8 && p.c_fc1 == BD_PREC_F16C8 && p.c_fc2 == BD_PREC_F16C8 && D == 768)) return false;
-    bd_gemm_args cp = proj_args(w, b, x, Mr, D), c1 = gemm_args(b.xn, D, (int64_t)Mr * D, w.fc1_f, D, 4 * D, b.h, 4 * D, (int64_t)Mr * 4 * D, 0, Mr, D, BD_ACT_GELU);
-    ln_producer(cp, b, (int64_t)Mr * D, D);
-    ln_consumer(c1, b, w.fc1_s, ln_eps);
-    return bd_gemm_takes_ln_fold(&cp, p.c_proj) && bd_gemm_takes_ln_fold(&c1, p.c_fc1);
-}
-// can this block's proj read its residual from the operand copy (given that its LayerNorm 1 is folded)?
-inline bool proj_c8_possible(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, float* x, int Mr, int D, float ln_eps) {
-    if (!w.ln_resid3 || !fold2_possible(w, p, b, x, Mr, D, ln_eps)) return false;
-    bd_gemm_args g = proj_args(w, b, x, Mr, D);
-    resid_from_copy(g, b, (int64_t)Mr * D, D, false);
-    return bd_gemm_takes_ln_fold(&g, p.c_proj) != 0;
-}
-inline ResidPlan plan_resid(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, float* x, int Mr, int D, float ln_eps,
-                            bool emit_next, bool xn_is_stream, bool next_proj_c8, bool need_f32_out) {
-    ResidPlan r{};
-    r.fold2 = fold2_possible(w, p, b, x, Mr, D, ln_eps);
-    if (r.fold2 && emit_next && w.ln_resid3) {
-        bd_gemm_args g = fc2_args(w, b, x, Mr, D);
-        resid_from_copy(g, b, (int64_t)Mr * D, D, false);
-        r.fc2_c8 = bd_gemm_takes_ln_fold(&g, p.c_fc2) != 0;
+    if (s.depth > 0) plan_resid(sched.back(), nullptr, s);
+    // b.x stale (the previous fc2 wrote the copy only) must meet a proj that reads the copy, and the stack must end with fp32 rows (final
+    // norm, head gather): plan_resid looks ahead so that neither can fail, and a failure here enqueues nothing
+    bool stale = false;
+    for (const BlockPlan& e : sched) {
+        if (stale && !e.proj_c8) return BD_ERR_SHAPE;
+        stale = e.fc2_c8 && !e.fc2_f32;
     }
-    r.proj_c8 = xn_is_stream && proj_c8_possible(w, p, b, x, Mr, D, ln_eps);
-    r.proj_f32 = !r.fc2_c8;                                  // (LayerNorm 2 as a kernel implies !fold2, hence !fc2_c8)
-    r.fc2_f32 = need_f32_out || !next_proj_c8;
-    return r;
+    return stale ? BD_ERR_SHAPE : BD_OK;
 }
 
-// x += proj(ao); x += fc2(gelu(fc1(LN2 x)))  on Mr rows (the whole stream, or the query view's compact rows of the last block).
-// emit_next: the NEXT block's LayerNorm 1 is folded -- fc2 also writes the operand copy / row statistics of the rows it completes.
-// xn_is_stream: b.xn holds the stream's operand copy (this block's LayerNorm 1 was folded); next_proj_c8: the next block's proj can read it
-// from there; x_stale: see above (in: b.x is stale, out: it is stale after this block).
-int proj_mlp_stage(const bd_block_weights& w, const BlockPlan& p, const BlockBufs& b, float* x, int Mr, int D, float ln_eps, void* stream,
-                   bool emit_next = false, bool xn_is_stream = false, bool next_proj_c8 = false, bool need_f32_out = true,
-                   bool x_stale = false, bool* x_stale_out = nullptr) {
-    const int64_t rD = (int64_t)Mr * D, r4D = (int64_t)Mr * 4 * D;
-    const ResidPlan r = plan_resid(w, p, b, x, Mr, D, ln_eps, emit_next, xn_is_stream, next_proj_c8, need_f32_out);
-    if (x_stale && !r.proj_c8) return BD_ERR_SHAPE;          // (the previous block's plan looked ahead: cannot happen)
-    bd_gemm_args gp = proj_args(w, b, x, Mr, D);
-    if (r.proj_c8) resid_from_copy(gp, b, rD, D, r.proj_f32);
-    else if (r.fold2) ln_producer(gp, b, rD, D);
-    BD_TRY(bd_gemm(&gp, p.c_proj, stream));
-    bd_gemm_args g1 = r.fold2 ? gemm_args(b.xn, D, rD, w.fc1_f, D, 4 * D, b.h, 4 * D, r4D, 0, Mr, D, BD_ACT_GELU)
-                              : gemm_args(b.xn, D, rD, w.fc1, D, 4 * D, b.h, 4 * D, r4D, handoff_kind(p.c_fc1, p.c_fc2), Mr, D, BD_ACT_GELU);
-    if (r.fold2) ln_consumer(g1, b, w.fc1_s, ln_eps);
-    else BD_TRY(bd_layernorm(x, D, w.ln2_w, w.ln2_b, ln_eps, b.xn, rD, nullptr, 0, Mr, D, 0, 0, 0, p.c_fc1, stream));
-    BD_TRY(bd_gemm(&g1, p.c_fc1, stream));
-    bd_gemm_args g2 = fc2_args(w, b, x, Mr, D);
-    if (r.fc2_c8) resid_from_copy(g2, b, rD, D, r.fc2_f32);
-    else if (emit_next) ln_producer(g2, b, rD, D);
-    BD_TRY(bd_gemm(&g2, p.c_fc2, stream));
-    if (x_stale_out) *x_stale_out = r.fc2_c8 && !r.fc2_f32;
-    return BD_OK;
-}
-
-// does the NEXT block's LayerNorm 1 fold behind this block's fc2 (M rows of the stream on both sides)?
-inline bool next_ln1_folds(const bd_block_weights& w, const BlockPlan& p, const bd_block_weights* next, int wprec, const BlockBufs& b, int M, int D,
-                           int heads, float ln_eps, float rms_eps) {
-    if (!next || p.c_fc2 != BD_PREC_F16C8 || D != 768) return false;
-    bd_gemm_args g = fc2_args(w, b, b.x, M, D);
-    ln_producer(g, b, (int64_t)M * D, D);
-    if (!bd_gemm_takes_ln_fold(&g, p.c_fc2)) return false;
-    const BlockPlan pn = plan_block(*next, wprec);
-    return ln1_foldable(*next, pn, b, M, D, heads, ln_eps, rms_eps);
-}
-
-// One pre-LN transformer block: x += proj(attn(LN1 x)); x += fc2(gelu(fc1(LN2 x))).
+// One pre-LN transformer block as its entry says: x += proj(attn(LN1 x)); x += fc2(gelu(fc1(LN2 x))).
 // BETR: blocks.py:876-886 (+ q/k RMSNorm :257); DINOv2: layers/block.py:89-114 (LayerScale folded).
-// n_prefix > 0 (DINOv2: cls + registers lead every image's tokens) and prefix_queries == false: the block's prefix rows are never read
-// again (last encoder block), so their attention is skipped (bd_attention_prefix) -- proj and the MLP then run on stale attention
-// rows there, whose results nobody consumes (row-wise operators: nothing leaks into the patch rows).
-// ln1_folded (in): this block's LayerNorm 1 is folded (the previous block's fc2 emitted for it); returns through *next_folded whether the
-// next block's is (this block's fc2 then emitted).
-// x_stale (in / out) and next_needs_f32: the 3-byte residual stream (proj_mlp_stage); next_compact: the next block runs its residual side on
-// other rows (the last decoder block), so its proj cannot read this block's copy.
-int run_block(const bd_block_weights& w, const BlockBufs& b, int M, int batch, int seq, int D, int heads, float ln_eps, float rms_eps,
-              int wprec, void* stream, int n_prefix = 0, bool prefix_queries = true, bool ln1_folded = false,
-              const bd_block_weights* next = nullptr, bool* next_folded = nullptr, bool* x_stale = nullptr, bool next_compact = false,
-              bool latency = false) {
-    const BlockPlan p = plan_block(w, wprec);
-    const int hd = D / heads;
-    BD_TRY(qkv_stage(w, p, b, M, D, heads, ln_eps, rms_eps, stream, ln1_folded));
+int run_block(const BlockPlan& e, const Stack& s, void* stream) {
+    const bd_block_weights& w = *e.w;
+    const BlockBufs& b = s.b;
+    const int D = s.D, hd = D / s.heads;
+    const int64_t pD = (int64_t)s.M * D, rD = (int64_t)e.Mr * D;
+    if (!e.ln1_folded) BD_TRY(bd_layernorm(b.x, D, w.ln1_w, w.ln1_b, s.ln_eps, b.xn, pD, nullptr, 0, s.M, D, 0, 0, 0, e.c_qkv, stream));
+    BD_TRY(launch(qkv_lin(e, s), stream));
+    if (e.qk16) BD_TRY(launch(qk16_v_lin(e, s), stream));
+    if (w.q_norm_w && !e.rms_fused) BD_TRY(bd_qk_rmsnorm(b.qkv, 3 * pD, w.q_norm_w, w.k_norm_w, s.rms_eps, s.M, s.heads, hd, e.aprec_in, stream));
     const float scale = 1.0f / sqrtf((float)hd);
-    if (n_prefix > 0 && seq > n_prefix && !prefix_queries)
-        BD_TRY(bd_attention_prefix(b.qkv, (int64_t)M * 3 * D, b.ao, (int64_t)M * D, batch, seq, heads, hd, scale, n_prefix, 0, p.aprec, stream));
+    const bool qo = e.attn == ATTN_QUERY_ONLY;
+    if (e.attn == ATTN_PREFIX_SKIP)
+        BD_TRY(bd_attention_prefix(b.qkv, 3 * pD, b.ao, pD, s.batch, s.seq, s.heads, hd, scale, s.n_prefix, 0, e.aprec, stream));
     else
-        BD_TRY(bd_attention_q_forms(b.qkv, (int64_t)M * 3 * D, b.ao, (int64_t)M * D, batch, seq, heads, hd, scale, nullptr, seq, p.aprec,
-                                    latency ? 1 : 0, stream));
-    const bool emit = next_ln1_folds(w, p, next, wprec, b, M, D, heads, ln_eps, rms_eps);
-    if (next_folded) *next_folded = emit;
-    bool next_c8 = false;
-    if (emit && next && !next_compact) {
-        const BlockPlan pn = plan_block(*next, wprec);
-        next_c8 = proj_c8_possible(*next, pn, b, b.x, M, D, ln_eps);
-    }
-    const bool stale_in = x_stale ? *x_stale : false;
-    // fp32 rows after this block: the stack's last block (final norm / head), or a next block that gathers rows from b.x
-    return proj_mlp_stage(w, p, b, b.x, M, D, ln_eps, stream, emit, ln1_folded, next_c8, /*need_f32_out=*/next == nullptr || next_compact, stale_in, x_stale);
-}
-
-// Last decoder block: its output is consumed for the query view only (betr.py:303), so only K/V need every token.
-// LN1 + QKV (+ q/k RMSNorm) run on all rows; attention takes queries from the query view's P rows and writes a
-// compact [B*P, D] result; proj, LN2 and the MLP then run on B*P rows (1/T of the work).  Row-wise arithmetic is
-// unchanged, so the result is bit-identical to the full-width block.  xc: fp32 [B*P, D] compact residual stream.
-int run_last_block_query_only(const bd_block_weights& w, const BlockBufs& b, float* xc, const int32_t* query_idx, int B, int T, int P,
-                              int D, int heads, float ln_eps, float rms_eps, int wprec, void* stream, bool ln1_folded = false,
-                              bool latency = false) {
-    const BlockPlan p = plan_block(w, wprec);
-    const int hd = D / heads, M = B * T * P, Mq = B * P;
-    BD_TRY(qkv_stage(w, p, b, M, D, heads, ln_eps, rms_eps, stream, ln1_folded));
-    BD_TRY(bd_attention_q_forms(b.qkv, (int64_t)M * 3 * D, b.ao, (int64_t)Mq * D, B, T * P, heads, hd, 1.0f / sqrtf((float)hd), query_idx, P,
-                                p.aprec, latency ? 1 : 0, stream));
-    BD_TRY(bd_gather_query_rows_f32(b.x, query_idx, xc, B, T, P, D, stream));
-    return proj_mlp_stage(w, p, b, xc, Mq, D, ln_eps, stream);
+        BD_TRY(bd_attention_q_forms(b.qkv, 3 * pD, b.ao, rD, s.batch, s.seq, s.heads, hd, scale, qo ? s.query_idx : nullptr, qo ? s.P : s.seq,
+                                    e.aprec, s.lat ? 1 : 0, stream));
+    if (qo) BD_TRY(bd_gather_query_rows_f32(b.x, s.query_idx, e.x, s.batch, s.seq / s.P, s.P, D, stream));
+    BD_TRY(launch(proj_lin(e, s), stream));
+    if (!e.fold2) BD_TRY(bd_layernorm(e.x, D, w.ln2_w, w.ln2_b, s.ln_eps, b.xn, rD, nullptr, 0, e.Mr, D, 0, 0, 0, e.c_fc1, stream));
+    BD_TRY(launch(fc1_lin(e, s), stream));
+    return launch(fc2_lin(e, s), stream);
 }
 
 BlockBufs carve_block(Carver& c, int64_t M, int D, int np, bool latency) {
@@ -402,7 +393,12 @@ extern "C" int bd_encoder_forward(const bd_dino_weights* w, const void* images, 
     const EncBufs e = carve_encoder(w, n_images, prec, workspace);
     if (workspace_bytes < e.bytes) return BD_ERR_WORKSPACE;
     const int P = w->grid * w->grid, D = w->dim, tpi = P + w->n_prefix;
-    const int Mp = n_images * P, Md = n_images * tpi;
+    const int Mp = n_images * P;
+    Stack s{};
+    s.blocks = w->blocks; s.depth = w->depth; s.b = e.blk;
+    s.M = n_images * tpi; s.batch = n_images; s.seq = tpi; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.n_prefix = w->n_prefix;
+    std::vector<BlockPlan> sched;
+    BD_TRY(plan_stack(s, wprec, sched));
     if (e.blk.sk && hipMemsetAsync(e.blk.sk, 0, e.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
 
     // K1+K2: normalise + im2col, then the patch-embed GEMM scattering rows b*P+p -> b*tpi+n_prefix+p and
@@ -418,14 +414,7 @@ extern "C" int bd_encoder_forward(const bd_dino_weights* w, const void* images, 
         BD_TRY(bd_gemm(&g, c_pe, stream));
     }
     BD_TRY(bd_write_prefix_tokens(e.blk.x, w->prefix_tokens, n_images, tpi, w->n_prefix, D, stream));
-    bool folded = false, stale = false;      // LayerNorm 1 of block i is folded behind block i-1's fc2 (never block 0's); b.x is stale
-    for (int i = 0; i < w->depth; ++i) {
-        bool next_folded = false;
-        BD_TRY(run_block(w->blocks[i], e.blk, Md, n_images, tpi, D, w->heads, w->ln_eps, 0.f, wprec, stream, w->n_prefix, i + 1 < w->depth,
-                         folded, i + 1 < w->depth ? &w->blocks[i + 1] : nullptr, &next_folded, &stale));
-        folded = next_folded;
-    }
-    if (stale) return BD_ERR_SHAPE;          // (the last block writes fp32 rows: the final norm reads them)
+    for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
     // final LayerNorm on the patch tokens only (vision_transformer.py:263-267); feats16 in the class the consumer's first Linear reads
     BD_TRY(bd_layernorm(e.blk.x, D, w->norm_w, w->norm_b, w->ln_eps, feats16, feats16_plane, feats32, D, Mp, D, P, tpi,
                         w->n_prefix, feats_prec, stream));
@@ -453,6 +442,14 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
     const int P = w->grid * w->grid, D = w->dim, F = w->patch * w->patch * w->box_dim;
     const int Mb = B * T * P, Mq = B * P;
     const int64_t pD = (int64_t)Mb * D;
+    // K9: joint self-attention over all T*P tokens of a sample; the last block runs the query view's rows only past K / V, on d.t2 (dead
+    // since the adapter) as its compact stream
+    Stack s{};
+    s.blocks = w->blocks; s.depth = w->depth; s.b = d.blk;
+    s.M = Mb; s.batch = B; s.seq = T * P; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.rms_eps = w->rms_eps;
+    s.lat = w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
+    std::vector<BlockPlan> sched;
+    BD_TRY(plan_stack(s, wprec, sched));
     if (d.blk.sk && hipMemsetAsync(d.blk.sk, 0, d.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
 
     // operand classes of the Linears outside the blocks (F16C8 family: per-Linear promotion, include/boxdreamer_hip.h)
@@ -481,22 +478,7 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
         BD_TRY(bd_gemm(&g, c_be, stream));
     }
     BD_TRY(bd_query_substitute(d.blk.x, d.rgb, w->pos_table, w->query_token, query_idx, B, T, P, D, stream));
-    // K9: joint self-attention over all T*P tokens of a sample
-    // (latency forms, one or two poses per call: the q, k / v column split of BD_PREC_F16C8_QK16 is two launches of ~20 us each where one
-    // F16C8 QKV launch takes ~26 us -- at these sizes a launch costs its fixed part, not its passes; q, k then carry the full F16C8 product)
-    const bool lat = w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS;
-    const int bprec = (lat && wprec == BD_PREC_F16C8_QK16) ? BD_PREC_F16C8 : wprec;
-    bool folded = false, stale = false;      // LayerNorm 1 of block i is folded behind block i-1's fc2 (never block 0's); b.x is stale
-    for (int i = 0; i + 1 < w->depth; ++i) {
-        bool next_folded = false;
-        BD_TRY(run_block(w->blocks[i], d.blk, Mb, B, T * P, D, w->heads, w->ln_eps, w->rms_eps, bprec, stream, 0, true, folded,
-                         &w->blocks[i + 1], &next_folded, &stale, /*next_compact=*/i + 2 == w->depth, lat));
-        folded = next_folded;
-    }
-    if (stale) return BD_ERR_SHAPE;          // (the block in front of the last one writes fp32 rows: the last block gathers its query rows from them)
-    // last block: query-view rows only past the K/V projection; d.t2 (dead since the adapter) holds the compact stream
-    BD_TRY(run_last_block_query_only(w->blocks[w->depth - 1], d.blk, d.t2, query_idx, B, T, P, D, w->heads,
-                                     w->ln_eps, w->rms_eps, bprec, stream, folded, lat));
+    for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
     // K10: head on the query view's tokens (no final norm, betr.py:298-306)
     BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c_bp, stream));
     {
