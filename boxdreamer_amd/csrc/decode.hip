@@ -133,7 +133,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ h
 // better_nb).  A one-wave-per-SIMD variant (256 threads x 196 registers) was slower: the scans and the rounds are dependent chains of
 // VALU -> SALU -> VALU hand-offs (~10-20 cycles per instruction for a lone wave; a build cut after each phase: loads 5 us, first scan 27 us, rounds 31 us),
 // which four waves per SIMD interleave.  Same total order, same tie rule, same arithmetic as decode_kernel: bit-identical corners and
-// index lists (tests/test_gpu_ops.py, tests/test_gpu_fuzz.py).
+// index lists (tests/test_gpu_ops.py, tests/test_gpu_fuzz.py; tests/test_gpu_steered.py steers the picks onto one or two threads, so that
+// the promotion of the second candidate, the register rescan and its tie filter decide them, at every size from hw = 1 to 224 x 224).
 // `better` without short-circuit evaluation: hipcc compiles && / || on per-lane conditions into EXEC-mask branches (a dozen scalar
 // instructions and a branch per element of the unrolled register scans below); bitwise forms stay two compares and an s_and / s_or
 __device__ __forceinline__ bool better_nb(float v, int i, float bv, int bi) { return (v > bv) | ((v == bv) & (i < bi)); }
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(1024) void decode_kernel_regs(const float* __restri
 #pragma unroll
     for (int j = 0; j < NE; ++j) {
         const int i = tid + 1024 * j;
-        const float x = (h[i < hw ? i : tid] + 1.0f) / 2.0f;     // box_utils.py:79
+        const float x = (h[i < hw ? i : 0] + 1.0f) / 2.0f;       // box_utils.py:79 (lanes past the map read element 0 and discard it)
         v[j] = i < hw ? x : __builtin_nanf("");
     }
     float c1v, c2v;

@@ -74,7 +74,10 @@ __global__ __launch_bounds__(64) void match_scores_kernel(const float* __restric
     }
 }
 
-// top-k mask per row (N <= 1024): k rounds of (largest value, then lowest index), one workgroup per row
+// top-k mask per row (N <= 1024): k rounds of (largest value, then lowest index), one workgroup per row.  A round picks the best
+// entry strictly AFTER the previous pick (pv, pi) in that order, so a picked entry is excluded by its place, not by its value:
+// -inf scores are ordinary values here (a row with fewer than k finite scores takes its lowest-index -inf entries next).
+// NaN scores are not ordered and never picked; the product path removes them (match_scores_kernel: nan_to_num).
 __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict__ scores, int N, int k,
                                                          unsigned char* __restrict__ mask) {
     __shared__ float val[MAXL];
@@ -83,9 +86,15 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     for (int i = tid; i < N; i += 256) { val[i] = scores[(int64_t)b * N + i]; mask[(int64_t)b * N + i] = 0; }
     __syncthreads();
+    float pv = INFINITY;
+    int pi = -1;
     for (int round = 0; round < k; ++round) {
         float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < N; i += 256) if (val[i] > bv || (val[i] == bv && i < bi)) { bv = val[i]; bi = i; }
+        for (int i = tid; i < N; i += 256) {
+            const float v = val[i];
+            const bool after = v < pv || (v == pv && i > pi);
+            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
@@ -93,11 +102,11 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
         }
         if (lane == 0) { wv[wid] = bv; wi[wid] = bi; }
         __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; ++w) if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
-            if (bi < N) { mask[(int64_t)b * N + bi] = 1; val[bi] = -INFINITY; }
-        }
-        __syncthreads();
+        bv = wv[0]; bi = wi[0];
+        for (int w = 1; w < 4; ++w) if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
+        if (tid == 0 && bi < N) mask[(int64_t)b * N + bi] = 1;
+        pv = bv; pi = bi;
+        __syncthreads();                    // wv / wi are rewritten in the next round
     }
 }
 

@@ -309,7 +309,9 @@ int bd_dino_match_scores(const float* feats, const void* images, int img_dtype, 
                          int L, int D, int H, int W, float lum_threshold, float* sums, float* counts, float* scores,
                          void* stream);
 
-/* Boolean top-k mask per row of scores [B, N] (matching.py:167-173): k largest, ties to the lower index. mask: uint8 [B, N]. */
+/* Boolean top-k mask per row of scores [B, N] (matching.py:167-173): k largest, ties to the lower index. mask: uint8 [B, N].
+ * Every row gets exactly k ones; -inf scores rank below every finite score (and among themselves by index).  NaN scores are
+ * unordered and never selected: callers pass NaN-free rows (bd_dino_match_scores writes none). */
 int bd_topk_mask(const float* scores, int B, int N, int k, unsigned char* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------
