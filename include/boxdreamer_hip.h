@@ -314,6 +314,23 @@ int bd_dino_match_scores(const float* feats, const void* images, int img_dtype, 
  * unordered and never selected: callers pass NaN-free rows (bd_dino_match_scores writes none). */
 int bd_topk_mask(const float* scores, int B, int N, int k, unsigned char* mask, void* stream);
 
+/* Eval-step pose metrics: the per-sample values of Metrics.compute_metrics, src/lightning/utils/metrics/metric_utils.py:97-128
+ * (query_pose_error :162-211, process_single_bs_2d :255-306 with project_optimized :224-239, process_single_bs_add :331-424).
+ * Per pose b (the query view, gathered by the caller): pred_poses / original_poses fp32 [n_poses, 4, 4], scale fp32 [n_poses, 3],
+ * coordinate_transform fp32 [n_poses, 4, 4], original_intrinsics fp32 [n_poses, 3, 3].  The prediction is composed as the
+ * reference does (:480-483, :282-283): pred[:3, 3] *= scale element-wise, then pred @ coordinate_transform.
+ * points: fp32 [*, 3], one packed buffer of model points; pose b uses pt_count[b] points from row pt_offset[b] (int64 / int32
+ * device arrays), so one batch can mix objects.  max_points >= every pt_count[b] (a pose with a count outside [1, max_points]
+ * gets NaN point metrics).  t_scale: 0 = null, 1 = 'm' (t_err x 100), 2 = 'mm' (t_err / 10).
+ * out: fp64 [n_poses, 6] = R_err (deg), t_err, inplane_R_err (deg), proj2d (px), add, adds -- ADD-S is the exact nearest-neighbour
+ * mean (what scipy's cKDTree returns), by direct fp32 differences; the per-pose scalars and all sums are fp64.  Deterministic:
+ * a pose's outputs are bit-identical whatever else is in the batch.  workspace: bd_pose_metrics_workspace_bytes(n_poses, max_points)
+ * bytes, caller-owned scratch. */
+size_t bd_pose_metrics_workspace_bytes(int n_poses, int max_points);
+int bd_pose_metrics(const float* pred_poses, const float* original_poses, const float* scale, const float* coordinate_transform,
+                    const float* original_intrinsics, const float* points, const int64_t* pt_offset, const int32_t* pt_count,
+                    int n_poses, int max_points, int t_scale, void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-path entry points
  * ---------------------------------------------------------------------------------------- */
