@@ -124,7 +124,7 @@ EXPORTS = [
     "bd_dino_match_scores", "bd_topk_mask", "bd_solve_pnp", "bd_gemm_fuses_qk_rmsnorm", "bd_gemm_takes_ln_fold", "bd_gemm_splitk_flag_bytes",
     "bd_gemm_splitk_workspace_bytes", "bd_solve_pnp_host", "bd_attention_prefix",
     "bd_lanes_prepare", "bd_encoder_workspace_bytes_lanes", "bd_encoder_forward_lanes", "bd_decoder_workspace_bytes_lanes",
-    "bd_decoder_forward_lanes", "bd_pose_metrics_workspace_bytes", "bd_pose_metrics",
+    "bd_decoder_forward_lanes", "bd_pose_metrics_workspace_bytes", "bd_pose_metrics", "bd_crop_resize_frames",
 ]
 
 _lib = None
@@ -190,6 +190,7 @@ def load() -> C.CDLL:
     lib.bd_pose_metrics_workspace_bytes.argtypes = [i, i]
     lib.bd_pose_metrics_workspace_bytes.restype = sz
     lib.bd_pose_metrics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp, vp]
+    lib.bd_crop_resize_frames.argtypes = [vp, i, i, i, i64, i64, vp, vp, vp, i, i, vp, i, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:

@@ -176,7 +176,34 @@ class BoxDreamer(nn.Module):
                 "self_check_max_abs_dlogits": rep.get("delta_final"), "self_check_unpromoted": rep.get("delta_unpromoted"),
                 "self_check_budget": rep.get("budget"), "self_check_ok": rep.get("ok")}
 
+    def _images_from_frames(self, data) -> torch.Tensor:
+        """`data["images"]` from raw frames (boxdreamer_amd/preprocess.py): uint8 `frames` [F, H, W, 3] + int32 `crop_boxes` [B, T, 4] on the
+        device, optionally `frame_idx` [B, T] (default: view i reads frame i), `keep_boxes` [B, T, 4] (background masking) and
+        `crop_size` (224) -> [B, T, 3, S, S] in bbox_feat's dtype, ONE launch on the current stream.  With `hip_graph` the launch stays
+        outside the captured graph and writes straight into the graph's static image buffer when one exists for the shape (the replay's
+        input copy of that tensor onto itself is a no-op); `data["images"]` then aliases that buffer until the next forward."""
+        from .preprocess import crop_resize_frames
+        missing = [k for k in ("frames", "crop_boxes") if k not in data]
+        if missing:
+            raise KeyError(f"the batch dict needs 'images', or 'frames' + 'crop_boxes' to make them on the device (missing: {missing})")
+        boxes = data["crop_boxes"]
+        if boxes.dim() != 3 or boxes.shape[-1] != 4:
+            raise ValueError(f"crop_boxes must be int32 [B, T, 4], got {tuple(boxes.shape)}")
+        B, T = boxes.shape[:2]
+        S = int(data.get("crop_size", 224))
+        feat = data.get("bbox_feat")
+        dtype = feat.dtype if isinstance(feat, torch.Tensor) and feat.dtype.is_floating_point else torch.float32
+        out = None
+        g = self._graph if self.hip_graph else None
+        if (g is not None and tuple(g.images.shape) == (B, T, 3, S, S) and g.images.dtype == dtype
+                and g.images.device == data["frames"].device):
+            out = g.images
+        return crop_resize_frames(data["frames"], boxes, frame_idx=data.get("frame_idx"), keep_boxes=data.get("keep_boxes"),
+                                  out_size=S, out=out, dtype=dtype)
+
     def forward(self, data):
+        if "images" not in data:      # opt-in: raw uint8 frames + crop windows in place of the dataset's float crops
+            data["images"] = self._images_from_frames(data)
         images = data["images"]
         B, T = images.shape[:2]
         query_idx = data["query_idx"]

@@ -331,6 +331,27 @@ int bd_pose_metrics(const float* pred_poses, const float* original_poses, const 
                     const float* original_intrinsics, const float* points, const int64_t* pt_offset, const int32_t* pt_count,
                     int n_poses, int max_points, int t_scale, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* Crop + ToTensor + antialiased resize of raw frames: what the reference's dataset does per view on the host
+ * (src/datasets/utils/preprocess.py:123-199 pad_and_resize_image, :202-274 _crop_image with bbox_obj, called from
+ * src/datasets/base.py:541-566; the transform is ToTensor + Resize(img_size, antialias=True)).
+ * frames: device uint8 [n_frames, H, W, 3] (HWC, RGB), row_stride / frame_stride in BYTES (row_stride >= 3 W; no alignment is
+ * required of the base or the strides).  boxes: device int32 [n_crops, 4] = x0 y0 x1 y1, the integer crop window [x0, x1) x [y0, y1),
+ * square (x1 - x0 == y1 - y0 >= 1); it may leave the frame on any side, pixels outside the frame are 0.  frame_idx: device int32
+ * [n_crops], the frame each crop reads, or NULL (crop i reads frame i; then n_crops <= n_frames).  keep_boxes: device int32
+ * [n_crops, 4] or NULL: pixels with x < kx0, x > kx1, y < ky0 or y > ky1 count as 0 (both edges inclusive: ImageDraw.rectangle).
+ * The crop (side s) is resized to out_size x out_size as ATen's _upsample_bilinear2d_aa with align_corners = false does it:
+ * separable triangle filter, scale = s / out_size, support = max(scale, 1), centre c_i = scale (i + 0.5), taps
+ * [max(0, int(c_i - support + 0.5)), min(s, int(c_i + support + 0.5))), weight max(0, 1 - |j - c_i + 0.5| / support), normalised to
+ * sum 1 per output sample; the window is clipped to the CROP (zero padding takes part in the filter).  Tap geometry and weights are
+ * evaluated in fp64, sums are fp32.  The result is value / 255, clamped to [0, 1], rounded once to out_dtype (BD_DTYPE_F32 / F16 /
+ * BF16) and stored CHW: out [n_crops, 3, out_size, out_size], contiguous.
+ * Boxes are device data and cannot be rejected here: a crop whose box is not square, has a side < 1 or > 2^20, or whose frame index
+ * lies outside [0, n_frames) is written as ZEROS.  out_size <= 512, n_crops <= 65535 (BD_ERR_SHAPE otherwise).  One launch, no
+ * workspace, no synchronisation; a crop's bits do not depend on the other crops of the launch. */
+int bd_crop_resize_frames(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
+                          const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int out_size,
+                          void* out, int out_dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-path entry points
  * ---------------------------------------------------------------------------------------- */
