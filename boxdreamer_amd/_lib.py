@@ -125,6 +125,8 @@ EXPORTS = [
     "bd_gemm_splitk_workspace_bytes", "bd_solve_pnp_host", "bd_attention_prefix",
     "bd_lanes_prepare", "bd_encoder_workspace_bytes_lanes", "bd_encoder_forward_lanes", "bd_decoder_workspace_bytes_lanes",
     "bd_decoder_forward_lanes", "bd_pose_metrics_workspace_bytes", "bd_pose_metrics", "bd_crop_resize_frames",
+    "bd_attention_varlen", "bd_query_substitute_varlen", "bd_gather_query_rows_f32_varlen", "bd_gather_query_tokens_varlen",
+    "bd_decoder_workspace_bytes_ragged", "bd_decoder_forward_ragged",
 ]
 
 _lib = None
@@ -191,6 +193,13 @@ def load() -> C.CDLL:
     lib.bd_pose_metrics_workspace_bytes.restype = sz
     lib.bd_pose_metrics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp, vp]
     lib.bd_crop_resize_frames.argtypes = [vp, i, i, i, i64, i64, vp, vp, vp, i, i, vp, i, vp]
+    lib.bd_attention_varlen.argtypes = [vp, i64, vp, i64, vp, i, i, i, i, i, i, f, vp, i, vp]
+    lib.bd_query_substitute_varlen.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
+    lib.bd_gather_query_rows_f32_varlen.argtypes = [vp, vp, vp, vp, i, i, i, vp]
+    lib.bd_gather_query_tokens_varlen.argtypes = [vp, vp, vp, vp, i64, i, i, i, i, vp]
+    lib.bd_decoder_workspace_bytes_ragged.argtypes = [C.POINTER(BetrWeights), i, i, i]
+    lib.bd_decoder_workspace_bytes_ragged.restype = sz
+    lib.bd_decoder_forward_ragged.argtypes = [C.POINTER(BetrWeights), vp, i, vp, i64, vp, vp, i, i, i, i, vp, vp, vp, sz, i, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:
@@ -328,3 +337,57 @@ def same_device(*tensors) -> torch.device:
 def require_gpu() -> None:
     if not torch.cuda.is_available():
         raise HipLibraryError("no HIP device visible: BoxDreamer's MI355X path cannot run (no CPU fallback)")
+
+
+# ---- Ragged batches (bd_attention_varlen / bd_decoder_forward_ragged): host-side bookkeeping.  The per-sample view counts are HOST
+# integers; everything the kernels need on the device is derived from them without reading anything back.
+def view_counts_list(view_counts, B=None):
+    """`view_counts` (a list / tuple of ints or a CPU integer tensor) -> list of Python ints.  A device tensor raises TypeError: reading
+    it would cost a device synchronisation per forward."""
+    if isinstance(view_counts, torch.Tensor):
+        if view_counts.is_cuda:
+            raise TypeError("view_counts must be host integers (a list or a CPU int tensor): reading a device tensor would synchronise "
+                            "the device on every forward")
+        if view_counts.dtype.is_floating_point or view_counts.dtype == torch.bool or view_counts.dim() != 1:
+            raise TypeError(f"view_counts must be a 1-D integer tensor, got {view_counts.dtype} {tuple(view_counts.shape)}")
+        counts = [int(c) for c in view_counts.tolist()]
+    else:
+        counts = list(view_counts)
+        if any(isinstance(c, bool) or int(c) != c for c in counts):
+            raise TypeError("view_counts must be integers")
+        counts = [int(c) for c in counts]
+    if B is not None and len(counts) != B:
+        raise ValueError(f"view_counts has {len(counts)} entries for a batch of {B} samples")
+    return counts
+
+
+def check_view_counts(counts, t_max: int, query_idx=None) -> None:
+    """A sample needs a reference and a query: 2 <= count <= T_max; its query view must be one of its own views."""
+    for b, c in enumerate(counts):
+        if not 2 <= c <= t_max:
+            raise ValueError(f"view_counts[{b}] = {c} is outside [2, {t_max}] (a sample needs a reference and a query, and fits the batch's view slots)")
+    if query_idx is not None:
+        for b, (q, c) in enumerate(zip(query_idx, counts)):
+            if not 0 <= int(q) < c:
+                raise ValueError(f"query_idx[{b}] = {int(q)} is not among the sample's {c} views (view_counts)")
+
+
+def view_starts(counts):
+    """[0, c0, c0 + c1, ...]: sample b owns the views [start[b], start[b + 1]) of the packed batch."""
+    out = [0]
+    for c in counts:
+        out.append(out[-1] + int(c))
+    return out
+
+
+def packing_index(counts, t_max: int):
+    """Flat indices into the (B * T_max) padded view slots of the valid views, sample by sample: packed = padded.flatten(0, 1)[index]."""
+    return [b * t_max + t for b, c in enumerate(counts) for t in range(c)]
+
+
+def attention_work_list(counts, heads: int, tokens_per_view: int, q_block: int, query_only: bool = False):
+    """The (sample, head, q-block) work items of one bd_attention_varlen launch in grid order -- what the kernels derive from view_start
+    (consecutive q-blocks of one (sample, head) are consecutive items, so the XCD remap keeps them on one L2).  Host mirror of the device
+    decomposition, for tests and for sizing: len(...) is the launch's grid."""
+    bpv = tokens_per_view // q_block
+    return [(b, h, q) for b, c in enumerate(counts) for h in range(heads) for q in range(bpv if query_only else c * bpv)]

@@ -111,6 +111,7 @@ class BETR(nn.Module):
         self.validate_inputs = True
         self.mask_error = None
         self.recast_count = 0         # forwards that had to re-cast features lacking an operand copy (features.py)
+        self._ragged_index = {}       # (view counts, T_max, device) -> (packing index, view_start) on the device (ragged batches)
 
     # -- packed-weight cache: invalidated by CONTENT, not by hooks.  The key carries every parameter's storage address
     # and version counter, so a checkpoint loaded through the PARENT module (`BoxDreamer.load_state_dict`, which recurses
@@ -178,15 +179,40 @@ class BETR(nn.Module):
         x = x.reshape(x.shape[0], h, w, p, p, c)
         return torch.einsum("nhwpqc->nchpwq", x).reshape(x.shape[0], c, h * p, h * p)
 
+    def ragged_index(self, counts, t_max: int, dev):
+        """(packing index int64 [n_views], view_start int32 [B + 1]) on `dev` for host view counts: built on the host, uploaded once per
+        distinct (counts, T_max) and kept (a serving process sees the same few mixes again and again)."""
+        key = (tuple(counts), int(t_max), str(dev))
+        hit = self._ragged_index.get(key)
+        if hit is None:
+            if len(self._ragged_index) >= 64:
+                self._ragged_index.clear()
+            hit = (torch.tensor(_lib.packing_index(counts, t_max), dtype=torch.int64).to(dev),
+                   torch.tensor(_lib.view_starts(counts), dtype=torch.int32).to(dev))
+            self._ragged_index[key] = hit
+        return hit
+
     @torch.no_grad()
-    def forward(self, pose_feat, rgbs=None, masks=None, pretrain_rgb_feat=None, image_masks=None):
+    def forward(self, pose_feat, rgbs=None, masks=None, pretrain_rgb_feat=None, image_masks=None, view_counts=None):
         """pose_feat (B,T,8,H,W) in [-1,1]; rgbs (B,T,3,H,W) (shape check only); masks (B,T) bool, one query
-        view per sample; pretrain_rgb_feat (B,T,P,C) from the encoder.  Returns (B,8,H,W) fp32 in [-1,1]."""
+        view per sample; pretrain_rgb_feat (B,T,P,C) from the encoder.  Returns (B,8,H,W) fp32 in [-1,1].
+
+        view_counts (host ints, length B; optional): a RAGGED batch.  The inputs stay (B, T_max, ...); sample b's valid views are the
+        slots [0, view_counts[b]) and its query view (`masks`) must be one of them.  The other slots are never read.  The sample
+        attends over its own views only, on packed token rows (bd_decoder_forward_ragged): its result is bit-identical to the sample
+        run alone at T = view_counts[b].  pretrain_rgb_feat is then either the packed features of the sum(view_counts) valid views,
+        (n_views, P, C) in sample order -- what the encoder returns for the packed images, with its operand copy -- or padded
+        (B, T_max, P, C), which is packed and re-cast here (slow path)."""
         assert rgbs is not None, "rgbs input should not be None"
         B, T, _, H, W = rgbs.shape
         assert H == W == self.img_size, f"H and W should be equal to img_size {self.img_size}, got {H}x{W}"
         if pretrain_rgb_feat is None:
             raise NotImplementedError("the MI355X path requires pretrained RGB features (use_pretrained=True)")
+        if view_counts is not None:
+            counts = _lib.view_counts_list(view_counts, B)
+            _lib.check_view_counts(counts, T)
+            if any(c != T for c in counts):
+                return self._forward_ragged(pose_feat, rgbs, masks, pretrain_rgb_feat, counts)
         _lib.require_gpu()
         lib = _lib.load()
         dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat)
@@ -234,5 +260,58 @@ class BETR(nn.Module):
                                                 B * T * P * D if np_ == 2 else 0, _lib.ptr(query_idx), B, T, H,
                                                 _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, lanes,
                                                 _lib.stream()), "bd_decoder_forward_lanes")
+        self.last_logits = logits
+        return heat
+
+    def _forward_ragged(self, pose_feat, rgbs, masks, pretrain_rgb_feat, counts):
+        """forward() for per-sample view counts that are not all T_max (validated host ints)."""
+        B, T, _, H, W = rgbs.shape
+        _lib.require_gpu()
+        lib = _lib.load()
+        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat)
+        prec = self.hip_precision
+        pid = _lib.prec_id(prec)
+        w = self._weights(dev, prec).struct
+        P, D = w.grid * w.grid, w.dim
+        n_views, max_views = sum(counts), max(counts)
+        if masks.dtype != torch.bool or masks.shape != (B, T):
+            raise ValueError("masks must be a (B, T) bool tensor")
+        if tuple(pose_feat.shape) != (B, T, self.box_dim, H, W):
+            raise ValueError(f"pose_feat must be (B, T, {self.box_dim}, H, W) = {(B, T, self.box_dim, H, W)}, got "
+                             f"{tuple(pose_feat.shape)}")
+        index, view_start = self.ragged_index(counts, T, dev)
+        packed_feats = pretrain_rgb_feat.dim() == 3 and tuple(pretrain_rgb_feat.shape) == (n_views, P, D)
+        if not packed_feats and tuple(pretrain_rgb_feat.shape) != (B, T, P, D):
+            raise ValueError(f"pretrain_rgb_feat must be packed ({n_views}, {P}, {D}) or padded ({B}, {T}, {P}, {D}), got "
+                             f"{tuple(pretrain_rgb_feat.shape)}")
+        if self.validate_inputs and not torch.cuda.is_current_stream_capturing():
+            # exactly one query view per sample, and among the sample's own views (a padded slot is never a view)
+            valid = torch.arange(T, device=dev)[None, :] < (view_start[1:] - view_start[:-1])[:, None]
+            bad = ((masks.sum(dim=1) != 1) | (masks & ~valid).any(dim=1)).any()
+            if self.validate_inputs == "deferred":
+                self.mask_error = bad
+            elif bool(bad):
+                raise ValueError("masks must mark exactly one query view per sample, among the sample's view_counts views")
+        query_view = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
+        np_ = _lib.planes(prec)
+        fcls = self.feats_class(prec)
+        feats16 = features.operand_of(pretrain_rgb_feat, fcls) if packed_feats else None
+        if feats16 is not None and (feats16.numel() != np_ * n_views * P * D or feats16.device != dev):
+            feats16 = None
+        if feats16 is None:
+            self.recast_count += 1
+            if self.recast_count == 1:
+                warnings.warn("BETR: pretrain_rgb_feat carries no operand-dtype copy from the HIP encoder; re-casting it "
+                              "(slow path, see boxdreamer_amd/features.py)", stacklevel=3)
+            f32 = pretrain_rgb_feat if packed_feats else pretrain_rgb_feat.reshape(B * T, P, D).index_select(0, index)
+            feats16 = hip_ops.to_operand(f32.reshape(n_views * P, D).float(), fcls)
+        pose_packed = pose_feat.reshape(B * T, self.box_dim, H, W).index_select(0, index)       # the valid views only: [n_views, 8, H, W]
+        ws = self._workspace(lib.bd_decoder_workspace_bytes_ragged(w, n_views, B, pid), dev)
+        logits = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
+        heat = torch.empty_like(logits)
+        _lib.check(lib.bd_decoder_forward_ragged(w, _lib.ptr(pose_packed), _lib.dtype_id(pose_packed), _lib.ptr(feats16),
+                                                 n_views * P * D if np_ == 2 else 0, _lib.ptr(view_start), _lib.ptr(query_view), B,
+                                                 n_views, max_views, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid,
+                                                 _lib.stream()), "bd_decoder_forward_ragged")
         self.last_logits = logits
         return heat

@@ -32,7 +32,7 @@ SPILL_ALLOWED = {      # regex on the mangled name -> tolerated scratch bytes
     # (round 5: the split-bf16 hd-96 3-wave attention instance lost its 72-byte spill with the buffer-load K / V staging; no allowance left for it)
     # pipelined attention with e4m3 output (the fp8 mode's BETR attention): 3 registers of output addressing stored before the key
     # loop and reloaded after it (once per workgroup; re-deriving them after the loop makes the other output kinds spill instead)
-    r"attn_kernel_ppIDF16bLi96ELi2EE": 16,
+    r"attn_kernel_ppIDF16bLi96ELi2ELb[01]EE": 16,
     # the persistent kernels' GENERIC epilogue (EP 0: table add, row remap, GELU into a foreign operand class) -- the patch-embed and
     # heatmap-embed GEMMs (2 of the 101 launches of a step) and the hand-off GEMMs of promoted Linears; its spills live in the epilogue
     # (profiles/r2_gemm_epilogue.md), the specialised epilogues EP 1-3 that every block Linear takes must stay at zero

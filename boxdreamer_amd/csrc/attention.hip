@@ -41,7 +41,23 @@ struct AttnArgs {
     int q_len;               // number of query rows per sequence (== seq when q_view is NULL)
     int q_off;               // (q_view == NULL) first query row inside every sequence: queries are rows [q_off, q_off + q_len)
     int out_rows;            // rows per sample in `out` (q_len: compact; seq with q_off: the result lands in rows [q_off, q_off + q_len))
+    // Ragged batches (bd_attention_varlen, the VL kernel instances): sample b owns the views [view_start[b], view_start[b + 1]) of `tpv` token
+    // rows each, packed back to back; `seq`, the sample's base row and (without q_view) `q_len` then come from the offsets, per sample.
+    const int32_t* view_start;   // device int32 [batch + 1], or NULL (uniform batch: every sample has `seq` rows)
+    int tpv, n_views, max_views; // token rows per view; host-known total (sizes the grid) and largest per-sample view count (bounds the descriptor)
 };
+
+// (VL) which sample owns work item `wg` when sample i owns the items [view_start[i] * ipv, view_start[i + 1] * ipv): the number of interior
+// offsets at or below wg -- the offsets ascend, so one ballot per 64 samples counts them (zero-view samples own nothing and are skipped).
+__device__ __forceinline__ int vl_sample_of(const int32_t* view_start, int batch, int ipv, int wg, int lane) {
+    int b = 0;
+    for (int i0 = 0; i0 < batch; i0 += 64) {
+        const int i = i0 + lane;
+        const bool below = i < batch && (int64_t)view_start[i + 1] * ipv <= (int64_t)wg;
+        b += __popcll(__ballot(below));
+    }
+    return __builtin_amdgcn_readfirstlane(b);
+}
 
 constexpr int KT = 64;   // keys per tile
 
@@ -62,7 +78,7 @@ __device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return _
 // OUTSPLIT: single-pass f16 attention whose result is written as split-bf16 (hi, lo) planes -- the strict mode's
 // attention (its GEMMs stay split-bf16 x3): q/k are RMS-normalised and P is in [0, 1], so one f16 pass costs ~1e-4 on
 // the logits while the x3 attention kernel is register-bound at one wave per SIMD.
-template <class T, int NS, int HD, int NW, int OUTMODE = 0>
+template <class T, int NS, int HD, int NW, int OUTMODE = 0, bool VL = false>
 __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_kernel(const AttnArgs p) {      // (HIP: 2nd argument = min waves per SIMD)
     bd_saturating_conversions();      // fp8 / f16 results saturate (bd_common.h: RANGE)
     typedef typename Op16<T>::vec8 vec8;
@@ -89,9 +105,10 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     AP(60)
 #endif
     const int lq = lane & 31, lh = lane >> 5;
-    const int seq = p.seq, heads = p.heads;
-    const int q_len = p.q_len;
-    const int nqb = (q_len + QB - 1) / QB;
+    int seq = p.seq;
+    const int heads = p.heads;
+    int q_len = p.q_len;
+    int nqb = (q_len + QB - 1) / QB;
 
     // XCD-aware remap: consecutive work items (same batch*head, consecutive q-blocks) share K/V and
     // are kept on one XCD's L2.
@@ -100,12 +117,35 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
         const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
         wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     }
-    const int qb = wg % nqb;
-    const int bh = wg / nqb;
-    const int head = bh % heads, b = bh / heads;
+    int qb = wg % nqb;
+    int bh = wg / nqb;
+    int head = bh % heads, b = bh / heads;
+    int64_t row0 = (int64_t)b * seq;                       // the sample's first token row
+    int vl_views = 0;
+    if constexpr (VL) {
+        // the work list is implicit: (sample, head, q-block) in that order, every sample with its own number of q-blocks (whole ones:
+        // tpv % QB == 0).  Offsets are device data: anything inconsistent with the host's n_views / max_views ends the workgroup.
+        if (!p.q_view) {
+            const int ipv = (p.tpv / QB) * heads;          // work items per view
+            b = vl_sample_of(p.view_start, p.batch, ipv, wg, lane);
+            if (b >= p.batch) return;
+        }
+        const int s0 = __builtin_amdgcn_readfirstlane(p.view_start[b]), s1 = __builtin_amdgcn_readfirstlane(p.view_start[b + 1]);
+        vl_views = s1 - s0;
+        if (s0 < 0 || vl_views <= 0 || vl_views > p.max_views || s1 > p.n_views) return;
+        seq = vl_views * p.tpv;
+        row0 = (int64_t)s0 * p.tpv;
+        if (!p.q_view) {
+            q_len = seq;
+            nqb = vl_views * (p.tpv / QB);
+            const int local = wg - s0 * (p.tpv / QB) * heads;
+            qb = local % nqb;
+            head = local / nqb;
+        }
+    }
 
     const int ld = 3 * heads * HD;                         // elements per token row (32-bit offsets inside a sample)
-    const T* base = (const T*)p.qkv + (int64_t)b * seq * ld + head * HD;
+    const T* base = (const T*)p.qkv + row0 * ld + head * HD;
     const T* qbase = base;
     const T* kbase = base + heads * HD;
     const T* vbase = base + 2 * heads * HD;
@@ -113,8 +153,14 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
 
     // ---- Q fragments (B operand of S^T): lane (q, h) holds Q[q][ks*16 + h*8 .. +7]
     const int q0 = qb * QB + wid * 32;                     // local query index (within the query range)
-    const int qbase_row = p.q_view ? p.q_view[b] * q_len : p.q_off;
+    int qbase_row = p.q_view ? p.q_view[b] * q_len : p.q_off;
+    if constexpr (VL) { if (p.q_view) { const int qv = p.q_view[b]; qbase_row = (qv < 0 ? 0 : (qv < vl_views ? qv : vl_views - 1)) * q_len; } }
     int qrow = q0 + lq; qrow = (qrow < q_len ? qrow : q_len - 1) + qbase_row;
+    // first row of this sample in `out`: its packed rows (ragged, every row a query), else its out_rows-row slot
+    auto out_row0 = [&]() -> int64_t {
+        if constexpr (VL) { if (!p.q_view) return row0; }
+        return (int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off);
+    };
     vec8 qf[NS][KS];
 #pragma unroll
     for (int s = 0; s < NS; ++s)
@@ -329,7 +375,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     const int q = q0 + lq;
     if (q < q_len) {
         if (OUTMODE == 2) {
-            fp8e4* orow = (fp8e4*)p.out + ((int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q) * (heads * HD) + head * HD;
+            fp8e4* orow = (fp8e4*)p.out + (out_row0() + q) * (heads * HD) + head * HD;
 #pragma unroll
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
@@ -341,7 +387,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
                 }
         } else if (OUTMODE == 3) {
             // F16C8 operand (the proj GEMM's A in the round-2 strict mode): f16 hi plane + k-permuted lo8 plane
-            const int64_t e0 = ((int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q) * (heads * HD) + head * HD;
+            const int64_t e0 = (out_row0() + q) * (heads * HD) + head * HD;
 #pragma unroll
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
@@ -354,7 +400,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
         } else if (OUTMODE == 1 || OUTMODE == 4) {
             // (hi, lo) planes of ANOTHER 16-bit type than the kernel's operands: 1 = split-bf16, 4 = split-f16 (BD_PREC_F16X3)
             typedef typename std::conditional<OUTMODE == 1, __bf16, _Float16>::type OT;
-            OT* orow = (OT*)p.out + ((int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q) * (heads * HD) + head * HD;
+            OT* orow = (OT*)p.out + (out_row0() + q) * (heads * HD) + head * HD;
 #pragma unroll
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
@@ -373,7 +419,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
                     *(ovec4*)(orow + p.out_plane + d0) = lo;
                 }
         } else {
-            T* orow = (T*)p.out + ((int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q) * (heads * HD) + head * HD;
+            T* orow = (T*)p.out + (out_row0() + q) * (heads * HD) + head * HD;
 #pragma unroll
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
@@ -419,7 +465,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
 // sets; order pinned with sched_barrier).  Operand fragments are read three slots ahead into a ring of four registers.
 // Staging: all 512 threads fetch tile t+2 (global -> registers) at the top of iteration t and store it (K as is, V transposed,
 // attn_kernel's LDS images) at its end; K ring 2 tiles, V^T ring 4 tiles, ONE barrier per tile.
-template <class T, int HD, int OUTMODE>
+template <class T, int HD, int OUTMODE, bool VL = false>
 __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
     bd_saturating_conversions();      // fp8 / f16 results saturate (bd_common.h: RANGE)
     typedef typename Op16<T>::vec8 vec8;
@@ -449,27 +495,54 @@ __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 31, lh = lane >> 5;
-    const int seq = p.seq, heads = p.heads;
-    const int q_len = p.q_len;
-    const int nqb = (q_len + QB - 1) / QB;
+    int seq = p.seq;
+    const int heads = p.heads;
+    int q_len = p.q_len;
+    int nqb = (q_len + QB - 1) / QB;
 
     int wg;
     {
         const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
         wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     }
-    const int qb = wg % nqb;
-    const int bh = wg / nqb;
-    const int head = bh % heads, b = bh / heads;
+    int qb = wg % nqb;
+    int bh = wg / nqb;
+    int head = bh % heads, b = bh / heads;
+    int64_t row0 = (int64_t)b * seq;
+    int vl_views = 0;
+    if constexpr (VL) {      // as attn_kernel: the implicit (sample, head, q-block) work list of a ragged batch
+        if (!p.q_view) {
+            const int ipv = (p.tpv / QB) * heads;
+            b = vl_sample_of(p.view_start, p.batch, ipv, wg, lane);
+            if (b >= p.batch) return;
+        }
+        const int s0 = __builtin_amdgcn_readfirstlane(p.view_start[b]), s1 = __builtin_amdgcn_readfirstlane(p.view_start[b + 1]);
+        vl_views = s1 - s0;
+        if (s0 < 0 || vl_views <= 0 || vl_views > p.max_views || s1 > p.n_views) return;
+        seq = vl_views * p.tpv;
+        row0 = (int64_t)s0 * p.tpv;
+        if (!p.q_view) {
+            q_len = seq;
+            nqb = vl_views * (p.tpv / QB);
+            const int local = wg - s0 * (p.tpv / QB) * heads;
+            qb = local % nqb;
+            head = local / nqb;
+        }
+    }
 
     const int ld = 3 * heads * HD;
-    const T* base = (const T*)p.qkv + (int64_t)b * seq * ld + head * HD;
+    const T* base = (const T*)p.qkv + row0 * ld + head * HD;
     const T* kbase = base + heads * HD;
     const T* vbase = base + 2 * heads * HD;
 
     const int q0 = qb * QB + wid * 32;
-    const int qbase_row = p.q_view ? p.q_view[b] * q_len : p.q_off;
+    int qbase_row = p.q_view ? p.q_view[b] * q_len : p.q_off;
+    if constexpr (VL) { if (p.q_view) { const int qv = p.q_view[b]; qbase_row = (qv < 0 ? 0 : (qv < vl_views ? qv : vl_views - 1)) * q_len; } }
     int qrow = q0 + lq; qrow = (qrow < q_len ? qrow : q_len - 1) + qbase_row;
+    auto out_row0 = [&]() -> int64_t {
+        if constexpr (VL) { if (!p.q_view) return row0; }
+        return (int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off);
+    };
     vec8 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = as_vec8<T>(*(const u128*)(base + (unsigned)(qrow * ld + ks * 16 + lh * 8)));
@@ -699,7 +772,7 @@ __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         constexpr int CPR = OROW / 16, HIC = HD / 8;           // 16-byte pieces per row image / of its hi plane
         static_assert((32 * CPR) % 64 == 0, "pieces per wave");
-        const int64_t row0 = (int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q0;
+        const int64_t orow0 = out_row0() + q0;
         unsigned char* const out_hi = (unsigned char*)p.out;
         unsigned char* const out_lo = out_hi + 2 * p.out_plane;
 #pragma unroll
@@ -707,7 +780,7 @@ __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
             const int c = ln + 64 * k, r = c / CPR, col = c % CPR;
             if (q0 + r >= q_len) continue;
             const u128 piece = *(const u128*)(wl + r * OSTRIDE + col * 16);
-            const int64_t e = (row0 + r) * (heads * HD) + head * HD;
+            const int64_t e = (orow0 + r) * (heads * HD) + head * HD;
             if (OUTMODE == 3 && col >= HIC) *(u128*)(out_lo + e + (col - HIC) * 16) = piece;
             else *(u128*)(out_hi + 2 * e + col * 16) = piece;
         }
@@ -715,7 +788,7 @@ __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
     }
     const int q = q0 + lq;
     if (q < q_len) {
-        const int64_t e0 = ((int64_t)b * p.out_rows + (p.out_rows == q_len ? 0 : p.q_off) + q) * (heads * HD) + head * HD;
+        const int64_t e0 = (out_row0() + q) * (heads * HD) + head * HD;
 #pragma unroll
         for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
@@ -755,6 +828,26 @@ template <class T, int NS, int HD, int NW, int OUTMODE = 0> int launch(const Att
     const int nqb = (a.q_len + NW * 32 - 1) / (NW * 32);
     const int slot = bd_trace_open(s, 1, a.batch * a.heads, a.seq, HD);
     hipLaunchKernelGGL((attn_kernel<T, NS, HD, NW, OUTMODE>), dim3(nqb * a.heads * a.batch), dim3(NW * 64), 0, s, a);
+    bd_trace_close(s, slot);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+// Ragged batches: the same two kernels, VL instances.  Whole q-blocks per view (tpv % 256 == 0 for the ping-pong kernel, % 128 for the
+// 4-wave one), so the grid is EXACTLY the batch's q-blocks -- n_views * (tpv / QB) * heads with every row a query, batch * (tpv / QB) * heads
+// with q_view -- and nothing is sized by the longest sample.  One launch; the trace record carries N = max_views * tpv.
+template <class T, int NS, int OUTMODE> int dispatch_vl(const AttnArgs& a, hipStream_t s) {
+    const int units = a.q_view ? a.batch : a.n_views;
+    const int slot = bd_trace_open(s, 1, a.batch * a.heads, a.max_views * a.tpv, 96);
+    if constexpr (NS == 1) {
+        if (a.tpv % 256 == 0) {
+            hipLaunchKernelGGL((attn_kernel_pp<T, 96, OUTMODE, true>), dim3(units * (a.tpv / 256) * a.heads), dim3(512), 0, s, a);
+            bd_trace_close(s, slot);
+            BD_CHECK_LAUNCH();
+            return BD_OK;
+        }
+    }
+    hipLaunchKernelGGL((attn_kernel<T, NS, 96, 4, OUTMODE, true>), dim3(units * (a.tpv / 128) * a.heads), dim3(256), 0, s, a);
     bd_trace_close(s, slot);
     BD_CHECK_LAUNCH();
     return BD_OK;
@@ -854,4 +947,23 @@ extern "C" int bd_attention_prefix(const void* qkv, int64_t qkv_plane, void* out
 extern "C" int bd_attention(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch,
                             int seq, int heads, int head_dim, float scale, int prec, void* stream) {
     return bd_attention_q(qkv, qkv_plane, out, out_plane, batch, seq, heads, head_dim, scale, nullptr, seq, prec, stream);
+}
+
+extern "C" int bd_attention_varlen(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, const int32_t* view_start, int batch,
+                                   int n_views, int max_views, int tokens_per_view, int heads, int head_dim, float scale,
+                                   const int32_t* q_view, int prec, void* stream) {
+    if (!qkv || !out || !view_start) return BD_ERR_NULL;
+    if (batch <= 0 || heads <= 0 || n_views < batch || max_views <= 0 || max_views > n_views - (batch - 1)) return BD_ERR_SHAPE;
+    if (tokens_per_view <= 0 || tokens_per_view % 128) return BD_ERR_SHAPE;      // whole q-blocks and key tiles per view: no tail masks
+    if (head_dim != 96) return BD_ERR_SHAPE;                                     // (DINOv2's head_dim 64 sequences are per image, never ragged)
+    if ((int64_t)max_views * tokens_per_view >= ((int64_t)1 << 31) || sample_bytes_out_of_range(max_views * tokens_per_view, heads, head_dim))
+        return BD_ERR_SHAPE;
+    if ((int64_t)n_views * (tokens_per_view / 128) * heads >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return BD_ERR_ALIGN;
+    AttnArgs a{qkv, qkv_plane, out, out_plane, batch, 0, heads, scale * 1.4426950408889634f, q_view, tokens_per_view, 0, tokens_per_view,
+               view_start, tokens_per_view, n_views, max_views};
+    hipStream_t s = (hipStream_t)stream;
+#define BD_CALL_VL(T_, NS_, OM_) dispatch_vl<T_, NS_, OM_>(a, s)
+    BD_ATTN_PREC_SWITCH(BD_CALL_VL)
+#undef BD_CALL_VL
 }

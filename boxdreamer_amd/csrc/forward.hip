@@ -88,6 +88,10 @@ struct Stack {
     const int32_t* query_idx;        // BETR: the last block runs the query view's P rows per sample past K / V ...
     int P;
     float* xc;                       // ... on this compact fp32 stream [batch * P, D]
+    // Ragged batch (bd_decoder_forward_ragged): sample b owns the views [view_start[b], view_start[b + 1]) of the packed stream, M = n_views * P
+    // rows; query_idx counts inside the sample.  Only attention and the query-row gather know where a sample starts (run_block).
+    const int32_t* view_start;       // device int32 [batch + 1], or NULL: every sample has seq rows
+    int n_views, max_views;
 };
 
 // Attention forms.  PREFIX_SKIP (last DINOv2 block): the prefix rows are never read again, so their attention is skipped
@@ -305,12 +309,16 @@ int run_block(const BlockPlan& e, const Stack& s, void* stream) {
     if (w.q_norm_w && !e.rms_fused) BD_TRY(bd_qk_rmsnorm(b.qkv, 3 * pD, w.q_norm_w, w.k_norm_w, s.rms_eps, s.M, s.heads, hd, e.aprec_in, stream));
     const float scale = 1.0f / sqrtf((float)hd);
     const bool qo = e.attn == ATTN_QUERY_ONLY;
-    if (e.attn == ATTN_PREFIX_SKIP)
+    if (s.view_start)
+        BD_TRY(bd_attention_varlen(b.qkv, 3 * pD, b.ao, rD, s.view_start, s.batch, s.n_views, s.max_views, s.P, s.heads, hd, scale,
+                                   qo ? s.query_idx : nullptr, e.aprec, stream));
+    else if (e.attn == ATTN_PREFIX_SKIP)
         BD_TRY(bd_attention_prefix(b.qkv, 3 * pD, b.ao, pD, s.batch, s.seq, s.heads, hd, scale, s.n_prefix, 0, e.aprec, stream));
     else
         BD_TRY(bd_attention_q_forms(b.qkv, 3 * pD, b.ao, rD, s.batch, s.seq, s.heads, hd, scale, qo ? s.query_idx : nullptr, qo ? s.P : s.seq,
                                     e.aprec, s.lat ? 1 : 0, stream));
-    if (qo) BD_TRY(bd_gather_query_rows_f32(b.x, s.query_idx, e.x, s.batch, s.seq / s.P, s.P, D, stream));
+    if (qo && s.view_start) BD_TRY(bd_gather_query_rows_f32_varlen(b.x, s.view_start, s.query_idx, e.x, s.batch, s.P, D, stream));
+    else if (qo) BD_TRY(bd_gather_query_rows_f32(b.x, s.query_idx, e.x, s.batch, s.seq / s.P, s.P, D, stream));
     BD_TRY(launch(proj_lin(e, s), stream));
     if (!e.fold2) BD_TRY(bd_layernorm(e.x, D, w.ln2_w, w.ln2_b, s.ln_eps, b.xn, rD, nullptr, 0, e.Mr, D, 0, 0, 0, e.c_fc1, stream));
     BD_TRY(launch(fc1_lin(e, s), stream));
@@ -345,10 +353,11 @@ EncBufs carve_encoder(const bd_dino_weights* w, int n, int prec, void* ws) {
 }
 
 struct DecBufs { void *a_heat, *t1, *qtok; float *t2, *rgb, *proj; BlockBufs blk; size_t bytes; };
-DecBufs carve_decoder(const bd_betr_weights* w, int B, int T, int prec, void* ws) {
+// n_views: views of the whole batch (B * T, or the sum of a ragged batch's view counts): every buffer is sized by token rows, none by T
+DecBufs carve_decoder_views(const bd_betr_weights* w, int64_t n_views, int B, int prec, void* ws) {
     Carver c{(unsigned char*)ws, 0};
     const int np = planes_of(prec), P = w->grid * w->grid, D = w->dim;
-    const int64_t Mb = (int64_t)B * T * P, Mq = (int64_t)B * P;
+    const int64_t Mb = n_views * P, Mq = (int64_t)B * P;
     const int F = w->patch * w->patch * w->box_dim;
     DecBufs d;
     d.a_heat = c.take((size_t)Mb * w->kpad * 2 * np);
@@ -361,6 +370,7 @@ DecBufs carve_decoder(const bd_betr_weights* w, int B, int T, int prec, void* ws
     d.bytes = c.off + 256;
     return d;
 }
+DecBufs carve_decoder(const bd_betr_weights* w, int B, int T, int prec, void* ws) { return carve_decoder_views(w, (int64_t)B * T, B, prec, ws); }
 
 inline bool bad_prec(int prec) {
     return prec != BD_PREC_BF16 && prec != BD_PREC_F16 && prec != BD_PREC_BF16X3 && prec != BD_PREC_FP8 &&
@@ -426,28 +436,26 @@ extern "C" size_t bd_decoder_workspace_bytes(const bd_betr_weights* w, int B, in
     return carve_decoder(w, B, T, prec, nullptr).bytes;
 }
 
-extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
-                                  int64_t feats16_plane, const int32_t* query_idx, int B, int T, int size,
-                                  float* logits, float* heat, void* workspace, size_t workspace_bytes, int wprec,
-                                  void* stream) {
-    if (!w || !bbox_feat || !feats16 || !query_idx || !workspace || !w->blocks || (!logits && !heat)) return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+namespace {
+// The decoder chain on n_views * P packed token rows.  view_start == NULL: the uniform batch of bd_decoder_forward (n_views = B * T, every
+// sample T views).  view_start != NULL: the ragged batch of bd_decoder_forward_ragged -- the same launches; attention, the query-token
+// substitution and the query-row gather take the sample boundaries from the offsets, everything else is row-wise and sees M = n_views * P.
+int decoder_chain(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16, int64_t feats16_plane,
+                  const int32_t* view_start, const int32_t* query_idx, int B, int n_views, int T, int size, float* logits, float* heat,
+                  void* workspace, size_t workspace_bytes, int wprec, void* stream) {
     const int prec = gemm_prec(wprec);
-    if (B <= 0 || T <= 0 || size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 ||
-        w->kpad < w->patch * w->patch * w->box_dim)
-        return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    const DecBufs d = carve_decoder(w, B, T, prec, workspace);
+    const DecBufs d = carve_decoder_views(w, n_views, B, prec, workspace);
     if (workspace_bytes < d.bytes) return BD_ERR_WORKSPACE;
     const int P = w->grid * w->grid, D = w->dim, F = w->patch * w->patch * w->box_dim;
-    const int Mb = B * T * P, Mq = B * P;
+    const int Mb = n_views * P, Mq = B * P;
     const int64_t pD = (int64_t)Mb * D;
     // K9: joint self-attention over all T*P tokens of a sample; the last block runs the query view's rows only past K / V, on d.t2 (dead
     // since the adapter) as its compact stream
     Stack s{};
     s.blocks = w->blocks; s.depth = w->depth; s.b = d.blk;
     s.M = Mb; s.batch = B; s.seq = T * P; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.rms_eps = w->rms_eps;
-    s.lat = w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
+    s.lat = !view_start && w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
+    s.view_start = view_start; s.n_views = n_views; s.max_views = T;      // (ragged: T is the largest per-sample view count)
     std::vector<BlockPlan> sched;
     BD_TRY(plan_stack(s, wprec, sched));
     if (d.blk.sk && hipMemsetAsync(d.blk.sk, 0, d.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
@@ -468,7 +476,7 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
     }
     BD_TRY(bd_layernorm(d.t2, D, nullptr, nullptr, w->adapter_ln_eps, nullptr, 0, d.rgb, D, Mb, D, 0, 0, 0, prec, stream));
     // K7+K8: heatmap patch embedding fused with  + rgb + pos  (betr.py:324-329, 367-399)
-    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, d.a_heat, (int64_t)Mb * w->kpad, B * T, w->box_dim, size, w->patch,
+    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, d.a_heat, (int64_t)Mb * w->kpad, n_views, w->box_dim, size, w->patch,
                                 w->kpad, c_be, stream));
     {
         bd_gemm_args g = gemm_args(d.a_heat, w->kpad, (int64_t)Mb * w->kpad, w->bbox_emb, w->kpad, D, d.blk.x, D, 0, 1,
@@ -477,7 +485,8 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
         g.resid = d.rgb; g.ldr = D;
         BD_TRY(bd_gemm(&g, c_be, stream));
     }
-    BD_TRY(bd_query_substitute(d.blk.x, d.rgb, w->pos_table, w->query_token, query_idx, B, T, P, D, stream));
+    if (view_start) BD_TRY(bd_query_substitute_varlen(d.blk.x, d.rgb, w->pos_table, w->query_token, view_start, query_idx, B, P, D, stream));
+    else BD_TRY(bd_query_substitute(d.blk.x, d.rgb, w->pos_table, w->query_token, query_idx, B, T, P, D, stream));
     for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
     // K10: head on the query view's tokens (no final norm, betr.py:298-306)
     BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c_bp, stream));
@@ -487,6 +496,43 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
     }
     BD_TRY(bd_unpatchify_sigmoid(d.proj, logits, heat, B, w->box_dim, size, w->patch, stream));
     return BD_OK;
+}
+}  // namespace
+
+extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
+                                  int64_t feats16_plane, const int32_t* query_idx, int B, int T, int size,
+                                  float* logits, float* heat, void* workspace, size_t workspace_bytes, int wprec,
+                                  void* stream) {
+    if (!w || !bbox_feat || !feats16 || !query_idx || !workspace || !w->blocks || (!logits && !heat)) return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (B <= 0 || T <= 0 || size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 ||
+        w->kpad < w->patch * w->patch * w->box_dim)
+        return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    return decoder_chain(w, bbox_feat, in_dtype, feats16, feats16_plane, nullptr, query_idx, B, B * T, T, size, logits, heat, workspace,
+                         workspace_bytes, wprec, stream);
+}
+
+extern "C" size_t bd_decoder_workspace_bytes_ragged(const bd_betr_weights* w, int n_views, int B, int prec) {
+    if (!w || B <= 0 || n_views < B || bad_prec(prec)) return 0;
+    return carve_decoder_views(w, n_views, B, prec, nullptr).bytes;
+}
+
+extern "C" int bd_decoder_forward_ragged(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
+                                         int64_t feats16_plane, const int32_t* view_start, const int32_t* query_view, int B, int n_views,
+                                         int max_views, int size, float* logits, float* heat, void* workspace, size_t workspace_bytes,
+                                         int wprec, void* stream) {
+    if (!w || !bbox_feat || !feats16 || !view_start || !query_view || !workspace || !w->blocks || (!logits && !heat)) return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (in_dtype < 0 || in_dtype > 2) return BD_ERR_DTYPE;
+    if (B <= 0 || n_views < B || max_views <= 0 || max_views > n_views - (B - 1) || (int64_t)max_views * B < n_views ||
+        size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 || w->kpad < w->patch * w->patch * w->box_dim)
+        return BD_ERR_SHAPE;
+    if ((w->grid * w->grid) % 128 || w->dim / w->heads != 96) return BD_ERR_SHAPE;      // what bd_attention_varlen takes
+    if ((int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    return decoder_chain(w, bbox_feat, in_dtype, feats16, feats16_plane, view_start, query_view, B, n_views, max_views, size, logits, heat,
+                         workspace, workspace_bytes, wprec, stream);
 }
 
 // ----------------------------------------------------------------------------------------------------------------------------

@@ -165,22 +165,32 @@ __global__ __launch_bounds__(256) void prefix_kernel(float* __restrict__ x, cons
     x[(n * tpi + pfx) * dim + d] = prefix[pfx * dim + d];
 }
 
+// The query view of sample b as a view index of the whole batch.  Uniform batch (vstart == NULL): b * T + qidx[b].  Ragged batch:
+// sample b owns the views [vstart[b], vstart[b + 1]) and qidx[b] counts inside them (clamped to the sample: the offsets are device data).
+__device__ __forceinline__ int64_t query_view_of(const int32_t* __restrict__ vstart, const int32_t* __restrict__ qidx, int b, int T) {
+    if (!vstart) return (int64_t)b * T + (qidx ? qidx[b] : 0);
+    const int v0 = vstart[b], n = vstart[b + 1] - v0, q = qidx ? qidx[b] : 0;
+    return (int64_t)v0 + (q < 0 || n <= 0 ? 0 : (q < n ? q : n - 1));
+}
+
 __global__ __launch_bounds__(256) void query_sub_kernel(float* __restrict__ x, const float* __restrict__ rgb,
                                                         const float* __restrict__ pos, const float* __restrict__ qtok,
-                                                        const int32_t* __restrict__ qidx, int B, int T, int P, int dim) {
+                                                        const int32_t* __restrict__ qidx, const int32_t* __restrict__ vstart,
+                                                        int B, int T, int P, int dim) {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)B * P * dim;
     if (t >= total) return;
     const int d = (int)(t % dim), tok = (int)((t / dim) % P);
     const int b = (int)(t / ((int64_t)dim * P));
-    const int64_t row = ((int64_t)b * T + qidx[b]) * P + tok;
+    const int64_t row = query_view_of(vstart, qidx, b, T) * P + tok;
     // betr.py:288-290 + :367,399:  (query + rgb) + pos  -- same association order as the reference
     x[row * dim + d] = (qtok[d] + rgb[row * dim + d]) + pos[tok * dim + d];
 }
 
 template <class T, int NS>
 __global__ __launch_bounds__(256) void gather_query_kernel(const float* __restrict__ x, const int32_t* __restrict__ qidx,
-                                                           void* __restrict__ out_, int64_t plane, int B, int T_, int P, int dim) {
+                                                           const int32_t* __restrict__ vstart, void* __restrict__ out_, int64_t plane,
+                                                           int B, int T_, int P, int dim) {
     bd_saturating_conversions();      // fp8 / f16 results saturate (bd_common.h: RANGE)
     T* out = (T*)out_;
     const int cpr = dim / 8;
@@ -189,14 +199,15 @@ __global__ __launch_bounds__(256) void gather_query_kernel(const float* __restri
     if (t >= total) return;
     const int c = (int)(t % cpr), tok = (int)((t / cpr) % P);
     const int b = (int)(t / ((int64_t)cpr * P));
-    const float* src = x + (((int64_t)b * T_ + (qidx ? qidx[b] : 0)) * P + tok) * dim + c * 8;
+    const float* src = x + (query_view_of(vstart, qidx, b, T_) * P + tok) * dim + c * 8;
     const float4 a = *(const float4*)src, bb = *(const float4*)(src + 4);
     const float v[8] = {a.x, a.y, a.z, a.w, bb.x, bb.y, bb.z, bb.w};
     store_operand8<T, NS>(out, plane, ((int64_t)b * P + tok) * dim + c * 8, v);
 }
 
 __global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __restrict__ x, const int32_t* __restrict__ qidx,
-                                                              float* __restrict__ out, int B, int T_, int P, int dim) {
+                                                              const int32_t* __restrict__ vstart, float* __restrict__ out, int B, int T_,
+                                                              int P, int dim) {
     const int cpr = dim / 4;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t total = (int64_t)B * P * cpr;
@@ -204,7 +215,7 @@ __global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float* __res
     const int c = (int)(t % cpr), tok = (int)((t / cpr) % P);
     const int b = (int)(t / ((int64_t)cpr * P));
     *(float4*)(out + ((int64_t)b * P + tok) * dim + c * 4) =
-        *(const float4*)(x + (((int64_t)b * T_ + qidx[b]) * P + tok) * dim + c * 4);
+        *(const float4*)(x + (query_view_of(vstart, qidx, b, T_) * P + tok) * dim + c * 4);
 }
 
 // one thread per output pixel (b, y, x): reads the pixel's 8 consecutive channel features, writes 8 planes
@@ -363,7 +374,18 @@ extern "C" int bd_query_substitute(float* x, const float* rgb, const float* pos,
     if (B <= 0 || T <= 0 || P <= 0 || dim <= 0) return BD_ERR_SHAPE;
     const int64_t total = (int64_t)B * P * dim;
     hipLaunchKernelGGL(query_sub_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, rgb, pos,
-                       query_token, query_idx, B, T, P, dim);
+                       query_token, query_idx, (const int32_t*)nullptr, B, T, P, dim);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_query_substitute_varlen(float* x, const float* rgb, const float* pos, const float* query_token,
+                                          const int32_t* view_start, const int32_t* query_view, int B, int P, int dim, void* stream) {
+    if (!x || !rgb || !pos || !query_token || !view_start || !query_view) return BD_ERR_NULL;
+    if (B <= 0 || P <= 0 || dim <= 0) return BD_ERR_SHAPE;
+    const int64_t total = (int64_t)B * P * dim;
+    hipLaunchKernelGGL(query_sub_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, rgb, pos,
+                       query_token, query_view, view_start, B, 0, P, dim);
     BD_CHECK_LAUNCH();
     return BD_OK;
 }
@@ -373,8 +395,19 @@ extern "C" int bd_gather_query_rows_f32(const float* x, const int32_t* query_idx
     if (!x || !query_idx || !out) return BD_ERR_NULL;
     if (B <= 0 || T <= 0 || P <= 0 || dim % 4) return BD_ERR_SHAPE;
     const int64_t total = (int64_t)B * P * (dim / 4);
-    hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, query_idx, out,
-                       B, T, P, dim);
+    hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, query_idx,
+                       (const int32_t*)nullptr, out, B, T, P, dim);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_gather_query_rows_f32_varlen(const float* x, const int32_t* view_start, const int32_t* query_view, float* out, int B,
+                                               int P, int dim, void* stream) {
+    if (!x || !view_start || !query_view || !out) return BD_ERR_NULL;
+    if (B <= 0 || P <= 0 || dim <= 0 || dim % 4) return BD_ERR_SHAPE;
+    const int64_t total = (int64_t)B * P * (dim / 4);
+    hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(nblk(total)), dim3(256), 0, (hipStream_t)stream, x, query_view, view_start, out,
+                       B, 0, P, dim);
     BD_CHECK_LAUNCH();
     return BD_OK;
 }
@@ -385,7 +418,18 @@ extern "C" int bd_gather_query_tokens(const float* x, const int32_t* query_idx, 
     if (B <= 0 || T <= 0 || P <= 0 || dim % 8) return BD_ERR_SHAPE;
     const int64_t total = (int64_t)B * P * (dim / 8);
     hipStream_t s = (hipStream_t)stream;
-    BD_PREC_SWITCH(gather_query_kernel, dim3(nblk(total)), dim3(256), 0, s, x, query_idx, out16, out_plane, B, T, P, dim)
+    BD_PREC_SWITCH(gather_query_kernel, dim3(nblk(total)), dim3(256), 0, s, x, query_idx, (const int32_t*)nullptr, out16, out_plane, B, T, P, dim)
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_gather_query_tokens_varlen(const float* x, const int32_t* view_start, const int32_t* query_view, void* out16,
+                                             int64_t out_plane, int B, int P, int dim, int prec, void* stream) {
+    if (!x || !view_start || !query_view || !out16) return BD_ERR_NULL;
+    if (B <= 0 || P <= 0 || dim <= 0 || dim % 8) return BD_ERR_SHAPE;
+    const int64_t total = (int64_t)B * P * (dim / 8);
+    hipStream_t s = (hipStream_t)stream;
+    BD_PREC_SWITCH(gather_query_kernel, dim3(nblk(total)), dim3(256), 0, s, x, query_view, view_start, out16, out_plane, B, 0, P, dim)
     BD_CHECK_LAUNCH();
     return BD_OK;
 }

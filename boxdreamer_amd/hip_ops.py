@@ -220,6 +220,24 @@ def attention_q(qkv16, batch, seq, heads, head_dim, scale, q_view, q_len, *, pre
     return out
 
 
+def attention_varlen(qkv16, view_counts, tokens_per_view, heads, head_dim, scale, *, prec="bf16", q_view=None, view_start=None):
+    """bd_attention_varlen on a packed ragged batch: qkv16 holds sum(view_counts) * tokens_per_view token rows, sample b the next
+    view_counts[b] views.  view_counts: HOST ints.  q_view (device int32 [B], view index inside the sample): only that view's rows are
+    queries, compact output [B * tokens_per_view, heads * head_dim]; None: every row is a query, packed output.  view_start: the
+    device int32 [B + 1] offsets when the caller already holds them (else built here from the counts)."""
+    lib = _lib.load()
+    counts = _lib.view_counts_list(view_counts)
+    dev = qkv16.device
+    if view_start is None:
+        view_start = torch.tensor(_lib.view_starts(counts), dtype=torch.int32).to(dev)
+    B, n_views = len(counts), sum(counts)
+    out = _alloc16((B if q_view is not None else n_views) * tokens_per_view, heads * head_dim, prec, dev)
+    check(lib.bd_attention_varlen(ptr(qkv16), _plane(qkv16, prec), ptr(out), _plane(out, prec), ptr(view_start), B, n_views,
+                                  max(counts) if counts else 0, tokens_per_view, heads, head_dim, scale, ptr(q_view), prec_id(prec),
+                                  stream()), "bd_attention_varlen")
+    return out
+
+
 def im2col_images(images, patch=14, kpad=640, *, prec="bf16"):
     lib = _lib.load()
     images = images.contiguous()

@@ -110,12 +110,16 @@ class BoxDreamer(nn.Module):
         B, T = images.shape[:2]
         mask = torch.zeros((B, T), dtype=torch.bool, device=images.device)
         mask[torch.arange(B, device=images.device), data["query_idx"].to(images.device).long()] = True
+        bbox_feat = data["bbox_feat"]
+        counts = self._view_counts(data, B, T)
+        if counts is not None:       # ragged batch: the first sample with its own view count (its padded slots are never read)
+            images, bbox_feat, mask = images[:1, :counts[0]], bbox_feat[:1, :counts[0]], mask[:1, :counts[0]]
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)
         if self.hip_promotion_file and self.hip_calibrate and calibrate.load_state(self.hip_promotion_file, self.rgb_encoder, self.decoder):
             self._calibrated_for = self.decoder._signature()
             return self.decoder.hip_calibration
-        rep = calibrate.calibrate(self.rgb_encoder, self.decoder, images, data["bbox_feat"], mask, promote=self.hip_calibrate)
+        rep = calibrate.calibrate(self.rgb_encoder, self.decoder, images, bbox_feat, mask, promote=self.hip_calibrate)
         self._calibrated_for = self.decoder._signature()
         # (no collective in here: an explicit model.calibrate(data) on ONE rank must not wait for the others.  forward() adopts rank 0's
         # state in one place that every rank reaches, _sync_ranks_once, and rank 0 writes the promotion file there)
@@ -155,6 +159,25 @@ class BoxDreamer(nn.Module):
             calibrate.save_state(self.hip_promotion_file, self.rgb_encoder, self.decoder, self.decoder.hip_calibration or {})
         self._pending_save = False
         self._ranks_synced_for = sig
+
+    @staticmethod
+    def _view_counts(data, B: int, T: int):
+        """The optional batch-dict key `view_counts` (a list or a CPU int tensor, one entry per sample: the sample's valid views are the
+        slots [0, count) of its T_max = T slots) as validated host ints -- or None when the key is absent or every count equals T, which
+        IS the uniform batch.  A device tensor raises TypeError (reading it would add a host sync per forward); counts outside [2, T] or
+        a host-side `query_idx` that is not among the sample's views raise ValueError (a device-side `query_idx` is checked on the
+        device and reported with the corners' D2H, like the one-hot check of camera_mask)."""
+        if data.get("view_counts") is None:
+            return None
+        counts = _lib.view_counts_list(data["view_counts"], B)
+        q = data.get("query_idx")
+        host_q = None
+        if isinstance(q, torch.Tensor) and not q.is_cuda:
+            host_q = q.reshape(-1).tolist()
+        elif q is not None and not isinstance(q, torch.Tensor):
+            host_q = list(q)
+        _lib.check_view_counts(counts, T, host_q)
+        return None if all(c == T for c in counts) else counts
 
     def _arange(self, n: int, dev) -> torch.Tensor:
         """arange(n) on `dev`, kept (read-only use): the host time between two batches is device idle time in an eval forward."""
@@ -213,6 +236,16 @@ class BoxDreamer(nn.Module):
         camera_mask = self._arange(T, dev)[None, :] == qi[:, None]
         data["camera_mask"] = camera_mask.clone()
         pose_feat = data["bbox_feat"]
+        # ragged batch: per-sample view counts (host ints).  None: the uniform batch, today's path bit for bit
+        counts = self._view_counts(data, B, T)
+        dense = self.dense_cfg is not None and _get(self.dense_cfg, "enable", False)
+        if counts is not None:
+            if dense:
+                raise NotImplementedError("view_counts together with dense_cfg.enable (ragged dense-reference mode) is not implemented")
+            if "cached_rgb_feat" in data:
+                raise NotImplementedError("view_counts together with cached_rgb_feat (ragged feature cache) is not implemented")
+            if not isinstance(self.decoder, BETR):
+                raise NotImplementedError("view_counts needs the BETR decoder")
 
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)                            # BoxDreamerModel.py:279-282
@@ -234,10 +267,23 @@ class BoxDreamer(nn.Module):
             data["hip_precision"] = self._precision_record()
             # sub-batch lanes this batch runs as (bit-identical for every value; `hip_lanes` in the decoder / encoder cfg, default "auto")
             data["hip_precision"]["sub_batch_lanes"] = _lib.resolve_lanes(self.decoder.hip_lanes, B * T, B, self.decoder.hip_precision)
+            if counts is not None:      # the ragged decoder call has no laned form yet: ONE lane (the encoder lanes its packed images as ever)
+                data["hip_precision"]["sub_batch_lanes"] = 1
+                data["hip_precision"]["ragged_views"] = sum(counts)
         ar = self._arange(B, dev)
         decoded = None
-        dense = self.dense_cfg is not None and _get(self.dense_cfg, "enable", False)
-        if (self.hip_graph and not dense and "cached_rgb_feat" not in data and not self.training and images.is_cuda
+        if counts is not None:
+            # (hip_graph: a ragged batch takes this eager branch -- capture of ragged shapes is a follow-up)
+            # the encoder and the decoder see the sum(counts) real views only, packed sample by sample; padded slots are never read
+            index, view_start = self.decoder.ragged_index(counts, T, dev)
+            rgb_feature = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, index))
+            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
+            if not (isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda):
+                # query_idx lives on the device: "is it one of the sample's views" travels with the deferred mask verdict (no sync here)
+                beyond = (qi >= (view_start[1:] - view_start[:-1]).long()).any()
+                err = self.decoder.mask_error
+                self.decoder.mask_error = beyond if err is None else (err | beyond)
+        elif (self.hip_graph and not dense and "cached_rgb_feat" not in data and not self.training and images.is_cuda
                 and isinstance(self.decoder, BETR) and not torch.cuda.is_current_stream_capturing()):
             heat, kp_px, kn, _ = self._graphed(images, pose_feat, qi, sig)
             # (the replay's outputs are static buffers the next replay overwrites: what the caller keeps is copied out of them below --
@@ -358,8 +404,8 @@ class BoxDreamer(nn.Module):
             data["pose_solver"] = ("host:cv2.solvePnP" if pnp._HAVE_CV2
                                    else "host:bd_solve_pnp_host (native threads, DLT + LM; parity vs OpenCV un-pinned)")
         if bad:
-            raise ValueError("camera_mask must mark exactly one query view per sample (reported with the corners' D2H; "
-                             "BETR.validate_inputs = True checks before the launch instead)")
+            raise ValueError("camera_mask must mark exactly one query view per sample, among the sample's view_counts views when those "
+                             "are given (reported with the corners' D2H; BETR.validate_inputs = True checks before the launch instead)")
         if not poses.is_cuda and pred_poses.is_cuda:
             # the solved poses go back through a pinned staging buffer: an asynchronous copy (from pageable memory it would wait for the
             # stream).  The buffer is rewritten only after the NEXT forward's D2H, which waits for everything enqueued before it.

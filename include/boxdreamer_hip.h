@@ -239,6 +239,29 @@ int bd_attention_q(const void* qkv, int64_t qkv_plane, void* out, int64_t out_pl
 int bd_attention_prefix(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch, int seq, int heads,
                         int head_dim, float scale, int n_prefix, int prefix_queries, int prec, void* stream);
 
+/* Ragged batches: bd_attention / bd_attention_q for samples with DIFFERENT numbers of views, packed back to back -- the
+ * flash_attn_varlen_func form of the boundary above (cu_seqlens), in units of views.  qkv: [n_views * tokens_per_view, 3, heads,
+ * head_dim]; sample b owns the views [view_start[b], view_start[b + 1]), i.e. the token rows [view_start[b] * tokens_per_view,
+ * view_start[b + 1] * tokens_per_view), and softmax(scale * Q K^T) V runs inside them: no padded views, nothing attends across samples.
+ * view_start: DEVICE int32 [batch + 1], ascending, view_start[0] = 0, view_start[batch] = n_views.  n_views (their total) and max_views
+ * (the largest per-sample count) are the HOST's copies of the same numbers: they size the grid and bound the per-sample buffer
+ * descriptor, so the call never reads the offsets on the host and never synchronises.  A sample whose offsets disagree with them
+ * (descending, more than max_views views, beyond n_views) is skipped by the kernel: its output rows are left untouched.
+ *   q_view == NULL   every row is a query; out is packed like the input: [n_views * tokens_per_view, heads * head_dim].
+ *   q_view != NULL   DEVICE int32 [batch], the view index INSIDE the sample (clamped to it): only that view's tokens_per_view rows are
+ *                    queries and out is compact [batch * tokens_per_view, heads * head_dim] -- bd_attention_q's form, the last BETR block.
+ * head_dim == 96 only (BETR; DINOv2's head_dim-64 sequences are per image and never ragged) and tokens_per_view % 128 == 0, so that every
+ * sample is whole 64-key tiles and whole query blocks and no tail is masked (BETR: 256): BD_ERR_SHAPE otherwise.  The 2 GiB rule of
+ * bd_attention applies per sample, to max_views * tokens_per_view rows.  Every `prec` bd_attention takes.
+ * ONE launch: the work list (sample, head, query block) is implicit in the offsets -- the grid is exactly the batch's query blocks,
+ * n_views * (tokens_per_view / 256 or 128) * heads (q_view: batch * ...), never sized by the longest sample; a workgroup finds its sample
+ * with one ballot over the offsets.  The same kernels as bd_attention (ping-pong for the single-plane classes at tokens_per_view % 256 == 0,
+ * else the 4-wave kernel), taking their base row and key count per sample: a row's bits equal bd_attention[_q] run on that sample alone
+ * (batch = 1, seq = its rows).  Launch trace: one kind-1 record, N = max_views * tokens_per_view. */
+int bd_attention_varlen(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, const int32_t* view_start, int batch,
+                        int n_views, int max_views, int tokens_per_view, int heads, int head_dim, float scale,
+                        const int32_t* q_view, int prec, void* stream);
+
 /* (x - mean_c) / std_c, then 14x14 patches -> A operand rows [n*grid*grid, kpad], k = c*p*p + py*p + px,
  * zero-padded to kpad.  Replaces encoder/dinov2.py:45-46,56 + the unfold inside the patch-embed conv. */
 int bd_im2col_images(const void* images, int img_dtype, void* out16, int64_t out_plane, int n_images,
@@ -266,6 +289,16 @@ int bd_gather_query_rows_f32(const float* x, const int32_t* query_idx, float* ou
  * (query_idx == NULL: view 0, i.e. a pure cast of an already compact [B*P, dim] tensor with T = 1). */
 int bd_gather_query_tokens(const float* x, const int32_t* query_idx, void* out16, int64_t out_plane,
                            int B, int T, int P, int dim, int prec, void* stream);
+
+/* The three query-view operators above for a ragged batch (bd_attention_varlen's packing): x, rgb are [n_views * P, dim], sample b's
+ * query view is view view_start[b] + query_view[b] of the packed batch (query_view counts inside the sample and is clamped to it).
+ * view_start: device int32 [B + 1]; query_view: device int32 [B]. */
+int bd_query_substitute_varlen(float* x, const float* rgb, const float* pos, const float* query_token, const int32_t* view_start,
+                               const int32_t* query_view, int B, int P, int dim, void* stream);
+int bd_gather_query_rows_f32_varlen(const float* x, const int32_t* view_start, const int32_t* query_view, float* out, int B, int P,
+                                    int dim, void* stream);
+int bd_gather_query_tokens_varlen(const float* x, const int32_t* view_start, const int32_t* query_view, void* out16, int64_t out_plane,
+                                  int B, int P, int dim, int prec, void* stream);
 
 /* BETR.unpatchify + 2*sigmoid-1 (betr.py:230-247, 432-435): proj fp32 [B*P, p*p*c] ->
  * logits, heat fp32 [B, c, size, size]. */
@@ -443,6 +476,27 @@ int bd_decoder_forward(const bd_betr_weights* w /*[host]*/, const void* bbox_fea
                        const void* feats16, int64_t feats16_plane, const int32_t* query_idx, int B,
                        int T, int size, float* logits, float* heat, void* workspace,
                        size_t workspace_bytes, int prec, void* stream);
+
+/* BETR.forward on a RAGGED batch: sample b has view_start[b + 1] - view_start[b] views (its references and its query), the batch's
+ * n_views views are packed back to back.  The reference cannot express this (its dataset emits one `length` per batch, and its
+ * sub_batchify pads with zero views that the joint attention then attends to, src/models/utils/data_utils.py:40-80); a caller that
+ * batches queries of different objects can.  bbox_feat: [n_views, c, size, size]; feats16: the encoder's operand copy of the same
+ * n_views images (bd_encoder_forward on the packed images: the encoder needs no ragged form); view_start: device int32 [B + 1];
+ * query_view: device int32 [B], the query's index inside its sample; n_views / max_views: the host's total and largest per-sample count
+ * (B <= n_views, max_views <= n_views - (B - 1), max_views * B >= n_views) -> logits, heat fp32 [B, c, size, size].
+ * The same chain of launches as bd_decoder_forward on M = n_views * P token rows -- the Linears, LayerNorm fold, 3-byte residual stream,
+ * per-Linear promotion and QK16 split are row-wise and unchanged; attention (bd_attention_varlen, one launch per block), the query-token
+ * substitution and the query-row gather take the sample boundaries from view_start.  No launch is sized by B * max_views.  A sample's
+ * outputs are bit-identical to bd_decoder_forward on that sample alone (B = 1, T = its views).  bd_betr_weights.latency_mode is ignored
+ * (no latency forms for ragged calls).  Needs grid * grid % 128 == 0 and head_dim 96 (BD_ERR_SHAPE otherwise).
+ * bd_decoder_workspace_bytes_ragged(w, B * T, B, prec) == bd_decoder_workspace_bytes(w, B, T, prec).
+ * Sub-batch lanes: there is no _lanes form of the ragged call yet -- it runs as ONE lane on `stream` (a split at sample boundaries,
+ * balanced on cumulative views, through the machinery below is the planned form). */
+size_t bd_decoder_workspace_bytes_ragged(const bd_betr_weights* w /*[host]*/, int n_views, int B, int prec);
+int bd_decoder_forward_ragged(const bd_betr_weights* w /*[host]*/, const void* bbox_feat, int in_dtype, const void* feats16,
+                              int64_t feats16_plane, const int32_t* view_start, const int32_t* query_view, int B, int n_views,
+                              int max_views, int size, float* logits, float* heat, void* workspace, size_t workspace_bytes,
+                              int prec, void* stream);
 
 /* Sub-batch lanes (ABI v6).  The same two operators with ONE batch run as `lanes` (1..4) contiguous sub-batches on `lanes`
  * streams: lane 0 on `stream`, the others on side streams the library owns (per device), forked from and joined back into
