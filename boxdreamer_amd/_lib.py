@@ -373,8 +373,13 @@ def check_view_counts(counts, t_max: int, query_idx=None) -> None:
 
 
 def view_starts(counts):
-    """[0, c0, c0 + c1, ...]: sample b owns the views [start[b], start[b + 1]) of the packed batch."""
+    """[0, c0, c0 + c1, ...]: sample b owns the views [start[b], start[b + 1]) of the packed batch.  Every sample needs a view: the
+    kernels that take a sample's query view from these offsets (csrc/layout.hip: query_view_of) have nothing to clamp an empty
+    sample to, and would address the next sample's rows -- or rows past the buffer."""
     out = [0]
+    for b, c in enumerate(counts):
+        if int(c) <= 0:
+            raise ValueError(f"view_counts[{b}] = {int(c)}: a sample of a ragged batch needs at least one view")
     for c in counts:
         out.append(out[-1] + int(c))
     return out

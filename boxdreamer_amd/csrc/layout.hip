@@ -166,7 +166,10 @@ __global__ __launch_bounds__(256) void prefix_kernel(float* __restrict__ x, cons
 }
 
 // The query view of sample b as a view index of the whole batch.  Uniform batch (vstart == NULL): b * T + qidx[b].  Ragged batch:
-// sample b owns the views [vstart[b], vstart[b + 1]) and qidx[b] counts inside them (clamped to the sample: the offsets are device data).
+// sample b owns the views [vstart[b], vstart[b + 1]) and qidx[b] counts inside them (clamped to the sample: the offsets are device data;
+// q < 0 takes the sample's view 0, q >= n its view n - 1).  An EMPTY sample (n <= 0) has no view to clamp to: it resolves to view
+// vstart[b], which belongs to the next sample -- or, for the last sample, lies past the buffer.  The C entries cannot see the offsets
+// (device data), so the callers that build them refuse an empty sample on the host (_lib.view_starts, _lib.check_view_counts).
 __device__ __forceinline__ int64_t query_view_of(const int32_t* __restrict__ vstart, const int32_t* __restrict__ qidx, int b, int T) {
     if (!vstart) return (int64_t)b * T + (qidx ? qidx[b] : 0);
     const int v0 = vstart[b], n = vstart[b + 1] - v0, q = qidx ? qidx[b] : 0;

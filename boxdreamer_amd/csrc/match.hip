@@ -16,6 +16,15 @@
 namespace {
 
 constexpr int MAXL = 1024;
+constexpr float BACKGROUND = -1.0f;      // inv[] entry of a background patch (a foreground patch's inverse norm lies in [0, 1e12])
+
+// Every product and sum rounded on its own, as the reference's fp32 tensor expression rounds them.  Contracted into v_fmac_f32
+// (hipcc's default; __fmul_rn / __fadd_rn do not stop it) the luminance of a pixel near the threshold lands on the other side of it,
+// and one flipped patch moves a score by 1e4 * c_other / L^2.
+__device__ __forceinline__ float luminance(float r, float g, float b) {
+#pragma clang fp contract(off)
+    return 0.299f * r + 0.587f * g + 0.114f * b;
+}
 
 // one workgroup (4 waves) per view
 __global__ __launch_bounds__(256) void match_sums_kernel(const float* __restrict__ feats, const void* __restrict__ images,
@@ -37,17 +46,24 @@ __global__ __launch_bounds__(256) void match_sums_kernel(const float* __restrict
         if (lane == 0) {
             const int py = (int)floorf((float)(l / g) * ((float)H / (float)g)), px = (int)floorf((float)(l % g) * ((float)W / (float)g));
             const size_t o = (size_t)v * 3 * plane + (size_t)(py < H ? py : H - 1) * W + (px < W ? px : W - 1);
-            const float lum = 0.299f * load_any(images, o, img_dtype) + 0.587f * load_any(images, o + plane, img_dtype) +
-                              0.114f * load_any(images, o + 2 * plane, img_dtype);
+            const float lum = luminance(load_any(images, o, img_dtype), load_any(images, o + plane, img_dtype),
+                                        load_any(images, o + 2 * plane, img_dtype));
             const bool fg = lum > thr;
-            inv[l] = fg ? 1.0f / fmaxf(sqrtf(ss), 1e-12f) : 0.f;
+            inv[l] = fg ? 1.0f / fmaxf(sqrtf(ss), 1e-12f) : BACKGROUND;
             if (fg) atomicAdd(&cnt, 1);
         }
     }
     __syncthreads();
     for (int d = tid; d < D; d += 256) {
         float s = 0.f;
-        for (int l = 0; l < L; ++l) s = fmaf(f[(int64_t)l * D + d], inv[l], s);
+        for (int l = 0; l < L; ++l) {
+            // a background patch contributes 0 whatever it holds: the reference fills its pairs with -1e4, and NaN * 0 / Inf * 0 would
+            // turn the view's scores into 0.  A select, not a branch (a branch here costs the loop its unrolled loads: +50 % time);
+            // finite features give the same sum as x * 0 + s.
+            const float w = inv[l];
+            const float x = f[(int64_t)l * D + d];
+            s = fmaf(w == BACKGROUND ? 0.f : x, w, s);
+        }
         sums[(int64_t)v * D + d] = s;
     }
     if (tid == 0) counts[v] = (float)cnt;
@@ -67,7 +83,11 @@ __global__ __launch_bounds__(64) void match_scores_kernel(const float* __restric
     dot = wave_sum(dot);
     if (lane == 0) {
         const float ll = (float)L * (float)L;
-        const float invalid = ll - counts[b * T + q] * counts[b * T + r];
+        const float pairs = counts[b * T + q] * counts[b * T + r];
+        // a view without foreground: the reference fills EVERY pair with -1e4, so non-finite features of the other view (NaN * 0
+        // in the dot product) do not reach the score
+        if (pairs == 0.f) dot = 0.f;
+        const float invalid = ll - pairs;
         float m = (dot - 1e4f * invalid) / ll;
         if (!(m == m) || fabsf(m) == INFINITY) m = 0.f;            // nan_to_num(0, 0, 0)
         scores[b * (T - 1) + n] = m;
