@@ -126,7 +126,7 @@ EXPORTS = [
     "bd_lanes_prepare", "bd_encoder_workspace_bytes_lanes", "bd_encoder_forward_lanes", "bd_decoder_workspace_bytes_lanes",
     "bd_decoder_forward_lanes", "bd_pose_metrics_workspace_bytes", "bd_pose_metrics", "bd_crop_resize_frames",
     "bd_attention_varlen", "bd_query_substitute_varlen", "bd_gather_query_rows_f32_varlen", "bd_gather_query_tokens_varlen",
-    "bd_decoder_workspace_bytes_ragged", "bd_decoder_forward_ragged",
+    "bd_decoder_workspace_bytes_ragged", "bd_decoder_forward_ragged", "bd_gather_view_rows",
 ]
 
 _lib = None
@@ -200,6 +200,7 @@ def load() -> C.CDLL:
     lib.bd_decoder_workspace_bytes_ragged.argtypes = [C.POINTER(BetrWeights), i, i, i]
     lib.bd_decoder_workspace_bytes_ragged.restype = sz
     lib.bd_decoder_forward_ragged.argtypes = [C.POINTER(BetrWeights), vp, i, vp, i64, vp, vp, i, i, i, i, vp, vp, vp, sz, i, vp]
+    lib.bd_gather_view_rows.argtypes = [vp, i64, i, vp, i64, i, vp, vp, i64, i, i, i, i, vp, vp, vp, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:
@@ -388,6 +389,53 @@ def view_starts(counts):
 def packing_index(counts, t_max: int):
     """Flat indices into the (B * T_max) padded view slots of the valid views, sample by sample: packed = padded.flatten(0, 1)[index]."""
     return [b * t_max + t for b, c in enumerate(counts) for t in range(c)]
+
+
+# ---- Reference bank (cache.RefFeatureBank, bd_gather_view_rows): the batch dict's `ref_rows` table, host side.  Like the view counts it is
+# a HOST value; the kernel's `src` table and the list of slots to encode are derived from it without reading anything back.
+def ref_rows_table(ref_rows, B: int, t_max: int):
+    """`ref_rows` (a (B, T_max) CPU integer tensor or a nested list of ints; >= 0: bank row, -1: encode this slot) -> list of B lists of
+    T_max Python ints.  A tensor that is not on the CPU raises TypeError (reading it would synchronise the device on every forward);
+    another shape raises ValueError."""
+    if isinstance(ref_rows, torch.Tensor):
+        if ref_rows.device.type != "cpu":
+            raise TypeError("ref_rows must be host integers (a nested list or a CPU int tensor): reading a device tensor would synchronise "
+                            "the device on every forward")
+        if ref_rows.dtype.is_floating_point or ref_rows.dtype == torch.bool:
+            raise TypeError(f"ref_rows must be an integer tensor, got {ref_rows.dtype}")
+        if tuple(ref_rows.shape) != (B, t_max):
+            raise ValueError(f"ref_rows must be (B, T_max) = {(B, t_max)}, got {tuple(ref_rows.shape)}")
+        return [[int(r) for r in row] for row in ref_rows.tolist()]
+    rows = [list(r) for r in ref_rows]
+    if len(rows) != B or any(len(r) != t_max for r in rows):
+        raise ValueError(f"ref_rows must be (B, T_max) = {(B, t_max)}, got {len(rows)} rows of lengths {sorted({len(r) for r in rows})}")
+    if any(isinstance(r, bool) or int(r) != r for row in rows for r in row):
+        raise TypeError("ref_rows must be integers")
+    return [[int(r) for r in row] for row in rows]
+
+
+def check_ref_rows(rows, counts, bank_len: int) -> None:
+    """Every VALID slot (t < counts[b]) holds a row of the bank or -1; padded slots are ignored whatever they hold."""
+    for b, (row, c) in enumerate(zip(rows, counts)):
+        for t in range(c):
+            if not -1 <= row[t] < bank_len:
+                raise ValueError(f"ref_rows[{b}][{t}] = {row[t]} is neither -1 (encode this slot) nor a row of the bank (it holds {bank_len})")
+
+
+def gather_sources(rows, counts, t_max: int):
+    """(src, encode) for one bd_gather_view_rows launch over the valid views, sample by sample (packing_index's order): src[v] is the
+    bank row of packed view v, or -(k + 1) when the view is the k-th one to encode; encode[k] is that view's flat index into the
+    (B * T_max) padded slots -- images.flatten(0, 1)[encode] is what the encoder runs on."""
+    src, encode = [], []
+    for b, c in enumerate(counts):
+        for t in range(c):
+            r = rows[b][t]
+            if r >= 0:
+                src.append(r)
+            else:
+                encode.append(b * t_max + t)
+                src.append(-len(encode))
+    return src, encode
 
 
 def attention_work_list(counts, heads: int, tokens_per_view: int, q_block: int, query_only: bool = False):

@@ -202,7 +202,10 @@ class BETR(nn.Module):
         attends over its own views only, on packed token rows (bd_decoder_forward_ragged): its result is bit-identical to the sample
         run alone at T = view_counts[b].  pretrain_rgb_feat is then either the packed features of the sum(view_counts) valid views,
         (n_views, P, C) in sample order -- what the encoder returns for the packed images, with its operand copy -- or padded
-        (B, T_max, P, C), which is packed and re-cast here (slow path)."""
+        (B, T_max, P, C), which is packed and re-cast here (slow path).
+
+        pretrain_rgb_feat may also be a features.OperandOnly (the operand copy alone, from cache.RefFeatureBank): (B, T, P, C), or
+        packed (n_views, P, C) for a ragged batch.  It must be in this decoder's feature class; ValueError otherwise."""
         assert rgbs is not None, "rgbs input should not be None"
         B, T, _, H, W = rgbs.shape
         assert H == W == self.img_size, f"H and W should be equal to img_size {self.img_size}, got {H}x{W}"
@@ -215,7 +218,8 @@ class BETR(nn.Module):
                 return self._forward_ragged(pose_feat, rgbs, masks, pretrain_rgb_feat, counts)
         _lib.require_gpu()
         lib = _lib.load()
-        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat)
+        only = isinstance(pretrain_rgb_feat, features.OperandOnly)       # an operand copy with no fp32 tensor behind it (a reference bank)
+        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat.operand if only else pretrain_rgb_feat)
         prec = self.hip_precision
         pid = _lib.prec_id(prec)
         w = self._weights(dev, prec).struct
@@ -241,7 +245,10 @@ class BETR(nn.Module):
         query_idx = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
         np_ = _lib.planes(prec)
         fcls = self.feats_class(prec)
-        feats16 = features.operand_of(pretrain_rgb_feat, fcls)
+        if only:              # nothing to re-cast from: a copy that does not fit is an error
+            feats16 = pretrain_rgb_feat.checked(fcls, np_ * B * T * P * D, dev)
+        else:
+            feats16 = features.operand_of(pretrain_rgb_feat, fcls)
         if feats16 is not None and (feats16.numel() != np_ * B * T * P * D or feats16.device != dev):
             feats16 = None
         if feats16 is None:   # features without an operand copy (computed elsewhere, copied, sliced): explicit re-cast
@@ -268,7 +275,8 @@ class BETR(nn.Module):
         B, T, _, H, W = rgbs.shape
         _lib.require_gpu()
         lib = _lib.load()
-        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat)
+        only = isinstance(pretrain_rgb_feat, features.OperandOnly)
+        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat.operand if only else pretrain_rgb_feat)
         prec = self.hip_precision
         pid = _lib.prec_id(prec)
         w = self._weights(dev, prec).struct
@@ -295,7 +303,12 @@ class BETR(nn.Module):
         query_view = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
         np_ = _lib.planes(prec)
         fcls = self.feats_class(prec)
-        feats16 = features.operand_of(pretrain_rgb_feat, fcls) if packed_feats else None
+        if only:
+            if not packed_feats:
+                raise ValueError(f"operand-only features of a ragged batch must be packed ({n_views}, {P}, {D}), got {tuple(pretrain_rgb_feat.shape)}")
+            feats16 = pretrain_rgb_feat.checked(fcls, np_ * n_views * P * D, dev)
+        else:
+            feats16 = features.operand_of(pretrain_rgb_feat, fcls) if packed_feats else None
         if feats16 is not None and (feats16.numel() != np_ * n_views * P * D or feats16.device != dev):
             feats16 = None
         if feats16 is None:

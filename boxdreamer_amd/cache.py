@@ -17,6 +17,15 @@ The facade's load-time calibration (model.py / calibrate.py) runs inside the FIR
 BEFORE that are stale.  `merge_cached_features` notices (stamp mismatch), warns once, and encodes every view of the batch afresh instead --
 never a silent mix of two promotion states, never an exception in the middle of a sweep.  Call `model.calibrate(data)` (or one forward)
 before `cache.encode` to keep the saving.
+
+RefFeatureBank (below) is the serving form of the same idea: many objects, each with its own number of references, encoded once
+into ONE device-resident store in the decoder's operand format (no fp32 copy: 3 bytes per element in the default mode against 7);
+a batch -- uniform or ragged (`view_counts`) -- names its references by bank row and one bd_gather_view_rows launch assembles the
+decoder's feature operand from those rows and the freshly encoded query views:
+    bank = RefFeatureBank(model.rgb_encoder, keep_images=True)
+    rows = bank.add(ref_images)                               # (R, 3, S, S) or (B, R, 3, S, S) -> CPU int64 row ids, stable for good
+    data["ref_bank"], data["ref_rows"] = bank, table          # (B, T_max) host ints: >= 0 bank row, -1 "encode this slot of data['images']"
+    model(data)
 """
 from __future__ import annotations
 
@@ -27,6 +36,7 @@ import torch
 from . import _lib, features
 
 _WARNED_STALE = False
+_WARNED_STALE_BANK = False
 
 
 def _new_operand(pid: int, n_views: int, P: int, C: int, dtype, dev) -> torch.Tensor:
@@ -110,6 +120,192 @@ class RefFeatureCache:
         for dst, src in zip(_plane_views(full16, pid, B * T, P, C), _plane_views(f16, pid, B * R, P, C)):
             dst.reshape(B, T, P, C)[valid] = src
         return features.attach(full32, full16, pid, features.stamp_of(ref_feats)), valid
+
+
+def _copy_views(dst16, dst_v0: int, src16, n: int, pid: int, P: int, C: int) -> None:
+    """Views [0, n) of operand tensor src16 -> views [dst_v0, dst_v0 + n) of dst16 (each of any capacity): contiguous
+    slice copies per plane; F16C8's lo8 plane moves as bytes at the head of plane-1 storage (_plane_views)."""
+    if n <= 0:
+        return
+    e = P * C
+    if _lib.planes(pid) == 1:
+        dst16.reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16.reshape(-1)[:n * e])
+        return
+    dst16[0].reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[0].reshape(-1)[:n * e])
+    if pid == _lib.PREC_F16C8:
+        dst16[1].view(torch.uint8).reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[1].view(torch.uint8).reshape(-1)[:n * e])
+    else:
+        dst16[1].reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[1].reshape(-1)[:n * e])
+
+
+class RefFeatureBank:
+    """Device-resident store of reference features in the decoder's operand format, addressed by row (one row = one view).
+
+    add() runs crops through the encoder once and appends their operand copy; the fp32 copy is dropped (the decoder never reads it).
+    All rows live in one tensor that grows geometrically; row ids never change, whatever is added later.  `stamp` is the encoder state
+    (encoder.state_stamp: operand class + per-Linear promotion) plus the operand class the rows are in.  When the encoder's state has
+    moved on since (the load-time calibration ran, calibrate.set_state was applied), the bank is stale: with keep_images=True it
+    re-encodes every row from the crops it kept (in the dtype they came in) -- once, with one warning -- and with keep_images=False it
+    raises RuntimeError; rows of two promotion states are never mixed."""
+
+    def __init__(self, encoder, keep_images: bool = True):
+        self.encoder = encoder                                 # a DinoV2Wrapper
+        self.keep_images = bool(keep_images)
+        self.refresh_count = 0
+        self._tables = {}       # (ref_rows of the valid slots, counts, T_max, device) -> device tables of one gather launch
+        self.clear()
+
+    def clear(self) -> None:
+        """Drop every row (ids start again at 0) and the kept crops."""
+        self._t16, self._cap, self._n = None, 0, 0
+        self._pid, self._P, self._C, self._stamp = None, 0, 0, None
+        self._images = []       # [(first row, crops (N, 3, S, S))] when keep_images
+
+    def __len__(self) -> int:
+        return self._n
+
+    @property
+    def stamp(self):
+        """(encoder.state_stamp under which the rows were encoded, operand class), None while the bank is empty."""
+        return self._stamp
+
+    @property
+    def operand_class(self):
+        return self._pid
+
+    @property
+    def tokens_per_view(self) -> int:
+        """P: patch tokens of one view (0 while the bank is empty)."""
+        return self._P
+
+    @property
+    def feature_dim(self) -> int:
+        """C: feature channels (0 while the bank is empty)."""
+        return self._C
+
+    @property
+    def bytes_per_view(self) -> int:
+        """Bytes of one row in the bank (all planes)."""
+        if self._pid is None:
+            return 0
+        one = self._P * self._C * (1 if self._pid == _lib.PREC_FP8 else 2)
+        return one + (self._P * self._C * (1 if self._pid == _lib.PREC_F16C8 else 2) if _lib.planes(self._pid) == 2 else 0)
+
+    def _now(self):
+        return (self.encoder.model.state_stamp(self.encoder.prec), int(self.encoder.model.feats_class(self.encoder.prec)))
+
+    def is_stale(self) -> bool:
+        return self._n > 0 and self._stamp != self._now()
+
+    def _reserve(self, need: int, dev) -> None:
+        if self._t16 is not None and need <= self._cap and self._t16.device == dev:
+            return
+        cap = max(need, 2 * self._cap, 8)
+        new = _new_operand(self._pid, cap, self._P, self._C, _lib.op_dtype(self._pid), dev)
+        if self._t16 is not None:       # growth re-lays the planes out: plane 1 starts at the new capacity
+            _copy_views(new, 0, self._t16.to(dev), self._n, self._pid, self._P, self._C)
+        self._t16, self._cap = new, cap
+
+    def _append(self, images: torch.Tensor) -> None:
+        if images.device != self.encoder.get_device():
+            self.encoder.to_device(images.device)
+        feats = self.encoder.predict(images)                   # (N, P, C) fp32, tagged; only the operand copy is kept
+        f16, pid = RefFeatureCache._feats16_view(feats)
+        n, P, C = feats.shape
+        if self._n == 0:
+            self._pid, self._P, self._C, self._stamp = _lib.operand_prec(pid), int(P), int(C), self._now()
+            self._t16, self._cap = None, 0
+        elif (_lib.operand_prec(pid), int(P), int(C)) != (self._pid, self._P, self._C):
+            raise ValueError(f"the bank holds ({self._P}, {self._C}) views of operand class {self._pid}; got ({P}, {C}) of class {pid}")
+        self._reserve(self._n + n, images.device)
+        _copy_views(self._t16, self._n, f16, n, self._pid, P, C)
+        if self.keep_images:
+            self._images.append((self._n, images))
+        self._n += n
+
+    def add(self, images: torch.Tensor) -> torch.Tensor:
+        """images (R, 3, S, S) or (B, R, 3, S, S) in [0, 1] -> CPU int64 row ids of the same leading shape.  Earlier ids stay valid."""
+        if images.dim() not in (4, 5):
+            raise ValueError(f"expected (R, 3, S, S) or (B, R, 3, S, S), got {tuple(images.shape)}")
+        lead = tuple(images.shape[:-3])
+        flat = images.reshape(-1, *images.shape[-3:])
+        self.ensure_fresh()                                    # never append rows of a new encoder state to rows of an old one
+        n0 = self._n
+        if flat.shape[0]:
+            self._append(flat.clone() if self.keep_images else flat)
+        return torch.arange(n0, self._n, dtype=torch.int64).reshape(lead)
+
+    def ensure_fresh(self) -> bool:
+        """Bring a stale bank up to the encoder's state.  Returns True when the rows were re-encoded.  RuntimeError when they cannot be."""
+        if not self.is_stale():
+            return False
+        if not self.keep_images:
+            raise RuntimeError("RefFeatureBank: the rows were encoded under another precision / promotion state of the encoder (the load-time "
+                               "calibration ran, or calibrate.set_state was applied, after add()) and the bank kept no crops to re-encode "
+                               "them from (keep_images=False): clear() and add() the references again")
+        global _WARNED_STALE_BANK
+        if not _WARNED_STALE_BANK:
+            _WARNED_STALE_BANK = True
+            warnings.warn("BoxDreamer HIP path: the reference bank was filled under another precision / promotion state of the encoder (the "
+                          "load-time calibration ran, or calibrate.set_state was applied, after RefFeatureBank.add); re-encoding its rows "
+                          "from the kept crops, once.", stacklevel=3)
+        # the new store is built on the side and swapped in when every row is there: a re-encode that fails part-way (out of memory,
+        # say) leaves the rows and the kept crops as they were, and the failure is what the caller sees
+        new = RefFeatureBank(self.encoder, keep_images=True)
+        for _, img in self._images:                            # in row order: ids are unchanged
+            new._append(img)
+        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images"):
+            setattr(self, k, getattr(new, k))
+        self.refresh_count += 1
+        return True
+
+    def image_of(self, row: int) -> torch.Tensor:
+        """The kept crop of a row (3, S, S) (keep_images=True)."""
+        for r0, img in self._images:
+            if r0 <= row < r0 + img.shape[0]:
+                return img[row - r0]
+        raise KeyError(f"row {row}: no crop kept")
+
+    def tables(self, rows, counts, t_max: int, dev):
+        """(src int32 [n_views], encode index int64 [n_fresh] or None, n_fresh) on `dev` for a validated host table: built on the host,
+        uploaded once per distinct (rows of the valid slots, counts, T_max) and kept, like BETR.ragged_index."""
+        key = (tuple(tuple(r[:c]) for r, c in zip(rows, counts)), tuple(counts), int(t_max), str(dev))
+        hit = self._tables.get(key)
+        if hit is None:
+            if len(self._tables) >= 64:
+                self._tables.clear()
+            src, encode = _lib.gather_sources(rows, counts, t_max)
+            hit = (torch.tensor(src, dtype=torch.int32).to(dev),
+                   torch.tensor(encode, dtype=torch.int64).to(dev) if encode else None, len(encode))
+            self._tables[key] = hit
+        return hit
+
+    def gather(self, src: torch.Tensor, fresh, lead) -> "features.OperandOnly":
+        """One bd_gather_view_rows launch: the operand of len(src) views from bank rows and `fresh` (the encoder's tagged output for
+        the views encoded in this forward, or None) -> features.OperandOnly of the logical shape (*lead, P, C); `lead` is (B, T) for a
+        uniform batch, (n_views,) for a packed ragged one."""
+        from . import hip_ops
+        n_views = int(src.numel())
+        lead = tuple(int(x) for x in lead)
+        if len(lead) not in (1, 2) or (lead[0] * lead[1] if len(lead) == 2 else lead[0]) != n_views:
+            raise ValueError(f"src names {n_views} views, the leading shape {lead} does not")
+        n_fresh, f16 = 0, None
+        pid, P, C = self._pid, self._P, self._C
+        if fresh is not None:
+            f16, fpid = RefFeatureCache._feats16_view(fresh)
+            n_fresh = int(fresh.shape[0])
+            if pid is None:                                    # an empty bank: every view is fresh
+                pid, P, C = _lib.operand_prec(fpid), int(fresh.shape[1]), int(fresh.shape[2])
+            elif (_lib.operand_prec(fpid), tuple(fresh.shape[1:])) != (pid, (P, C)) or features.stamp_of(fresh) != self._stamp[0]:
+                raise ValueError("the freshly encoded views and the bank's rows differ in operand class, shape or encoder state")
+        if pid is None:
+            raise ValueError("nothing to gather: the bank is empty and no view was encoded")
+        dev = src.device
+        out16 = torch.empty((2, n_views * P, C) if _lib.planes(pid) == 2 else (n_views * P, C), dtype=_lib.op_dtype(pid), device=dev)
+        hip_ops.gather_view_rows(self._t16 if self._n else None, self._n, f16, n_fresh, src, out16, n_views, P, C, prec=pid,
+                                 bank_plane=self._cap * P * C if _lib.planes(pid) == 2 else 0)
+        stamp = self._stamp[0] if self._stamp is not None else features.stamp_of(fresh)
+        return features.OperandOnly(lead + (P, C), out16, pid, stamp)
 
 
 def merge_cached_features(encoder, images: torch.Tensor, cached: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:

@@ -132,8 +132,11 @@ def self_check(encoder, decoder, images, bbox_feat, masks) -> float:
     return float((cur - ref).abs().max())
 
 
+MAX_SAMPLES = 2      # samples of a batch the self-check measures on (model.py prepares exactly these for a banked batch)
+
+
 @torch.no_grad()
-def calibrate(encoder, decoder, images, bbox_feat, masks, *, budget: float = BUDGET, promote: bool = True, max_samples: int = 2,
+def calibrate(encoder, decoder, images, bbox_feat, masks, *, budget: float = BUDGET, promote: bool = True, max_samples: int = MAX_SAMPLES,
               verbose: bool = False) -> dict:
     """Measure the default mode against the all-promoted reference on `max_samples` samples of the given batch and, if it exceeds
     `budget`, promote the cheapest sufficient set of units.  Returns (and stores in `decoder.hip_calibration`) the report; warns when

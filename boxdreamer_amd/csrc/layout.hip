@@ -305,6 +305,58 @@ __global__ __launch_bounds__(256) void render_heat_kernel(const float* __restric
     else ((_Float16*)out)[o] = (_Float16)v;
 }
 
+// ---------------------------------------------------------------- segmented copy of whole views between operand tensors (bd_gather_view_rows)
+// A view is up to three contiguous byte runs ("segments"): plane 0, plane 1 (the split classes' second 16-bit plane, or F16C8's one-byte
+// lo8 plane, packed view after view at the head of plane-1 storage) and the optional fp32 copy.  Each run is a whole number of 16-byte
+// chunks (the host checks P * dim % 16 == 0 and the alignment of every base), so the kernel moves nothing but 16-byte vectors and never
+// looks at an element: NaN payloads and e4m3 bytes pass through as they are.  The grid is (view, block of GATHER_PER_WG chunks of the
+// view's concatenated runs); src[view] is uniform over the workgroup (one scalar load), an entry outside its table ends the workgroup
+// before it touches memory.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int GATHER_UNROLL = 4, GATHER_PER_WG = 256 * GATHER_UNROLL;
+
+struct GatherSeg {
+    const char* bank;      // view v of the segment starts at base + v * view_bytes, in all three tensors
+    const char* fresh;
+    char* out;
+    int64_t view_bytes;    // 0: segment absent
+};
+struct GatherViewArgs {
+    GatherSeg seg[3];
+    const int32_t* src;
+    int bank_views, n_fresh;
+    unsigned blocks_per_view;
+};
+
+__global__ __launch_bounds__(256) void gather_view_rows_kernel(const GatherViewArgs a) {
+    const unsigned view = blockIdx.x / a.blocks_per_view, blk = blockIdx.x - view * a.blocks_per_view;
+    const int s = a.src[view];
+    const bool fresh = s < 0;
+    const int64_t sv = fresh ? -(int64_t)s - 1 : (int64_t)s;
+    if (sv >= (int64_t)(fresh ? a.n_fresh : a.bank_views)) return;       // inconsistent entry: the view's output stays untouched
+    u32x4 v[GATHER_UNROLL];
+    char* dst[GATHER_UNROLL];
+#pragma unroll
+    for (int i = 0; i < GATHER_UNROLL; ++i) {
+        int64_t off = ((int64_t)blk * GATHER_PER_WG + i * 256 + threadIdx.x) * 16;
+        dst[i] = nullptr;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int64_t vb = a.seg[k].view_bytes;
+            if (!dst[i] && off >= 0) {
+                if (off < vb) {
+                    v[i] = *(const u32x4*)((fresh ? a.seg[k].fresh : a.seg[k].bank) + sv * vb + off);
+                    dst[i] = a.seg[k].out + (int64_t)view * vb + off;
+                }
+                off -= vb;        // (negative from here on: the chunk belonged to segment k)
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < GATHER_UNROLL; ++i)
+        if (dst[i]) *(u32x4*)dst[i] = v[i];
+}
+
 inline unsigned nblk(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
@@ -433,6 +485,61 @@ extern "C" int bd_gather_query_tokens_varlen(const float* x, const int32_t* view
     const int64_t total = (int64_t)B * P * (dim / 8);
     hipStream_t s = (hipStream_t)stream;
     BD_PREC_SWITCH(gather_query_kernel, dim3(nblk(total)), dim3(256), 0, s, x, query_view, view_start, out16, out_plane, B, 0, P, dim)
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+// Assembles the decoder's feature operand of one batch from cached views (a device-resident bank) and the views encoded in this
+// forward -- what replaces running the references through the encoder again for every query (the reference model does:
+// BoxDreamerModel.py:274-285).  See include/boxdreamer_hip.h.
+extern "C" int bd_gather_view_rows(const void* bank16, int64_t bank_plane, int bank_views, const void* fresh16, int64_t fresh_plane,
+                                   int n_fresh, const int32_t* src, void* out16, int64_t out_plane, int n_views, int P, int dim,
+                                   int prec, const float* bank32, const float* fresh32, float* out32, void* stream) {
+    if (!src || !out16 || (bank_views > 0 && !bank16) || (n_fresh > 0 && !fresh16)) return BD_ERR_NULL;
+    if (out32 && ((bank_views > 0 && !bank32) || (n_fresh > 0 && !fresh32))) return BD_ERR_NULL;
+    if (bank_views < 0 || n_fresh < 0 || n_views < 0 || P <= 0 || dim <= 0) return BD_ERR_SHAPE;
+    int esz, plane1;          // bytes per element of plane 0; of plane 1 (0: one plane)
+    switch (prec) {
+        case BD_PREC_BF16: case BD_PREC_F16: esz = 2; plane1 = 0; break;
+        case BD_PREC_FP8: esz = 1; plane1 = 0; break;
+        case BD_PREC_BF16X3: case BD_PREC_F16X3: esz = 2; plane1 = 2; break;
+        case BD_PREC_F16C8: esz = 2; plane1 = 1; break;
+        default: return BD_ERR_DTYPE;
+    }
+    const int64_t elems = (int64_t)P * dim;
+    if (elems % 16) return BD_ERR_ALIGN;
+    const auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (misaligned(bank16) || misaligned(fresh16) || misaligned(out16) || ((uintptr_t)src & 3)) return BD_ERR_ALIGN;
+    if (out32 && (misaligned(bank32) || misaligned(fresh32) || misaligned(out32))) return BD_ERR_ALIGN;
+    if (plane1) {             // plane offsets count 16-bit elements: 16-byte aligned planes, and no overlap with plane 0
+        if (bank_plane % 8 || fresh_plane % 8 || out_plane % 8) return BD_ERR_ALIGN;
+        if ((bank_views > 0 && bank_plane < elems * bank_views) || (n_fresh > 0 && fresh_plane < elems * n_fresh) || out_plane < elems * n_views)
+            return BD_ERR_SHAPE;
+    }
+    // out must not overlap a source: a view copied early would be read back as another view's source.  Byte extents over all planes
+    const auto extent = [&](int64_t plane, int views) { return plane1 ? plane * 2 + elems * plane1 * views : elems * esz * views; };
+    const auto overlap = [](const void* p, int64_t np, const void* q, int64_t nq) {
+        return np > 0 && nq > 0 && (uintptr_t)p < (uintptr_t)q + (uintptr_t)nq && (uintptr_t)q < (uintptr_t)p + (uintptr_t)np;
+    };
+    const int64_t out_bytes = extent(out_plane, n_views);
+    if (overlap(out16, out_bytes, bank16, extent(bank_plane, bank_views)) || overlap(out16, out_bytes, fresh16, extent(fresh_plane, n_fresh)))
+        return BD_ERR_SHAPE;
+    if (out32 && (overlap(out32, elems * 4 * n_views, bank32, elems * 4 * bank_views) || overlap(out32, elems * 4 * n_views, fresh32, elems * 4 * n_fresh)))
+        return BD_ERR_SHAPE;
+    if (n_views == 0) return BD_OK;
+    GatherViewArgs a{};
+    a.seg[0] = {(const char*)bank16, (const char*)fresh16, (char*)out16, elems * esz};
+    if (plane1)
+        a.seg[1] = {(const char*)bank16 + bank_plane * 2, (const char*)fresh16 + fresh_plane * 2, (char*)out16 + out_plane * 2, elems * plane1};
+    if (out32) a.seg[2] = {(const char*)bank32, (const char*)fresh32, (char*)out32, elems * 4};
+    a.src = src;
+    a.bank_views = bank_views;
+    a.n_fresh = n_fresh;
+    const int64_t view_chunks = (a.seg[0].view_bytes + a.seg[1].view_bytes + a.seg[2].view_bytes) / 16;
+    const int64_t bpv = (view_chunks + GATHER_PER_WG - 1) / GATHER_PER_WG;
+    if (bpv * n_views > 0x7fffffffLL) return BD_ERR_SHAPE;
+    a.blocks_per_view = (unsigned)bpv;
+    hipLaunchKernelGGL(gather_view_rows_kernel, dim3((unsigned)(bpv * n_views)), dim3(256), 0, (hipStream_t)stream, a);
     BD_CHECK_LAUNCH();
     return BD_OK;
 }

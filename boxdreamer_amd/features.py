@@ -7,6 +7,9 @@ object's lifetime, `operand_of` returns it only when the object still describes 
 another tensor object that aliases the same storage (a `.view()` / `.reshape()` / `.contiguous()` no-op).  Anything else
 -- a copy, a slice, features computed elsewhere -- has NO operand copy: `operand_of` returns None and the decoder re-casts
 explicitly (counted in `BETR.recast_count`, warned about once), never silently on stale data.
+
+Features that exist as an operand copy ONLY (cache.RefFeatureBank: no fp32 tensor is ever made) travel in `OperandOnly`, an explicit
+carrier the decoder checks and never re-casts.
 """
 from __future__ import annotations
 
@@ -60,3 +63,38 @@ def carry(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     if tag is not None and dst is not src and dst.data_ptr() == tag[2] and dst.numel() == tag[3] and dst.is_contiguous():
         setattr(dst, _ATTR, (tag[0], tag[1], tag[2], tag[3], _version(dst), tag[5] if len(tag) > 5 else None))
     return dst
+
+
+class OperandOnly:
+    """Features that exist in the decoder's operand format ONLY -- what cache.RefFeatureBank assembles with bd_gather_view_rows: there
+    is no fp32 tensor behind them, so nothing to re-cast from.  `shape` is the logical (B, T, P, C) or packed (n_views, P, C) shape,
+    `operand` the operand tensor ([rows, C], or [2, rows, C] for the two-plane classes), `class_id` its operand class and `stamp` the
+    encoder state it was produced under.  BETR.forward checks it the way it checks an attached copy (class, element count, device) and
+    raises where it would have re-cast."""
+
+    def __init__(self, shape, operand: torch.Tensor, class_id: int, stamp=None):
+        self.shape, self.operand, self.class_id, self.stamp = tuple(int(s) for s in shape), operand, int(class_id), stamp
+
+    @property
+    def device(self):
+        return self.operand.device
+
+    def dim(self) -> int:
+        return len(self.shape)
+
+    def numel(self) -> int:
+        n = 1
+        for s in self.shape:
+            n *= s
+        return n
+
+    def checked(self, class_id: int, numel: int, device) -> torch.Tensor:
+        """The operand tensor when it is what the decoder reads (class, element count over all planes, device); ValueError otherwise."""
+        if self.class_id != int(class_id):
+            raise ValueError(f"operand-only features are in operand class {self.class_id}, the decoder reads class {int(class_id)} (its "
+                             "adapter's first Linear changed class after the features were made, or they come from another precision "
+                             "mode); there is no fp32 copy to re-cast from -- refill the reference bank")
+        if self.operand.numel() != int(numel) or self.operand.device != device:
+            raise ValueError(f"operand-only features hold {self.operand.numel()} elements on {self.operand.device}, the decoder needs "
+                             f"{int(numel)} on {device}")
+        return self.operand

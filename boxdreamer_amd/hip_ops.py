@@ -238,6 +238,21 @@ def attention_varlen(qkv16, view_counts, tokens_per_view, heads, head_dim, scale
     return out
 
 
+def gather_view_rows(bank16, bank_views, fresh16, n_fresh, src, out16, n_views, P, dim, *, prec, bank_plane=None, fresh_plane=None,
+                     out_plane=None, bank32=None, fresh32=None, out32=None):
+    """bd_gather_view_rows: out view v = bank view src[v] (src[v] >= 0) or fresh view -(src[v] + 1), whole views of one operand class,
+    one launch.  bank16 / fresh16 / out16: operand tensors ([rows, dim], or [2, rows, dim] for the two-plane classes; the plane offsets
+    default to each tensor's own plane size) -- either source may be None when its view count is 0.  src: device int32 [n_views].
+    bank32 / fresh32 / out32: optional fp32 copies moved the same way.  Returns out16."""
+    lib = _lib.load()
+    pl = [(_plane(t, prec) if t is not None else 0) if given is None else int(given)
+          for t, given in ((bank16, bank_plane), (fresh16, fresh_plane), (out16, out_plane))]
+    check(lib.bd_gather_view_rows(ptr(bank16), pl[0], int(bank_views), ptr(fresh16), pl[1], int(n_fresh), ptr(src), ptr(out16), pl[2],
+                                  int(n_views), int(P), int(dim), prec_id(prec), ptr(bank32), ptr(fresh32), ptr(out32), stream()),
+          "bd_gather_view_rows")
+    return out16
+
+
 def im2col_images(images, patch=14, kpad=640, *, prec="bf16"):
     lib = _lib.load()
     images = images.contiguous()

@@ -105,7 +105,7 @@ class BoxDreamer(nn.Module):
         self._aranges = {}
 
     def calibrate(self, data) -> dict:
-        """Run the precision self-check / promotion on (the first sample of) a batch dict now (forward() does it once by itself)."""
+        """Run the precision self-check / promotion on (the first samples of) a batch dict now (forward() does it once by itself)."""
         images = data["images"]
         B, T = images.shape[:2]
         mask = torch.zeros((B, T), dtype=torch.bool, device=images.device)
@@ -114,6 +114,23 @@ class BoxDreamer(nn.Module):
         counts = self._view_counts(data, B, T)
         if counts is not None:       # ragged batch: the first sample with its own view count (its padded slots are never read)
             images, bbox_feat, mask = images[:1, :counts[0]], bbox_feat[:1, :counts[0]], mask[:1, :counts[0]]
+        bank = data.get("ref_bank")
+        if bank is not None and data.get("ref_rows") is not None:
+            # a banked batch: the images of banked slots are never read (they may hold anything).  Every sample the self-check measures
+            # on takes its references from the crops the bank kept; only those samples are sliced out and copied
+            rows = _lib.ref_rows_table(data["ref_rows"], B, T)
+            _lib.check_ref_rows(rows, counts if counts is not None else [T] * B, len(bank))
+            n = min(calibrate.MAX_SAMPLES, images.shape[0])
+            images, bbox_feat, mask = images[:n], bbox_feat[:n], mask[:n]
+            banked = [(b, t, rows[b][t]) for b in range(n) for t in range(images.shape[1]) if rows[b][t] >= 0]
+            if banked:
+                if not bank.keep_images:
+                    raise RuntimeError("the precision self-check needs the reference crops of the samples it measures on, and the reference "
+                                       "bank kept none (keep_images=False): run model.calibrate(data) on a batch with real images (or one "
+                                       "plain forward) first")
+                images = images.clone()
+                for b, t, r in banked:
+                    images[b, t] = bank.image_of(r).to(images.dtype)
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)
         if self.hip_promotion_file and self.hip_calibrate and calibrate.load_state(self.hip_promotion_file, self.rgb_encoder, self.decoder):
@@ -246,6 +263,22 @@ class BoxDreamer(nn.Module):
                 raise NotImplementedError("view_counts together with cached_rgb_feat (ragged feature cache) is not implemented")
             if not isinstance(self.decoder, BETR):
                 raise NotImplementedError("view_counts needs the BETR decoder")
+        # reference bank (boxdreamer_amd/cache.py: RefFeatureBank): references named by bank row, only the -1 slots are encoded.  The
+        # table is a host value, validated here, before any launch
+        bank, bank_rows = data.get("ref_bank"), None
+        if bank is not None or data.get("ref_rows") is not None:
+            if dense:
+                raise NotImplementedError("ref_bank together with dense_cfg.enable (banked dense-reference mode) is not implemented")
+            if "cached_rgb_feat" in data:
+                raise NotImplementedError("ref_bank together with cached_rgb_feat: give the references one way or the other")
+            if not isinstance(self.decoder, BETR):
+                raise NotImplementedError("ref_bank needs the BETR decoder")
+            if bank is None or data.get("ref_rows") is None:
+                raise KeyError("the batch dict needs both 'ref_bank' (a cache.RefFeatureBank) and 'ref_rows' (its (B, T_max) host table)")
+            if bank.encoder is not self.rgb_encoder:
+                raise ValueError("ref_bank was built on another encoder than this model's rgb_encoder")
+            bank_rows = _lib.ref_rows_table(data["ref_rows"], B, T)
+            _lib.check_ref_rows(bank_rows, counts if counts is not None else [T] * B, len(bank))
 
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)                            # BoxDreamerModel.py:279-282
@@ -272,17 +305,19 @@ class BoxDreamer(nn.Module):
                 data["hip_precision"]["ragged_views"] = sum(counts)
         ar = self._arange(B, dev)
         decoded = None
-        if counts is not None:
+        if bank is not None:
+            # (hip_graph: a banked batch takes this eager branch, like a ragged one)
+            rgb_feature = self._banked_features(data, bank, bank_rows, images, counts)
+            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
+            if counts is not None:
+                self._defer_query_check(query_idx, qi, self.decoder.ragged_index(counts, T, dev)[1])
+        elif counts is not None:
             # (hip_graph: a ragged batch takes this eager branch -- capture of ragged shapes is a follow-up)
             # the encoder and the decoder see the sum(counts) real views only, packed sample by sample; padded slots are never read
             index, view_start = self.decoder.ragged_index(counts, T, dev)
             rgb_feature = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, index))
             query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
-            if not (isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda):
-                # query_idx lives on the device: "is it one of the sample's views" travels with the deferred mask verdict (no sync here)
-                beyond = (qi >= (view_start[1:] - view_start[:-1]).long()).any()
-                err = self.decoder.mask_error
-                self.decoder.mask_error = beyond if err is None else (err | beyond)
+            self._defer_query_check(query_idx, qi, view_start)
         elif (self.hip_graph and not dense and "cached_rgb_feat" not in data and not self.training and images.is_cuda
                 and isinstance(self.decoder, BETR) and not torch.cuda.is_current_stream_capturing()):
             heat, kp_px, kn, _ = self._graphed(images, pose_feat, qi, sig)
@@ -336,6 +371,32 @@ class BoxDreamer(nn.Module):
         data["pred_intrinsics"] = data["intrinsics"]
         self.host_syncs_per_forward = syncs
         return data
+
+    def _defer_query_check(self, query_idx, qi, view_start) -> None:
+        """Ragged batch, query_idx on the device (a host one was checked before any launch): "is it one of the sample's views" travels
+        with the decoder's deferred mask verdict (no sync here)."""
+        if isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda:
+            return
+        beyond = (qi >= (view_start[1:] - view_start[:-1]).long()).any()
+        err = self.decoder.mask_error
+        self.decoder.mask_error = beyond if err is None else (err | beyond)
+
+    def _banked_features(self, data, bank, rows, images, counts):
+        """The decoder's feature operand of a banked batch (uniform: counts None): a stale bank is refreshed first (this runs after the
+        calibration branch, so a bank filled before the first forward just works), the -1 slots among the valid views are encoded,
+        packed, in ONE predict call, and ONE bd_gather_view_rows launch assembles the operand of the B * T (uniform) or
+        sum(view_counts) (ragged) views from bank rows and those fresh views.  Images in banked or padded slots are never read; no
+        fp32 features exist on this path (features.OperandOnly)."""
+        B, T = images.shape[:2]
+        refreshed = bank.ensure_fresh()
+        cts = counts if counts is not None else [T] * B
+        n_views = sum(cts)
+        src, encode, n_fresh = bank.tables(rows, cts, T, images.device)
+        fresh = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, encode)) if n_fresh else None
+        feats = bank.gather(src, fresh, (B, T) if counts is None else (n_views,))
+        if "hip_precision" in data:
+            data["hip_precision"]["ref_bank"] = {"banked_views": n_views - n_fresh, "encoded_views": n_fresh, "refreshed": bool(refreshed)}
+        return feats
 
     def _graphed(self, images, pose_feat, qi, sig=None):
         """Replay (capturing first, per batch shape) encoder -> decoder -> corner decode as one HIP graph; returns the graph's STATIC

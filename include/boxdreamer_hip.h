@@ -300,6 +300,23 @@ int bd_gather_query_rows_f32_varlen(const float* x, const int32_t* view_start, c
 int bd_gather_query_tokens_varlen(const float* x, const int32_t* view_start, const int32_t* query_view, void* out16, int64_t out_plane,
                                   int B, int P, int dim, int prec, void* stream);
 
+/* Segmented copy of whole views between operand tensors of ONE class: the decoder's feature operand of a batch (uniform or ragged),
+ * assembled from a device-resident bank of cached reference views and the views the encoder produced in this forward -- in place of
+ * re-encoding an object's references for every query (BoxDreamerModel.py:274-285).  Output view v is bank view s = src[v] when
+ * s >= 0, fresh view -(s + 1) when s < 0 (src: device int32 [n_views]).  Per view: plane 0 (P * dim elements), and for the two-plane
+ * classes plane 1 -- P * dim 16-bit elements (BF16X3, F16X3), or P * dim BYTES for F16C8, whose lo8 plane is packed row-wise at the
+ * head of plane-1 storage: view v lives at byte v * P * dim of plane 1 in all three tensors, whatever their plane offsets.  *_plane:
+ * offset of plane 1 in 16-bit elements (ignored by one-plane classes), a multiple of 8 and at least views * P * dim.  Classes:
+ * BD_PREC_BF16, _F16, _FP8, _BF16X3, _F16X3, _F16C8 (BD_ERR_DTYPE otherwise).  bank32 / fresh32 / out32: optional fp32 copies
+ * [views, P, dim] moved the same way; out32 == NULL: no fp32 traffic.  An entry of src outside its table (s >= bank_views,
+ * -(s + 1) >= n_fresh) leaves that view's output bytes untouched and the others are copied (bd_attention_varlen's convention for
+ * inconsistent device data).  Checked before any launch: NULL pointers (a table may be NULL when its view count is 0) BD_ERR_NULL;
+ * negative counts, a plane 1 that starts inside plane 0, an out tensor whose bytes overlap bank's or fresh's BD_ERR_SHAPE; P * dim % 16 != 0, a pointer or a plane offset that is not
+ * 16-byte aligned BD_ERR_ALIGN; n_views == 0 returns BD_OK without a launch.  One launch of 16-byte vector copies. */
+int bd_gather_view_rows(const void* bank16, int64_t bank_plane, int bank_views, const void* fresh16, int64_t fresh_plane, int n_fresh,
+                        const int32_t* src, void* out16, int64_t out_plane, int n_views, int P, int dim, int prec,
+                        const float* bank32, const float* fresh32, float* out32, void* stream);
+
 /* BETR.unpatchify + 2*sigmoid-1 (betr.py:230-247, 432-435): proj fp32 [B*P, p*p*c] ->
  * logits, heat fp32 [B, c, size, size]. */
 int bd_unpatchify_sigmoid(const float* proj, float* logits, float* heat, int B, int channels, int size,
