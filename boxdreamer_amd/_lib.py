@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -26,7 +27,6 @@ F16C8_D = 11                                           # lo planes are scaled 2^
 PREC_NAMES = {"bf16": PREC_BF16, "fp16": PREC_F16, "f16": PREC_F16, "bf16x3": PREC_BF16X3, "fp8": PREC_FP8,
               "bf16x3_attn_x3": PREC_BF16X3_ATTN_X3, "f16c8": PREC_F16C8, "f16c8_qk16": PREC_F16C8_QK16,
               "f16x3": PREC_F16X3, "f16x3_attn_x3": PREC_F16X3_ATTN_X3}
-_F16X3_FAMILY = (PREC_F16X3, PREC_F16X3_ATTN_X3)
 # "fp8_mixed" (configs[4], usable form): the e4m3 class with the precision-critical Linears kept in bf16 through the per-Linear
 # promotion bits -- a POLICY over BD_PREC_FP8, not another library mode (fp8_mixed_policy below; the modules apply it at construction)
 PREC_NAMES["fp8_mixed"] = PREC_FP8
@@ -45,7 +45,6 @@ def fp8_mixed_policy(depth: int, normed: bool):
     if normed:      # BETR
         return [PROMOTE_QKV | PROMOTE_PROJ] * depth, PROMOTE_ADAPTER_FC1 | PROMOTE_ADAPTER_FC2 | PROMOTE_BBOX_PROJ
     return [PROMOTE_PROJ] * depth, 0
-_X3_FAMILY = (PREC_BF16X3, PREC_BF16X3_ATTN_X3)
 ACT_NONE, ACT_GELU = 0, 1
 # per-Linear promotion: F16C8 family -> split-f16, e4m3 -> bf16 (include/boxdreamer_hip.h: BD_PROMOTE_*)
 PROMOTE_QKV, PROMOTE_PROJ, PROMOTE_FC1, PROMOTE_FC2, PROMOTE_ATTN = 1, 2, 4, 8, 16
@@ -238,30 +237,46 @@ def prec_id(prec) -> int:
         raise ValueError(f"unknown precision {prec!r}; choose from {sorted(PREC_NAMES)}") from None
 
 
+class Traits(NamedTuple):
+    """What a precision id says about an operand tensor (include/boxdreamer_hip.h; boxdreamer_amd/operand.py turns it into bytes)."""
+    cls: int                    # operand class: the value the unit operators and the weight packer take
+    planes: int
+    dtype: torch.dtype          # storage element type of every plane
+    plane_bytes: tuple          # bytes per element of each plane
+    k_multiple: int             # K padding granularity of GEMM operands: one 128-byte tile row per slab
+
+
+_CLASSES = {PREC_BF16: (1, torch.bfloat16, (2,), 64), PREC_F16: (1, torch.float16, (2,), 64),
+            PREC_FP8: (1, torch.float8_e4m3fn, (1,), 128),                                           # OCP e4m3 (gfx950), not MI300's fnuz
+            PREC_BF16X3: (2, torch.bfloat16, (2, 2), 64), PREC_F16X3: (2, torch.float16, (2, 2), 64),   # (hi, lo) planes
+            PREC_F16C8: (2, torch.float16, (2, 1), 64)}        # plane 1: one raw e4m3 byte per element at the head of 16-bit storage
+_WHOLE_PATH = {PREC_BF16X3_ATTN_X3: PREC_BF16X3, PREC_F16X3_ATTN_X3: PREC_F16X3, PREC_F16C8_QK16: PREC_F16C8}
+# one row per operand class and per whole-path id that runs in one; the attention-only codes (3, 5, 9, 10, 16, 17) name no operand
+TRAITS = {pid: Traits(cls, *_CLASSES[cls]) for pid, cls in {**{c: c for c in _CLASSES}, **_WHOLE_PATH}.items()}
+
+
+def traits(prec) -> Traits:
+    try:
+        return TRAITS[prec_id(prec)]
+    except KeyError:
+        raise ValueError(f"precision id {prec!r} names no operand class (an attention-only code, or unknown)") from None
+
+
 def operand_prec(prec) -> int:
     """Operand class of a (possibly whole-path) precision id: the value the unit operators and the weight packer take."""
-    pid = prec_id(prec)
-    if pid == PREC_F16C8_QK16:
-        return PREC_F16C8
-    if pid in _F16X3_FAMILY:
-        return PREC_F16X3
-    return PREC_BF16X3 if pid in _X3_FAMILY else pid
+    return traits(prec).cls
 
 
 def op_dtype(prec) -> torch.dtype:
-    pid = prec_id(prec)
-    if pid == PREC_FP8:
-        return torch.float8_e4m3fn          # OCP e4m3 (gfx950), not MI300's fnuz
-    return torch.float16 if pid in (PREC_F16, PREC_F16C8, PREC_F16C8_QK16) + _F16X3_FAMILY else torch.bfloat16     # F16C8: plane 1 holds raw e4m3 bytes
+    return traits(prec).dtype
 
 
 def k_multiple(prec) -> int:
-    """K padding granularity of GEMM operands: one 128-byte tile row per slab."""
-    return 128 if prec_id(prec) == PREC_FP8 else 64
+    return traits(prec).k_multiple
 
 
 def planes(prec) -> int:
-    return 2 if prec_id(prec) in _X3_FAMILY + _F16X3_FAMILY or prec_id(prec) in (PREC_F16C8, PREC_F16C8_QK16) else 1
+    return traits(prec).planes
 
 
 AUTO_LANES_MIN_VIEWS = 24      # one batch runs as two sub-batch lanes from this many (sample, view) images on (profiles/r4_subbatch_lanes.md)

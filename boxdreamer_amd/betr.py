@@ -14,7 +14,7 @@ import warnings
 import torch
 from torch import nn
 
-from . import _lib, features, hip_ops, pack
+from . import _lib, features, hip_ops, operand, pack
 
 
 class _Norm(nn.Module):
@@ -54,6 +54,19 @@ class SelfAttentionBlock(nn.Module):
         self.attn = _Attention(hidden_size, num_heads)
         self.norm2 = _Norm(hidden_size)
         self.mlp = _Mlp(hidden_size, int(hidden_size * mlp_ratio), hidden_size)
+
+
+class _Views:
+    """Which of a forward's (B, T) view slots are views: all of them (counts None), or per sample the first counts[b] -- a ragged
+    batch, with its device tables (BETR.ragged_index): the packing index of the valid slots and the samples' view offsets."""
+
+    def __init__(self, decoder, B: int, T: int, counts, dev):
+        self.n_views, self.max_views = (B * T, T) if counts is None else (sum(counts), max(counts))
+        self.index, self.view_start = decoder.ragged_index(counts, T, dev) if counts is not None else (None, None)
+
+    def pack(self, x):
+        """(B, T, ...) -> the views sample by sample: n_views leading rows (a uniform batch's slots already are that, in place)."""
+        return x.contiguous() if self.index is None else x.flatten(0, 1).index_select(0, self.index)
 
 
 class BETR(nn.Module):
@@ -211,11 +224,12 @@ class BETR(nn.Module):
         assert H == W == self.img_size, f"H and W should be equal to img_size {self.img_size}, got {H}x{W}"
         if pretrain_rgb_feat is None:
             raise NotImplementedError("the MI355X path requires pretrained RGB features (use_pretrained=True)")
+        counts = None
         if view_counts is not None:
             counts = _lib.view_counts_list(view_counts, B)
             _lib.check_view_counts(counts, T)
-            if any(c != T for c in counts):
-                return self._forward_ragged(pose_feat, rgbs, masks, pretrain_rgb_feat, counts)
+            if all(c == T for c in counts):      # IS the uniform batch
+                counts = None
         _lib.require_gpu()
         lib = _lib.load()
         only = isinstance(pretrain_rgb_feat, features.OperandOnly)       # an operand copy with no fp32 tensor behind it (a reference bank)
@@ -223,7 +237,7 @@ class BETR(nn.Module):
         prec = self.hip_precision
         pid = _lib.prec_id(prec)
         w = self._weights(dev, prec).struct
-        if w.latency_mode != int(self.hip_latency):
+        if counts is None and w.latency_mode != int(self.hip_latency):      # (the ragged entry point has no latency forms)
             self._check_not_frozen("switching hip_latency (the workspace layout changes)")
             w.latency_mode = int(self.hip_latency)
         P, D = w.grid * w.grid, w.dim
@@ -232,99 +246,56 @@ class BETR(nn.Module):
         if tuple(pose_feat.shape) != (B, T, self.box_dim, H, W):
             raise ValueError(f"pose_feat must be (B, T, {self.box_dim}, H, W) = {(B, T, self.box_dim, H, W)}, got "
                              f"{tuple(pose_feat.shape)}")
-        if pretrain_rgb_feat.numel() != B * T * P * D or pretrain_rgb_feat.shape[-1] != D:
-            raise ValueError(f"pretrain_rgb_feat must be (B, T, {P}, {D}), got {tuple(pretrain_rgb_feat.shape)}")
+        views = _Views(self, B, T, counts, dev)
+        n_views, shape = views.n_views, tuple(pretrain_rgb_feat.shape)
+        # `packed`: the features are the n_views views in order (a uniform batch's always are); else padded (B, T_max, P, D) of a ragged one
+        packed = counts is None or shape == (n_views, P, D)
+        if counts is None and (pretrain_rgb_feat.numel() != B * T * P * D or shape[-1] != D):
+            raise ValueError(f"pretrain_rgb_feat must be (B, T, {P}, {D}), got {shape}")
+        if not packed and shape != (B, T, P, D):
+            raise ValueError(f"pretrain_rgb_feat must be packed ({n_views}, {P}, {D}) or padded ({B}, {T}, {P}, {D}), got {shape}")
         if self.validate_inputs and not torch.cuda.is_current_stream_capturing():
             # the reference writes the query token through `pose_feat[masks] = ...` (betr.py:286-290), which fails unless
             # every sample marks exactly one view; argmax below would silently pick view 0 for an empty row
-            bad = (masks.sum(dim=1) != 1).any()
+            bad = masks.sum(dim=1) != 1
+            if counts is not None:       # ... and among the sample's own views (a padded slot is never a view)
+                valid = torch.arange(T, device=dev)[None, :] < (views.view_start[1:] - views.view_start[:-1])[:, None]
+                bad = bad | (masks & ~valid).any(dim=1)
+            bad = bad.any()
             if self.validate_inputs == "deferred":
                 self.mask_error = bad                  # stays on the device; the caller raises (no sync here)
             elif bool(bad):
-                raise ValueError("masks must mark exactly one query view per sample")
+                raise ValueError("masks must mark exactly one query view per sample" +
+                                 (", among the sample's view_counts views" if counts is not None else ""))
         query_idx = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
-        np_ = _lib.planes(prec)
         fcls = self.feats_class(prec)
-        if only:              # nothing to re-cast from: a copy that does not fit is an error
-            feats16 = pretrain_rgb_feat.checked(fcls, np_ * B * T * P * D, dev)
-        else:
-            feats16 = features.operand_of(pretrain_rgb_feat, fcls)
-        if feats16 is not None and (feats16.numel() != np_ * B * T * P * D or feats16.device != dev):
-            feats16 = None
+        if only and not packed:
+            raise ValueError(f"operand-only features of a ragged batch must be packed ({n_views}, {P}, {D}), got {shape}")
+        # (padded features of a ragged batch are never taken as they are: their copy holds the padded slots too)
+        feats16 = features.resolve(pretrain_rgb_feat, fcls, _lib.planes(fcls) * n_views * P * D, dev) if packed else None
         if feats16 is None:   # features without an operand copy (computed elsewhere, copied, sliced): explicit re-cast
             self.recast_count += 1
             if self.recast_count == 1:
                 warnings.warn("BETR: pretrain_rgb_feat carries no operand-dtype copy from the HIP encoder; re-casting it "
                               "(slow path, see boxdreamer_amd/features.py)", stacklevel=2)
-            feats16 = hip_ops.to_operand(pretrain_rgb_feat.reshape(B * T * P, D).float(), fcls)
-        pose_feat = pose_feat.contiguous()
-        lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, prec)
-        ws = self._workspace(max(lib.bd_decoder_workspace_bytes(w, B, T, pid),
-                                 lib.bd_decoder_workspace_bytes_lanes(w, B, T, pid, lanes)), dev)
-        logits = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
-        heat = torch.empty_like(logits)
-        _lib.check(lib.bd_decoder_forward_lanes(w, _lib.ptr(pose_feat), _lib.dtype_id(pose_feat), _lib.ptr(feats16),
-                                                B * T * P * D if np_ == 2 else 0, _lib.ptr(query_idx), B, T, H,
-                                                _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, lanes,
-                                                _lib.stream()), "bd_decoder_forward_lanes")
-        self.last_logits = logits
-        return heat
-
-    def _forward_ragged(self, pose_feat, rgbs, masks, pretrain_rgb_feat, counts):
-        """forward() for per-sample view counts that are not all T_max (validated host ints)."""
-        B, T, _, H, W = rgbs.shape
-        _lib.require_gpu()
-        lib = _lib.load()
-        only = isinstance(pretrain_rgb_feat, features.OperandOnly)
-        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat.operand if only else pretrain_rgb_feat)
-        prec = self.hip_precision
-        pid = _lib.prec_id(prec)
-        w = self._weights(dev, prec).struct
-        P, D = w.grid * w.grid, w.dim
-        n_views, max_views = sum(counts), max(counts)
-        if masks.dtype != torch.bool or masks.shape != (B, T):
-            raise ValueError("masks must be a (B, T) bool tensor")
-        if tuple(pose_feat.shape) != (B, T, self.box_dim, H, W):
-            raise ValueError(f"pose_feat must be (B, T, {self.box_dim}, H, W) = {(B, T, self.box_dim, H, W)}, got "
-                             f"{tuple(pose_feat.shape)}")
-        index, view_start = self.ragged_index(counts, T, dev)
-        packed_feats = pretrain_rgb_feat.dim() == 3 and tuple(pretrain_rgb_feat.shape) == (n_views, P, D)
-        if not packed_feats and tuple(pretrain_rgb_feat.shape) != (B, T, P, D):
-            raise ValueError(f"pretrain_rgb_feat must be packed ({n_views}, {P}, {D}) or padded ({B}, {T}, {P}, {D}), got "
-                             f"{tuple(pretrain_rgb_feat.shape)}")
-        if self.validate_inputs and not torch.cuda.is_current_stream_capturing():
-            # exactly one query view per sample, and among the sample's own views (a padded slot is never a view)
-            valid = torch.arange(T, device=dev)[None, :] < (view_start[1:] - view_start[:-1])[:, None]
-            bad = ((masks.sum(dim=1) != 1) | (masks & ~valid).any(dim=1)).any()
-            if self.validate_inputs == "deferred":
-                self.mask_error = bad
-            elif bool(bad):
-                raise ValueError("masks must mark exactly one query view per sample, among the sample's view_counts views")
-        query_view = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
-        np_ = _lib.planes(prec)
-        fcls = self.feats_class(prec)
-        if only:
-            if not packed_feats:
-                raise ValueError(f"operand-only features of a ragged batch must be packed ({n_views}, {P}, {D}), got {tuple(pretrain_rgb_feat.shape)}")
-            feats16 = pretrain_rgb_feat.checked(fcls, np_ * n_views * P * D, dev)
-        else:
-            feats16 = features.operand_of(pretrain_rgb_feat, fcls) if packed_feats else None
-        if feats16 is not None and (feats16.numel() != np_ * n_views * P * D or feats16.device != dev):
-            feats16 = None
-        if feats16 is None:
-            self.recast_count += 1
-            if self.recast_count == 1:
-                warnings.warn("BETR: pretrain_rgb_feat carries no operand-dtype copy from the HIP encoder; re-casting it "
-                              "(slow path, see boxdreamer_amd/features.py)", stacklevel=3)
-            f32 = pretrain_rgb_feat if packed_feats else pretrain_rgb_feat.reshape(B * T, P, D).index_select(0, index)
+            f32 = pretrain_rgb_feat if packed else views.pack(pretrain_rgb_feat)
             feats16 = hip_ops.to_operand(f32.reshape(n_views * P, D).float(), fcls)
-        pose_packed = pose_feat.reshape(B * T, self.box_dim, H, W).index_select(0, index)       # the valid views only: [n_views, 8, H, W]
-        ws = self._workspace(lib.bd_decoder_workspace_bytes_ragged(w, n_views, B, pid), dev)
+        pose = views.pack(pose_feat)                       # the valid views only: [n_views, 8, H, W]
+        plane = operand.plane_offset(feats16, fcls)
         logits = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
         heat = torch.empty_like(logits)
-        _lib.check(lib.bd_decoder_forward_ragged(w, _lib.ptr(pose_packed), _lib.dtype_id(pose_packed), _lib.ptr(feats16),
-                                                 n_views * P * D if np_ == 2 else 0, _lib.ptr(view_start), _lib.ptr(query_view), B,
-                                                 n_views, max_views, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid,
-                                                 _lib.stream()), "bd_decoder_forward_ragged")
+        if counts is None:
+            lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, prec)
+            ws = self._workspace(max(lib.bd_decoder_workspace_bytes(w, B, T, pid),
+                                     lib.bd_decoder_workspace_bytes_lanes(w, B, T, pid, lanes)), dev)
+            _lib.check(lib.bd_decoder_forward_lanes(w, _lib.ptr(pose), _lib.dtype_id(pose), _lib.ptr(feats16), plane, _lib.ptr(query_idx),
+                                                    B, T, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, lanes,
+                                                    _lib.stream()), "bd_decoder_forward_lanes")
+        else:
+            ws = self._workspace(lib.bd_decoder_workspace_bytes_ragged(w, n_views, B, pid), dev)
+            _lib.check(lib.bd_decoder_forward_ragged(w, _lib.ptr(pose), _lib.dtype_id(pose), _lib.ptr(feats16), plane,
+                                                     _lib.ptr(views.view_start), _lib.ptr(query_idx), B, n_views, views.max_views, H,
+                                                     _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, _lib.stream()),
+                       "bd_decoder_forward_ragged")
         self.last_logits = logits
         return heat

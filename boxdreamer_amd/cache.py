@@ -33,31 +33,10 @@ import warnings
 
 import torch
 
-from . import _lib, features
+from . import _lib, features, hip_ops, operand
 
 _WARNED_STALE = False
 _WARNED_STALE_BANK = False
-
-
-def _new_operand(pid: int, n_views: int, P: int, C: int, dtype, dev) -> torch.Tensor:
-    pid = _lib.operand_prec(pid)        # a whole-path id (f16c8_qk16, ...) carries the byte layout of its operand class
-    rows = n_views * P
-    return torch.zeros((2, rows, C) if _lib.planes(pid) == 2 else (rows, C), dtype=dtype, device=dev)
-
-
-def _plane_views(t16: torch.Tensor, pid: int, n_views: int, P: int, C: int):
-    """Per-view row views [n_views, P, C] of every plane of an operand tensor, in the plane's OWN element type.
-    Split-bf16: two elementwise 16-bit planes.  F16C8 (include/boxdreamer_hip.h): plane 0 is f16, plane 1 is one e4m3 BYTE per
-    element -- rows of C bytes packed into the first rows*C bytes of the plane's storage (the rest is unused) -- so it must be
-    moved as uint8 rows, never as 16-bit rows."""
-    pid = _lib.operand_prec(pid)
-    rows = n_views * P
-    if _lib.planes(pid) == 1:
-        return [t16.reshape(n_views, P, C)]
-    if pid == _lib.PREC_F16C8:
-        lo8 = t16[1].view(torch.uint8).reshape(-1)[: rows * C].reshape(n_views, P, C)
-        return [t16[0].reshape(n_views, P, C), lo8]
-    return [t16[0].reshape(n_views, P, C), t16[1].reshape(n_views, P, C)]
 
 
 def _init_last_stale():
@@ -82,11 +61,11 @@ def take_views(feats: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     if tag is None:
         return out32
     f16, pid = tag
-    out16 = _new_operand(pid, B * Tn, P, C, f16.dtype, dev)
-    for dst, src in zip(_plane_views(out16, pid, B * Tn, P, C), _plane_views(f16, pid, B * T, P, C)):
-        g = src[flat]
+    out16 = operand.empty(pid, B * Tn * P, C, dev, zero=True)
+    for dst, src in zip(operand.row_planes(out16, pid, B * Tn * P), operand.row_planes(f16, pid, B * T * P)):
+        g = src.reshape(B * T, P, C)[flat]
         g[~valid] = 0
-        dst.copy_(g)
+        dst.copy_(g.reshape(-1, C))
     return features.attach(out32, out16, pid, features.stamp_of(feats))
 
 
@@ -98,44 +77,21 @@ class RefFeatureCache:
         """(B, R, 3, H, W) -> (B, R, P, C) fp32 features tagged with their operand-dtype copy."""
         return self.encoder.predict(images)
 
-    @staticmethod
-    def _feats16_view(feats: torch.Tensor):
-        tag = features.tag_of(feats)
-        if tag is None:
-            raise ValueError("features were not produced by the HIP encoder (no operand-dtype copy attached)")
-        return tag
-
     def place(self, ref_feats: torch.Tensor, query_idx: torch.Tensor, T: int):
         """Scatter R = T-1 cached reference features into a (B, T, P, C) layout leaving the query slot empty.
         Returns (features, valid_mask (B, T) bool)."""
         B, R, P, C = ref_feats.shape
         assert R == T - 1
-        f16, pid = self._feats16_view(ref_feats)
+        f16, pid = features.require_tag(ref_feats)
         dev = ref_feats.device
         valid = torch.ones((B, T), dtype=torch.bool, device=dev)
         valid[torch.arange(B, device=dev), query_idx.to(dev).long()] = False
         full32 = torch.zeros((B, T, P, C), dtype=torch.float32, device=dev)
         full32[valid] = ref_feats.reshape(B * R, P, C)
-        full16 = _new_operand(pid, B * T, P, C, f16.dtype, dev)
-        for dst, src in zip(_plane_views(full16, pid, B * T, P, C), _plane_views(f16, pid, B * R, P, C)):
-            dst.reshape(B, T, P, C)[valid] = src
+        full16 = operand.empty(pid, B * T * P, C, dev, zero=True)
+        for dst, src in zip(operand.row_planes(full16, pid, B * T * P), operand.row_planes(f16, pid, B * R * P)):
+            dst.reshape(B, T, P, C)[valid] = src.reshape(B * R, P, C)
         return features.attach(full32, full16, pid, features.stamp_of(ref_feats)), valid
-
-
-def _copy_views(dst16, dst_v0: int, src16, n: int, pid: int, P: int, C: int) -> None:
-    """Views [0, n) of operand tensor src16 -> views [dst_v0, dst_v0 + n) of dst16 (each of any capacity): contiguous
-    slice copies per plane; F16C8's lo8 plane moves as bytes at the head of plane-1 storage (_plane_views)."""
-    if n <= 0:
-        return
-    e = P * C
-    if _lib.planes(pid) == 1:
-        dst16.reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16.reshape(-1)[:n * e])
-        return
-    dst16[0].reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[0].reshape(-1)[:n * e])
-    if pid == _lib.PREC_F16C8:
-        dst16[1].view(torch.uint8).reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[1].view(torch.uint8).reshape(-1)[:n * e])
-    else:
-        dst16[1].reshape(-1)[dst_v0 * e:(dst_v0 + n) * e].copy_(src16[1].reshape(-1)[:n * e])
 
 
 class RefFeatureBank:
@@ -186,10 +142,7 @@ class RefFeatureBank:
     @property
     def bytes_per_view(self) -> int:
         """Bytes of one row in the bank (all planes)."""
-        if self._pid is None:
-            return 0
-        one = self._P * self._C * (1 if self._pid == _lib.PREC_FP8 else 2)
-        return one + (self._P * self._C * (1 if self._pid == _lib.PREC_F16C8 else 2) if _lib.planes(self._pid) == 2 else 0)
+        return 0 if self._pid is None else self._P * operand.row_bytes(self._pid, self._C)
 
     def _now(self):
         return (self.encoder.model.state_stamp(self.encoder.prec), int(self.encoder.model.feats_class(self.encoder.prec)))
@@ -201,16 +154,16 @@ class RefFeatureBank:
         if self._t16 is not None and need <= self._cap and self._t16.device == dev:
             return
         cap = max(need, 2 * self._cap, 8)
-        new = _new_operand(self._pid, cap, self._P, self._C, _lib.op_dtype(self._pid), dev)
+        new = operand.empty(self._pid, cap * self._P, self._C, dev, zero=True)
         if self._t16 is not None:       # growth re-lays the planes out: plane 1 starts at the new capacity
-            _copy_views(new, 0, self._t16.to(dev), self._n, self._pid, self._P, self._C)
+            operand.copy_rows(new, 0, self._t16.to(dev), self._n * self._P, self._pid)
         self._t16, self._cap = new, cap
 
     def _append(self, images: torch.Tensor) -> None:
         if images.device != self.encoder.get_device():
             self.encoder.to_device(images.device)
         feats = self.encoder.predict(images)                   # (N, P, C) fp32, tagged; only the operand copy is kept
-        f16, pid = RefFeatureCache._feats16_view(feats)
+        f16, pid = features.require_tag(feats)
         n, P, C = feats.shape
         if self._n == 0:
             self._pid, self._P, self._C, self._stamp = _lib.operand_prec(pid), int(P), int(C), self._now()
@@ -218,7 +171,7 @@ class RefFeatureBank:
         elif (_lib.operand_prec(pid), int(P), int(C)) != (self._pid, self._P, self._C):
             raise ValueError(f"the bank holds ({self._P}, {self._C}) views of operand class {self._pid}; got ({P}, {C}) of class {pid}")
         self._reserve(self._n + n, images.device)
-        _copy_views(self._t16, self._n, f16, n, self._pid, P, C)
+        operand.copy_rows(self._t16, self._n * P, f16, n * P, self._pid)
         if self.keep_images:
             self._images.append((self._n, images))
         self._n += n
@@ -259,6 +212,22 @@ class RefFeatureBank:
         self.refresh_count += 1
         return True
 
+    def real_crops(self, images: torch.Tensor, rows, n: int) -> torch.Tensor:
+        """images[:n] of a banked batch ((B, T, 3, S, S); `rows`: its validated host table) with every banked slot -- whose image is never
+        read and may hold anything -- replaced by the crop the bank kept: what the precision self-check measures on.  Only those
+        samples are sliced out and copied."""
+        images = images[:n]
+        banked = [(b, t, rows[b][t]) for b in range(images.shape[0]) for t in range(images.shape[1]) if rows[b][t] >= 0]
+        if banked:
+            if not self.keep_images:
+                raise RuntimeError("the precision self-check needs the reference crops of the samples it measures on, and the reference "
+                                   "bank kept none (keep_images=False): run model.calibrate(data) on a batch with real images (or one "
+                                   "plain forward) first")
+            images = images.clone()
+            for b, t, r in banked:
+                images[b, t] = self.image_of(r).to(images.dtype)
+        return images
+
     def image_of(self, row: int) -> torch.Tensor:
         """The kept crop of a row (3, S, S) (keep_images=True)."""
         for r0, img in self._images:
@@ -284,7 +253,6 @@ class RefFeatureBank:
         """One bd_gather_view_rows launch: the operand of len(src) views from bank rows and `fresh` (the encoder's tagged output for
         the views encoded in this forward, or None) -> features.OperandOnly of the logical shape (*lead, P, C); `lead` is (B, T) for a
         uniform batch, (n_views,) for a packed ragged one."""
-        from . import hip_ops
         n_views = int(src.numel())
         lead = tuple(int(x) for x in lead)
         if len(lead) not in (1, 2) or (lead[0] * lead[1] if len(lead) == 2 else lead[0]) != n_views:
@@ -292,7 +260,7 @@ class RefFeatureBank:
         n_fresh, f16 = 0, None
         pid, P, C = self._pid, self._P, self._C
         if fresh is not None:
-            f16, fpid = RefFeatureCache._feats16_view(fresh)
+            f16, fpid = features.require_tag(fresh)
             n_fresh = int(fresh.shape[0])
             if pid is None:                                    # an empty bank: every view is fresh
                 pid, P, C = _lib.operand_prec(fpid), int(fresh.shape[1]), int(fresh.shape[2])
@@ -300,10 +268,9 @@ class RefFeatureBank:
                 raise ValueError("the freshly encoded views and the bank's rows differ in operand class, shape or encoder state")
         if pid is None:
             raise ValueError("nothing to gather: the bank is empty and no view was encoded")
-        dev = src.device
-        out16 = torch.empty((2, n_views * P, C) if _lib.planes(pid) == 2 else (n_views * P, C), dtype=_lib.op_dtype(pid), device=dev)
-        hip_ops.gather_view_rows(self._t16 if self._n else None, self._n, f16, n_fresh, src, out16, n_views, P, C, prec=pid,
-                                 bank_plane=self._cap * P * C if _lib.planes(pid) == 2 else 0)
+        out16 = operand.empty(pid, n_views * P, C, src.device)
+        # (the plane offsets default to each tensor's own: the bank's is its capacity, operand.plane_offset)
+        hip_ops.gather_view_rows(self._t16 if self._n else None, self._n, f16, n_fresh, src, out16, n_views, P, C, prec=pid)
         stamp = self._stamp[0] if self._stamp is not None else features.stamp_of(fresh)
         return features.OperandOnly(lead + (P, C), out16, pid, stamp)
 
@@ -313,7 +280,7 @@ def merge_cached_features(encoder, images: torch.Tensor, cached: torch.Tensor, v
     says whether THIS call fell back to encoding every view (the facade records it per forward in data["hip_precision"]["cache_stale"]:
     the warning fires once per process, the fallback every time)."""
     B, T = images.shape[:2]
-    f16, pid = RefFeatureCache._feats16_view(cached)
+    f16, pid = features.require_tag(cached)
     stamp, now = features.stamp_of(cached), encoder.model.state_stamp(encoder.prec)
     # (a missing stamp -- an older producer, or a tag lost through .to() / .clone() -- counts as stale whenever the encoder's state carries
     # a promotion: such features cannot be told apart from ones computed under another state)
@@ -330,7 +297,7 @@ def merge_cached_features(encoder, images: torch.Tensor, cached: torch.Tensor, v
         return encoder.predict(images)
     miss = ~valid
     new = encoder.predict(images[miss])                       # (n_miss, P, C), tagged
-    n16, npid = RefFeatureCache._feats16_view(new)
+    n16, npid = features.require_tag(new)
     if npid != pid:
         raise ValueError("cached features were produced in a different precision mode")
     P, C = cached.shape[2:]
@@ -338,8 +305,8 @@ def merge_cached_features(encoder, images: torch.Tensor, cached: torch.Tensor, v
     out32[miss] = new
     out16 = f16.clone()
     n_miss = int(new.shape[0])
-    for dst, src in zip(_plane_views(out16, pid, B * T, P, C), _plane_views(n16, pid, n_miss, P, C)):
-        dst.reshape(B, T, P, C)[miss] = src
+    for dst, src in zip(operand.row_planes(out16, pid, B * T * P), operand.row_planes(n16, pid, n_miss * P)):
+        dst.reshape(B, T, P, C)[miss] = src.reshape(n_miss, P, C)
     return features.attach(out32, out16, pid, now)
 
 

@@ -15,7 +15,7 @@ import weakref
 
 import torch
 
-from . import _lib, features, pack, synth
+from . import _lib, features, operand, pack, synth
 
 _ARCH = {  # model_type -> (dim, depth, heads)
     "dinov2_vits14_reg": (384, 12, 6),
@@ -135,11 +135,9 @@ class DinoV2Encoder:
                                  lib.bd_encoder_workspace_bytes_lanes(w, n, _lib.prec_id(prec), lanes)), images.device)
         feats32 = torch.empty((n, P, D), dtype=torch.float32, device=images.device)
         fcls = self.feats_class(prec)
-        np_ = _lib.planes(fcls)
-        feats16 = torch.empty((np_, n * P, D) if np_ == 2 else (n * P, D), dtype=_lib.op_dtype(fcls),
-                              device=images.device)
+        feats16 = operand.empty(fcls, n * P, D, images.device)
         _lib.check(lib.bd_encoder_forward_lanes(w, _lib.ptr(images), _lib.dtype_id(images), n, size, _lib.ptr(feats32),
-                                                _lib.ptr(feats16), n * P * D if np_ == 2 else 0, _lib.ptr(ws),
+                                                _lib.ptr(feats16), operand.plane_offset(feats16, fcls), _lib.ptr(ws),
                                                 ws.numel(), _lib.prec_id(prec), lanes, _lib.stream()), "bd_encoder_forward_lanes")
         return feats32, feats16
 

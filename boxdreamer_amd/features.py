@@ -51,6 +51,14 @@ def tag_of(feats32: torch.Tensor):
     return tag[0], tag[1]
 
 
+def require_tag(feats32: torch.Tensor):
+    """tag_of for callers that cannot go on without the operand copy (the feature cache and the reference bank)."""
+    tag = tag_of(feats32)
+    if tag is None:
+        raise ValueError("features were not produced by the HIP encoder (no operand-dtype copy attached)")
+    return tag
+
+
 def stamp_of(feats32: torch.Tensor):
     """The producer stamp `attach` recorded (None: none recorded / no tag)."""
     tag = getattr(feats32, _ATTR, None)
@@ -98,3 +106,13 @@ class OperandOnly:
             raise ValueError(f"operand-only features hold {self.operand.numel()} elements on {self.operand.device}, the decoder needs "
                              f"{int(numel)} on {device}")
         return self.operand
+
+
+def resolve(feat, cls: int, n_elems: int, device):
+    """The operand tensor the decoder reads for `feat` -- class `cls`, `n_elems` elements over all planes, on `device` -- or None when
+    the caller has to re-cast: an OperandOnly that does not fit raises (nothing to re-cast from), a tagged fp32 tensor gives its copy
+    when that fits, anything else (computed elsewhere, copied, sliced) gives None."""
+    if isinstance(feat, OperandOnly):
+        return feat.checked(cls, n_elems, device)
+    f16 = operand_of(feat, cls)
+    return f16 if f16 is not None and f16.numel() == n_elems and f16.device == device else None

@@ -10,18 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, operand
 from ._lib import check, planes, prec_id, ptr, stream
-
-
-def _alloc16(rows: int, cols: int, prec, device) -> torch.Tensor:
-    shape = (2, rows, cols) if planes(prec) == 2 else (rows, cols)
-    return torch.empty(shape, dtype=_lib.op_dtype(prec), device=device)
-
-
-def _plane(t: torch.Tensor, prec) -> int:
-    return t[0].numel() if planes(prec) == 2 else 0
-
 
 E4M3_MAX = 448.0
 
@@ -134,17 +124,17 @@ def gemm(a16, w16, bias=None, *, prec="bf16", act=_lib.ACT_NONE, resid=None, add
         elif mode in _OUT_SPLIT:
             out = torch.empty((2, rows_out, N), dtype=_OUT_SPLIT[mode], device=A2.device)
         else:
-            out = _alloc16(rows_out, N, prec, A2.device)
+            out = operand.empty(prec, rows_out, N, A2.device)
     g = _lib.GemmArgs()
-    g.A, g.lda, g.a_plane = ptr(a16), A2.stride(0), _plane(a16, prec)
-    g.W, g.ldw, g.w_plane = ptr(w16), W2.stride(0), _plane(w16, prec)
+    g.A, g.lda, g.a_plane = ptr(a16), A2.stride(0), operand.plane_offset(a16, prec)
+    g.W, g.ldw, g.w_plane = ptr(w16), W2.stride(0), operand.plane_offset(w16, prec)
     g.bias = ptr(bias)
     g.wscale = ptr(wscale)
     g.resid, g.ldr = ptr(resid), (resid.stride(0) if resid is not None else 0)
     g.addtab, g.tab_rows = ptr(addtab), (addtab.shape[0] if addtab is not None else 0)
     o2 = out[0] if (mode in _OUT_SPLIT or (not mode and np_ == 2)) else out
     g.out, g.ldo, g.out_f32 = ptr(out), o2.stride(0), mode
-    g.out_plane = out[0].numel() if mode in _OUT_SPLIT else (0 if mode else _plane(out, prec))
+    g.out_plane = out[0].numel() if mode in _OUT_SPLIT else (0 if mode else operand.plane_offset(out, prec))
     g.w_qexp = int(w_qexp)
     if rms is not None:                      # (wq, wk, eps[, parts]): fused q/k RMSNorm of a QKV Linear ([q | k | v] columns, or [q | k])
         g.rms_wq, g.rms_wk, g.rms_eps = ptr(rms[0]), ptr(rms[1]), float(rms[2])
@@ -175,10 +165,10 @@ def layernorm(x, gamma, beta, eps, *, prec="bf16", want16=True, want32=False, ro
     lib = _lib.load()
     M = rows if rows is not None else x.shape[0]
     cols = x.shape[1]
-    o16 = _alloc16(M, cols, prec, x.device) if want16 else None
+    o16 = operand.empty(prec, M, cols, x.device) if want16 else None
     o32 = torch.empty((M, cols), dtype=torch.float32, device=x.device) if want32 else None
     check(lib.bd_layernorm(ptr(x), x.stride(0), ptr(gamma), ptr(beta), eps, ptr(o16),
-                           _plane(o16, prec) if o16 is not None else 0, ptr(o32), cols, M, cols, *rpg,
+                           operand.plane_offset(o16, prec) if o16 is not None else 0, ptr(o32), cols, M, cols, *rpg,
                            prec_id(prec), stream()), "bd_layernorm")
     return o16, o32
 
@@ -187,7 +177,7 @@ def qk_rmsnorm_(qkv16, wq, wk, eps, heads, head_dim, *, prec="bf16"):
     lib = _lib.load()
     q2 = qkv16[0] if planes(prec) == 2 else qkv16
     rows = q2.numel() // (3 * heads * head_dim)
-    check(lib.bd_qk_rmsnorm(ptr(qkv16), _plane(qkv16, prec), ptr(wq), ptr(wk), eps, rows, heads, head_dim,
+    check(lib.bd_qk_rmsnorm(ptr(qkv16), operand.plane_offset(qkv16, prec), ptr(wq), ptr(wk), eps, rows, heads, head_dim,
                             prec_id(prec), stream()), "bd_qk_rmsnorm")
     return qkv16
 
@@ -195,8 +185,8 @@ def qk_rmsnorm_(qkv16, wq, wk, eps, heads, head_dim, *, prec="bf16"):
 def attention(qkv16, batch, seq, heads, head_dim, scale, *, prec="bf16"):
     lib = _lib.load()
     dev = qkv16.device
-    out = _alloc16(batch * seq, heads * head_dim, prec, dev)
-    check(lib.bd_attention(ptr(qkv16), _plane(qkv16, prec), ptr(out), _plane(out, prec), batch, seq, heads,
+    out = operand.empty(prec, batch * seq, heads * head_dim, dev)
+    check(lib.bd_attention(ptr(qkv16), operand.plane_offset(qkv16, prec), ptr(out), operand.plane_offset(out, prec), batch, seq, heads,
                            head_dim, scale, prec_id(prec), stream()), "bd_attention")
     return out
 
@@ -205,8 +195,8 @@ def attention_prefix(qkv16, batch, seq, heads, head_dim, scale, n_prefix, *, pre
     """bd_attention_prefix: patch queries in the tiled kernel, the n_prefix leading queries in a side launch (or skipped)."""
     lib = _lib.load()
     if out is None:
-        out = _alloc16(batch * seq, heads * head_dim, prec, qkv16.device)
-    check(lib.bd_attention_prefix(ptr(qkv16), _plane(qkv16, prec), ptr(out), _plane(out, prec), batch, seq, heads, head_dim, scale,
+        out = operand.empty(prec, batch * seq, heads * head_dim, qkv16.device)
+    check(lib.bd_attention_prefix(ptr(qkv16), operand.plane_offset(qkv16, prec), ptr(out), operand.plane_offset(out, prec), batch, seq, heads, head_dim, scale,
                                   n_prefix, int(bool(prefix_queries)), prec_id(prec), stream()), "bd_attention_prefix")
     return out
 
@@ -214,8 +204,8 @@ def attention_prefix(qkv16, batch, seq, heads, head_dim, scale, n_prefix, *, pre
 def attention_q(qkv16, batch, seq, heads, head_dim, scale, q_view, q_len, *, prec="bf16"):
     """Attention with queries restricted to rows [q_view[b]*q_len, +q_len) of each sequence; compact output."""
     lib = _lib.load()
-    out = _alloc16(batch * q_len, heads * head_dim, prec, qkv16.device)
-    check(lib.bd_attention_q(ptr(qkv16), _plane(qkv16, prec), ptr(out), _plane(out, prec), batch, seq, heads, head_dim,
+    out = operand.empty(prec, batch * q_len, heads * head_dim, qkv16.device)
+    check(lib.bd_attention_q(ptr(qkv16), operand.plane_offset(qkv16, prec), ptr(out), operand.plane_offset(out, prec), batch, seq, heads, head_dim,
                              scale, ptr(q_view), q_len, prec_id(prec), stream()), "bd_attention_q")
     return out
 
@@ -231,8 +221,8 @@ def attention_varlen(qkv16, view_counts, tokens_per_view, heads, head_dim, scale
     if view_start is None:
         view_start = torch.tensor(_lib.view_starts(counts), dtype=torch.int32).to(dev)
     B, n_views = len(counts), sum(counts)
-    out = _alloc16((B if q_view is not None else n_views) * tokens_per_view, heads * head_dim, prec, dev)
-    check(lib.bd_attention_varlen(ptr(qkv16), _plane(qkv16, prec), ptr(out), _plane(out, prec), ptr(view_start), B, n_views,
+    out = operand.empty(prec, (B if q_view is not None else n_views) * tokens_per_view, heads * head_dim, dev)
+    check(lib.bd_attention_varlen(ptr(qkv16), operand.plane_offset(qkv16, prec), ptr(out), operand.plane_offset(out, prec), ptr(view_start), B, n_views,
                                   max(counts) if counts else 0, tokens_per_view, heads, head_dim, scale, ptr(q_view), prec_id(prec),
                                   stream()), "bd_attention_varlen")
     return out
@@ -245,7 +235,7 @@ def gather_view_rows(bank16, bank_views, fresh16, n_fresh, src, out16, n_views, 
     default to each tensor's own plane size) -- either source may be None when its view count is 0.  src: device int32 [n_views].
     bank32 / fresh32 / out32: optional fp32 copies moved the same way.  Returns out16."""
     lib = _lib.load()
-    pl = [(_plane(t, prec) if t is not None else 0) if given is None else int(given)
+    pl = [(operand.plane_offset(t, prec) if t is not None else 0) if given is None else int(given)
           for t, given in ((bank16, bank_plane), (fresh16, fresh_plane), (out16, out_plane))]
     check(lib.bd_gather_view_rows(ptr(bank16), pl[0], int(bank_views), ptr(fresh16), pl[1], int(n_fresh), ptr(src), ptr(out16), pl[2],
                                   int(n_views), int(P), int(dim), prec_id(prec), ptr(bank32), ptr(fresh32), ptr(out32), stream()),
@@ -258,8 +248,8 @@ def im2col_images(images, patch=14, kpad=640, *, prec="bf16"):
     images = images.contiguous()
     n, size = images.shape[0], images.shape[-1]
     grid = size // patch
-    out = _alloc16(n * grid * grid, kpad, prec, images.device)
-    check(lib.bd_im2col_images(ptr(images), _lib.dtype_id(images), ptr(out), _plane(out, prec), n, size, patch,
+    out = operand.empty(prec, n * grid * grid, kpad, images.device)
+    check(lib.bd_im2col_images(ptr(images), _lib.dtype_id(images), ptr(out), operand.plane_offset(out, prec), n, size, patch,
                                kpad, prec_id(prec), stream()), "bd_im2col_images")
     return out
 
@@ -269,8 +259,8 @@ def patchify_heatmaps(heat, patch=14, kpad=1600, *, prec="bf16"):
     heat = heat.contiguous()
     n, c, size = heat.shape[0], heat.shape[1], heat.shape[-1]
     grid = size // patch
-    out = _alloc16(n * grid * grid, kpad, prec, heat.device)
-    check(lib.bd_patchify_heatmaps(ptr(heat), _lib.dtype_id(heat), ptr(out), _plane(out, prec), n, c, size, patch,
+    out = operand.empty(prec, n * grid * grid, kpad, heat.device)
+    check(lib.bd_patchify_heatmaps(ptr(heat), _lib.dtype_id(heat), ptr(out), operand.plane_offset(out, prec), n, c, size, patch,
                                    kpad, prec_id(prec), stream()), "bd_patchify_heatmaps")
     return out
 

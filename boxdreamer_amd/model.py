@@ -7,10 +7,10 @@ f4) is wired through boxdreamer_amd/dense.py.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
-
-import os
 
 from .betr import BETR
 from . import _lib, calibrate, features, pnp
@@ -116,21 +116,11 @@ class BoxDreamer(nn.Module):
             images, bbox_feat, mask = images[:1, :counts[0]], bbox_feat[:1, :counts[0]], mask[:1, :counts[0]]
         bank = data.get("ref_bank")
         if bank is not None and data.get("ref_rows") is not None:
-            # a banked batch: the images of banked slots are never read (they may hold anything).  Every sample the self-check measures
-            # on takes its references from the crops the bank kept; only those samples are sliced out and copied
+            # a banked batch: every sample the self-check measures on takes its references from the crops the bank kept
             rows = _lib.ref_rows_table(data["ref_rows"], B, T)
             _lib.check_ref_rows(rows, counts if counts is not None else [T] * B, len(bank))
             n = min(calibrate.MAX_SAMPLES, images.shape[0])
-            images, bbox_feat, mask = images[:n], bbox_feat[:n], mask[:n]
-            banked = [(b, t, rows[b][t]) for b in range(n) for t in range(images.shape[1]) if rows[b][t] >= 0]
-            if banked:
-                if not bank.keep_images:
-                    raise RuntimeError("the precision self-check needs the reference crops of the samples it measures on, and the reference "
-                                       "bank kept none (keep_images=False): run model.calibrate(data) on a batch with real images (or one "
-                                       "plain forward) first")
-                images = images.clone()
-                for b, t, r in banked:
-                    images[b, t] = bank.image_of(r).to(images.dtype)
+            images, bbox_feat, mask = bank.real_crops(images, rows, n), bbox_feat[:n], mask[:n]
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)
         if self.hip_promotion_file and self.hip_calibrate and calibrate.load_state(self.hip_promotion_file, self.rgb_encoder, self.decoder):
@@ -256,29 +246,7 @@ class BoxDreamer(nn.Module):
         # ragged batch: per-sample view counts (host ints).  None: the uniform batch, today's path bit for bit
         counts = self._view_counts(data, B, T)
         dense = self.dense_cfg is not None and _get(self.dense_cfg, "enable", False)
-        if counts is not None:
-            if dense:
-                raise NotImplementedError("view_counts together with dense_cfg.enable (ragged dense-reference mode) is not implemented")
-            if "cached_rgb_feat" in data:
-                raise NotImplementedError("view_counts together with cached_rgb_feat (ragged feature cache) is not implemented")
-            if not isinstance(self.decoder, BETR):
-                raise NotImplementedError("view_counts needs the BETR decoder")
-        # reference bank (boxdreamer_amd/cache.py: RefFeatureBank): references named by bank row, only the -1 slots are encoded.  The
-        # table is a host value, validated here, before any launch
-        bank, bank_rows = data.get("ref_bank"), None
-        if bank is not None or data.get("ref_rows") is not None:
-            if dense:
-                raise NotImplementedError("ref_bank together with dense_cfg.enable (banked dense-reference mode) is not implemented")
-            if "cached_rgb_feat" in data:
-                raise NotImplementedError("ref_bank together with cached_rgb_feat: give the references one way or the other")
-            if not isinstance(self.decoder, BETR):
-                raise NotImplementedError("ref_bank needs the BETR decoder")
-            if bank is None or data.get("ref_rows") is None:
-                raise KeyError("the batch dict needs both 'ref_bank' (a cache.RefFeatureBank) and 'ref_rows' (its (B, T_max) host table)")
-            if bank.encoder is not self.rgb_encoder:
-                raise ValueError("ref_bank was built on another encoder than this model's rgb_encoder")
-            bank_rows = _lib.ref_rows_table(data["ref_rows"], B, T)
-            _lib.check_ref_rows(bank_rows, counts if counts is not None else [T] * B, len(bank))
+        bank, bank_rows = self._check_mode(data, B, T, counts, dense)
 
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)                            # BoxDreamerModel.py:279-282
@@ -298,41 +266,21 @@ class BoxDreamer(nn.Module):
             if images.is_cuda and not torch.cuda.is_current_stream_capturing():
                 self._sync_ranks_once()
             data["hip_precision"] = self._precision_record()
-            # sub-batch lanes this batch runs as (bit-identical for every value; `hip_lanes` in the decoder / encoder cfg, default "auto")
-            data["hip_precision"]["sub_batch_lanes"] = _lib.resolve_lanes(self.decoder.hip_lanes, B * T, B, self.decoder.hip_precision)
-            if counts is not None:      # the ragged decoder call has no laned form yet: ONE lane (the encoder lanes its packed images as ever)
-                data["hip_precision"]["sub_batch_lanes"] = 1
-                data["hip_precision"]["ragged_views"] = sum(counts)
         ar = self._arange(B, dev)
         decoded = None
-        if bank is not None:
-            # (hip_graph: a banked batch takes this eager branch, like a ragged one)
-            rgb_feature = self._banked_features(data, bank, bank_rows, images, counts)
-            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
-            if counts is not None:
-                self._defer_query_check(query_idx, qi, self.decoder.ragged_index(counts, T, dev)[1])
-        elif counts is not None:
-            # (hip_graph: a ragged batch takes this eager branch -- capture of ragged shapes is a follow-up)
-            # the encoder and the decoder see the sum(counts) real views only, packed sample by sample; padded slots are never read
-            index, view_start = self.decoder.ragged_index(counts, T, dev)
-            rgb_feature = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, index))
-            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
-            self._defer_query_check(query_idx, qi, view_start)
-        elif (self.hip_graph and not dense and "cached_rgb_feat" not in data and not self.training and images.is_cuda
-                and isinstance(self.decoder, BETR) and not torch.cuda.is_current_stream_capturing()):
+        if (self.hip_graph and bank is None and counts is None and not dense and "cached_rgb_feat" not in data and not self.training
+                and images.is_cuda and isinstance(self.decoder, BETR) and not torch.cuda.is_current_stream_capturing()):
+            # (a banked or a ragged batch takes the eager branch -- capture of ragged shapes is a follow-up)
+            data["hip_precision"].update(self._lanes_record(B, T, None))
             heat, kp_px, kn, _ = self._graphed(images, pose_feat, qi, sig)
             # (the replay's outputs are static buffers the next replay overwrites: what the caller keeps is copied out of them below --
             # pred_bbox's query slot is written straight from the static heat map, the corners get their own tensors)
             query_ret, decoded = heat, (kn.clone(), kp_px.clone())
             self.decoder.mask_error = None          # query_idx indexes one view per sample by construction
         else:
-            if "cached_rgb_feat" in data:       # "next" row f1: references encoded once per object (boxdreamer_amd/cache.py)
-                rgb_feature = merge_cached_features(self.rgb_encoder, images, data["cached_rgb_feat"],
-                                                    data["cached_rgb_mask"])
-                if "hip_precision" in data:       # the stale-cache fallback re-encodes every view on EVERY forward: say so every time
-                    data["hip_precision"]["cache_stale"] = bool(merge_cached_features.last_stale)
-            else:
-                rgb_feature = self.rgb_encoder.predict(images)
+            rgb_feature, record = self._eager_features(data, images, counts, bank, bank_rows)
+            if sig is not None:
+                data["hip_precision"].update(record)
             if dense:     # BoxDreamerModel.py:291-327
                 data, pose_feat, images, camera_mask, rgb_feature, _ = process_dense_input(
                     data, pose_feat, images, camera_mask, rgb_feature, None, self.dense_cfg)
@@ -351,8 +299,11 @@ class BoxDreamer(nn.Module):
                 B, T = images.shape[:2]
                 ar, qi = torch.arange(B, device=dev), data["query_idx"].to(dev).long()
                 camera_mask = torch.arange(T, device=dev)[None, :] == qi[:, None]
-            else:
+            elif counts is None:
                 query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None)
+            else:       # (the keyword goes to a BETR only: _check_mode)
+                query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None, view_counts=counts)
+                self._defer_query_check(query_idx, qi, counts, T)
 
         # BoxDreamerModel.py:341-344 (`pred_bbox[camera_mask] = query_ret`): the same write through (sample, view) indices -- a boolean-mask
         # assignment runs nonzero() and waits for the device.  In eval the copy (the largest device operation of the dict contract: bbox_feat's
@@ -372,31 +323,73 @@ class BoxDreamer(nn.Module):
         self.host_syncs_per_forward = syncs
         return data
 
-    def _defer_query_check(self, query_idx, qi, view_start) -> None:
+    def _defer_query_check(self, query_idx, qi, counts, T: int) -> None:
         """Ragged batch, query_idx on the device (a host one was checked before any launch): "is it one of the sample's views" travels
         with the decoder's deferred mask verdict (no sync here)."""
         if isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda:
             return
+        view_start = self.decoder.ragged_index(counts, T, qi.device)[1]
         beyond = (qi >= (view_start[1:] - view_start[:-1]).long()).any()
         err = self.decoder.mask_error
         self.decoder.mask_error = beyond if err is None else (err | beyond)
 
-    def _banked_features(self, data, bank, rows, images, counts):
-        """The decoder's feature operand of a banked batch (uniform: counts None): a stale bank is refreshed first (this runs after the
-        calibration branch, so a bank filled before the first forward just works), the -1 slots among the valid views are encoded,
-        packed, in ONE predict call, and ONE bd_gather_view_rows launch assembles the operand of the B * T (uniform) or
-        sum(view_counts) (ragged) views from bank rows and those fresh views.  Images in banked or padded slots are never read; no
-        fp32 features exist on this path (features.OperandOnly)."""
+    def _check_mode(self, data, B: int, T: int, counts, dense: bool):
+        """One batch names its references ONE way: refuse, before any launch, the combinations that are not implemented.  Returns
+        (cache.RefFeatureBank, its validated host table of bank rows; -1: encode this slot), or (None, None) without a bank."""
+        bank, rows = data.get("ref_bank"), data.get("ref_rows")
+        ragged, banked, cached, betr = counts is not None, bank is not None or rows is not None, "cached_rgb_feat" in data, isinstance(self.decoder, BETR)
+        if ragged and dense:
+            raise NotImplementedError("view_counts together with dense_cfg.enable (ragged dense-reference mode) is not implemented")
+        if ragged and cached:
+            raise NotImplementedError("view_counts together with cached_rgb_feat (ragged feature cache) is not implemented")
+        if ragged and not betr:
+            raise NotImplementedError("view_counts needs the BETR decoder")
+        if banked and dense:
+            raise NotImplementedError("ref_bank together with dense_cfg.enable (banked dense-reference mode) is not implemented")
+        if banked and cached:
+            raise NotImplementedError("ref_bank together with cached_rgb_feat: give the references one way or the other")
+        if banked and not betr:
+            raise NotImplementedError("ref_bank needs the BETR decoder")
+        if banked and (bank is None or rows is None):
+            raise KeyError("the batch dict needs both 'ref_bank' (a cache.RefFeatureBank) and 'ref_rows' (its (B, T_max) host table)")
+        if banked and bank.encoder is not self.rgb_encoder:
+            raise ValueError("ref_bank was built on another encoder than this model's rgb_encoder")
+        if not banked:
+            return None, None
+        rows = _lib.ref_rows_table(rows, B, T)
+        _lib.check_ref_rows(rows, counts if ragged else [T] * B, len(bank))
+        return bank, rows
+
+    def _lanes_record(self, B: int, T: int, counts) -> dict:
+        """Sub-batch lanes this batch runs as (bit-identical for every value; `hip_lanes` in the decoder / encoder cfg, default "auto").  The
+        ragged decoder call has no laned form yet: ONE lane (the encoder lanes its packed images as ever)."""
+        if counts is not None:
+            return {"sub_batch_lanes": 1, "ragged_views": sum(counts)}
+        return {"sub_batch_lanes": _lib.resolve_lanes(self.decoder.hip_lanes, B * T, B, self.decoder.hip_precision)}
+
+    def _eager_features(self, data, images, counts, bank, bank_rows):
+        """(the decoder's features, this forward's entries of data["hip_precision"]) from the ONE source the batch names.  Bank: a stale bank
+        is refreshed first (after the calibration branch, so a bank filled before the first forward just works), the -1 slots among the
+        valid views are encoded, packed, in ONE predict call and ONE bd_gather_view_rows launch assembles the operand; images in banked or
+        padded slots are never read and no fp32 features exist (features.OperandOnly).  view_counts: the encoder sees the real views only,
+        packed.  cached_rgb_feat: only the views the cache lacks are encoded (a stale cache re-encodes all, and says so every time)."""
         B, T = images.shape[:2]
-        refreshed = bank.ensure_fresh()
-        cts = counts if counts is not None else [T] * B
-        n_views = sum(cts)
-        src, encode, n_fresh = bank.tables(rows, cts, T, images.device)
-        fresh = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, encode)) if n_fresh else None
-        feats = bank.gather(src, fresh, (B, T) if counts is None else (n_views,))
-        if "hip_precision" in data:
-            data["hip_precision"]["ref_bank"] = {"banked_views": n_views - n_fresh, "encoded_views": n_fresh, "refreshed": bool(refreshed)}
-        return feats
+        record = self._lanes_record(B, T, counts) if isinstance(self.decoder, BETR) else {}
+        if bank is not None:
+            refreshed = bank.ensure_fresh()
+            cts = counts if counts is not None else [T] * B
+            src, encode, n_fresh = bank.tables(bank_rows, cts, T, images.device)
+            fresh = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, encode)) if n_fresh else None
+            record["ref_bank"] = {"banked_views": sum(cts) - n_fresh, "encoded_views": n_fresh, "refreshed": bool(refreshed)}
+            return bank.gather(src, fresh, (B, T) if counts is None else (sum(cts),)), record
+        if counts is not None:
+            index = self.decoder.ragged_index(counts, T, images.device)[0]
+            return self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, index)), record
+        if "cached_rgb_feat" in data:
+            feats = merge_cached_features(self.rgb_encoder, images, data["cached_rgb_feat"], data["cached_rgb_mask"])
+            record["cache_stale"] = bool(merge_cached_features.last_stale)
+            return feats, record
+        return self.rgb_encoder.predict(images), record
 
     def _graphed(self, images, pose_feat, qi, sig=None):
         """Replay (capturing first, per batch shape) encoder -> decoder -> corner decode as one HIP graph; returns the graph's STATIC

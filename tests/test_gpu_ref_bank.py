@@ -8,7 +8,7 @@ import warnings
 import pytest
 import torch
 
-from boxdreamer_amd import _lib, cache as cache_mod, hip_ops
+from boxdreamer_amd import _lib, cache as cache_mod, hip_ops, operand
 from boxdreamer_amd.cache import RefFeatureBank
 from test_gpu_path import LOGIT_TOL, _build
 from test_gpu_ragged import DEPTH, OUT_KEYS, _decode, _facade, _oracle, _ragged_batch, _to_dev
@@ -97,9 +97,9 @@ def test_gather_view_rows_moves_whole_views_byte_for_byte(hip, name, shape):
     bad = [0, BANK_VIEWS, -1, -(N_FRESH + 1), 2]
     got = run(bad, True)
     assert all((x == FILL).all() for v in (1, 3) for x in got.view(v))
-    if name == "f16c8":       # the layout is cache._plane_views': f16 plane 0, one-byte lo8 rows packed at the head of plane-1 storage
+    if name == "f16c8":       # the layout is operand.row_planes': f16 plane 0, one-byte lo8 rows packed at the head of plane-1 storage
         def planes(r):
-            return cache_mod._plane_views(r.t.view(torch.float16).reshape(2, r.cap * P, dim), pid, r.cap, P, dim)
+            return [p.reshape(r.cap, P, dim) for p in operand.row_planes(r.t.view(torch.float16).reshape(2, r.cap * P, dim), pid, r.cap * P)]
         for v, s in enumerate(SRC):
             from_, sv = (bank, s) if s >= 0 else (fresh, -(s + 1))
             for o, x in zip(planes(out), planes(from_)):

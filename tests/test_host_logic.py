@@ -316,7 +316,8 @@ def test_reference_feature_cache_moves_every_operand_plane_in_its_own_layout(pre
     elementwise 16-bit plane; `place` / the merge must move it as byte rows.  Host-only check (torch ops): the operand copy of the
     placed layout decodes, view by view, to the values of the views that were placed."""
     from boxdreamer_amd import features, hip_ops
-    from boxdreamer_amd.cache import RefFeatureCache, _plane_views
+    from boxdreamer_amd.cache import RefFeatureCache
+    from boxdreamer_amd.operand import row_planes
     B, R, P, C = 2, 3, 4, 64
     T = R + 1
     pid = _lib.operand_prec(prec)
@@ -336,7 +337,7 @@ def test_reference_feature_cache_moves_every_operand_plane_in_its_own_layout(pre
     assert torch.equal(full[valid], x.reshape(B * R, P, C))
     if pid == _lib.PREC_F16C8:                       # nothing of the poisoned tail travelled
         assert int(got16[1].view(torch.uint8).reshape(-1)[B * T * P * C:].max()) == 0
-    assert len(_plane_views(got16, pid, B * T, P, C)) == _lib.planes(pid)
+    assert len(row_planes(got16, pid, B * T * P)) == _lib.planes(pid)
 
 
 def test_cached_features_of_another_promotion_state_are_not_merged():
