@@ -126,6 +126,7 @@ EXPORTS = [
     "bd_decoder_forward_lanes", "bd_pose_metrics_workspace_bytes", "bd_pose_metrics", "bd_crop_resize_frames",
     "bd_attention_varlen", "bd_query_substitute_varlen", "bd_gather_query_rows_f32_varlen", "bd_gather_query_tokens_varlen",
     "bd_decoder_workspace_bytes_ragged", "bd_decoder_forward_ragged", "bd_gather_view_rows",
+    "bd_match_view_sums", "bd_match_select_rows",
 ]
 
 _lib = None
@@ -200,6 +201,8 @@ def load() -> C.CDLL:
     lib.bd_decoder_workspace_bytes_ragged.restype = sz
     lib.bd_decoder_forward_ragged.argtypes = [C.POINTER(BetrWeights), vp, i, vp, i64, vp, vp, i, i, i, i, vp, vp, vp, sz, i, vp]
     lib.bd_gather_view_rows.argtypes = [vp, i64, i, vp, i64, i, vp, vp, i64, i, i, i, i, vp, vp, vp, vp]
+    lib.bd_match_view_sums.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, vp]
+    lib.bd_match_select_rows.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:
@@ -451,6 +454,35 @@ def gather_sources(rows, counts, t_max: int):
                 encode.append(b * t_max + t)
                 src.append(-len(encode))
     return src, encode
+
+
+# ---- Dense-reference mode over the bank (bd_match_select_rows): the same `ref_rows` table names a sample's whole database of banked
+# references and its one query slot.  Host values again: the kernel's (rows, n_refs) tables are derived without reading anything back.
+def dense_bank_tables(rows, counts, topk: int, query_idx=None):
+    """(rows [B][N_max], n_refs [B], N_max, query [B]) of one bd_match_select_rows launch from a validated `ref_rows` table
+    (check_ref_rows): sample b's reference slots are its valid slots except its query slot, in slot order, padded with -1 up to
+    N_max = max(counts) - 1.  The banked dense mode encodes the query only: exactly one valid slot per sample is -1, that slot is the
+    query (and equals the host `query_idx[b]` when one is given); a sample needs at least `topk` references and at most 1024.
+    ValueError otherwise."""
+    out, n_refs, query = [], [], []
+    n_max = max(counts) - 1
+    for b, (row, c) in enumerate(zip(rows, counts)):
+        fresh = [t for t in range(c) if row[t] < 0]
+        if len(fresh) != 1:
+            raise ValueError(f"ref_rows[{b}] has {len(fresh)} entries -1 among its {c} views (slots {fresh}): the banked dense-reference mode "
+                             "encodes the query only, exactly one slot is -1 and every other is a row of the bank")
+        q = fresh[0]
+        if query_idx is not None and int(query_idx[b]) != q:
+            raise ValueError(f"ref_rows[{b}][{q}] = -1 but query_idx[{b}] = {int(query_idx[b])}: the slot to encode must be the query view")
+        if c - 1 < topk:
+            raise ValueError(f"sample {b} has {c - 1} references, fewer than dense_cfg.filter_topk = {topk}")
+        if c - 1 > 1024:
+            raise ValueError(f"sample {b} has {c - 1} references, more than the 1024 one bd_match_select_rows launch ranks")
+        refs = [row[t] for t in range(c) if t != q]
+        n_refs.append(len(refs))
+        query.append(q)
+        out.append(refs + [-1] * (n_max - len(refs)))
+    return out, n_refs, n_max, query
 
 
 def attention_work_list(counts, heads: int, tokens_per_view: int, q_block: int, query_only: bool = False):

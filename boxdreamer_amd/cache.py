@@ -26,6 +26,9 @@ decoder's feature operand from those rows and the freshly encoded query views:
     rows = bank.add(ref_images)                               # (R, 3, S, S) or (B, R, 3, S, S) -> CPU int64 row ids, stable for good
     data["ref_bank"], data["ref_rows"] = bank, table          # (B, T_max) host ints: >= 0 bank row, -1 "encode this slot of data['images']"
     model(data)
+With `match_threshold=0.05` the bank also keeps each row's dense-reference match summary (bd_match_view_sums), and a model with
+`dense_cfg.enable` selects its `filter_topk` references among a sample's whole banked database (bd_match_select_rows): the table then
+holds one -1 per sample, at the query.
 """
 from __future__ import annotations
 
@@ -102,13 +105,21 @@ class RefFeatureBank:
     (encoder.state_stamp: operand class + per-Linear promotion) plus the operand class the rows are in.  When the encoder's state has
     moved on since (the load-time calibration ran, calibrate.set_state was applied), the bank is stale: with keep_images=True it
     re-encodes every row from the crops it kept (in the dtype they came in) -- once, with one warning -- and with keep_images=False it
-    raises RuntimeError; rows of two promotion states are never mixed."""
+    raises RuntimeError; rows of two promotion states are never mixed.
 
-    def __init__(self, encoder, keep_images: bool = True):
+    `match_threshold` (None: none kept, today's bank byte for byte; 0.05 is dense.match_views' luminance threshold, the reference's):
+    every row also gets its dense-reference match summary -- the foreground feature sum (C floats) and the foreground patch count of
+    bd_match_view_sums, computed from the encoder's fp32 output and the crop before that copy is dropped: 3 KB per view against the
+    operand row's ~590 KB.  With them a dense-reference forward (dense_cfg.enable + ref_bank) scores and selects among a sample's
+    whole database without its features or crops (select)."""
+
+    def __init__(self, encoder, keep_images: bool = True, match_threshold: float | None = None):
         self.encoder = encoder                                 # a DinoV2Wrapper
         self.keep_images = bool(keep_images)
+        self.match_threshold = None if match_threshold is None else float(match_threshold)
         self.refresh_count = 0
         self._tables = {}       # (ref_rows of the valid slots, counts, T_max, device) -> device tables of one gather launch
+        self._dense_tables = {}  # (reference rows, n_refs, N_max, device) -> device tables of one select launch
         self.clear()
 
     def clear(self) -> None:
@@ -116,6 +127,7 @@ class RefFeatureBank:
         self._t16, self._cap, self._n = None, 0, 0
         self._pid, self._P, self._C, self._stamp = None, 0, 0, None
         self._images = []       # [(first row, crops (N, 3, S, S))] when keep_images
+        self._msums, self._mcounts = None, None                # [cap, C] / [cap] fp32 match summaries (match_threshold)
 
     def __len__(self) -> int:
         return self._n
@@ -128,6 +140,11 @@ class RefFeatureBank:
     @property
     def operand_class(self):
         return self._pid
+
+    @property
+    def has_match_summaries(self) -> bool:
+        """Whether every row carries its dense-reference match summary (the bank was built with a match_threshold)."""
+        return self.match_threshold is not None
 
     @property
     def tokens_per_view(self) -> int:
@@ -157,6 +174,13 @@ class RefFeatureBank:
         new = operand.empty(self._pid, cap * self._P, self._C, dev, zero=True)
         if self._t16 is not None:       # growth re-lays the planes out: plane 1 starts at the new capacity
             operand.copy_rows(new, 0, self._t16.to(dev), self._n * self._P, self._pid)
+        if self.has_match_summaries:
+            msums = torch.zeros((cap, self._C), dtype=torch.float32, device=dev)
+            mcounts = torch.zeros((cap,), dtype=torch.float32, device=dev)
+            if self._msums is not None:
+                msums[:self._n].copy_(self._msums[:self._n])
+                mcounts[:self._n].copy_(self._mcounts[:self._n])
+            self._msums, self._mcounts = msums, mcounts
         self._t16, self._cap = new, cap
 
     def _append(self, images: torch.Tensor) -> None:
@@ -165,13 +189,18 @@ class RefFeatureBank:
         feats = self.encoder.predict(images)                   # (N, P, C) fp32, tagged; only the operand copy is kept
         f16, pid = features.require_tag(feats)
         n, P, C = feats.shape
+        if self.has_match_summaries and P > 1024:
+            raise ValueError(f"match summaries cover views of at most 1024 patch tokens (bd_match_view_sums); these have {P}")
         if self._n == 0:
             self._pid, self._P, self._C, self._stamp = _lib.operand_prec(pid), int(P), int(C), self._now()
-            self._t16, self._cap = None, 0
+            self._t16, self._cap, self._msums, self._mcounts = None, 0, None, None
         elif (_lib.operand_prec(pid), int(P), int(C)) != (self._pid, self._P, self._C):
             raise ValueError(f"the bank holds ({self._P}, {self._C}) views of operand class {self._pid}; got ({P}, {C}) of class {pid}")
         self._reserve(self._n + n, images.device)
         operand.copy_rows(self._t16, self._n * P, f16, n * P, self._pid)
+        if self.has_match_summaries:       # straight into the rows' place, while the fp32 features still exist
+            hip_ops.match_view_sums(feats, images.contiguous(), self.match_threshold, self._msums[self._n:self._n + n],
+                                    self._mcounts[self._n:self._n + n])
         if self.keep_images:
             self._images.append((self._n, images))
         self._n += n
@@ -204,10 +233,10 @@ class RefFeatureBank:
                           "from the kept crops, once.", stacklevel=3)
         # the new store is built on the side and swapped in when every row is there: a re-encode that fails part-way (out of memory,
         # say) leaves the rows and the kept crops as they were, and the failure is what the caller sees
-        new = RefFeatureBank(self.encoder, keep_images=True)
+        new = RefFeatureBank(self.encoder, keep_images=True, match_threshold=self.match_threshold)
         for _, img in self._images:                            # in row order: ids are unchanged
             new._append(img)
-        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images"):
+        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images", "_msums", "_mcounts"):
             setattr(self, k, getattr(new, k))
         self.refresh_count += 1
         return True
@@ -248,6 +277,32 @@ class RefFeatureBank:
                    torch.tensor(encode, dtype=torch.int64).to(dev) if encode else None, len(encode))
             self._tables[key] = hit
         return hit
+
+    def dense_tables(self, ref_rows, n_refs, n_max: int, query, t_max: int, dev):
+        """(rows int32 [B, N_max], n_refs int32 [B], query int64 [B], flat slot of every query int64 [B]) on `dev` for the host tables of
+        _lib.dense_bank_tables: uploaded once per distinct table and kept, like tables()."""
+        key = (tuple(tuple(r[:n]) for r, n in zip(ref_rows, n_refs)), tuple(query), int(n_max), int(t_max), str(dev))
+        hit = self._dense_tables.get(key)
+        if hit is None:
+            if len(self._dense_tables) >= 64:
+                self._dense_tables.clear()
+            B = len(n_refs)
+            hit = (torch.tensor(ref_rows, dtype=torch.int32).reshape(B, n_max).to(dev), torch.tensor(n_refs, dtype=torch.int32).to(dev),
+                   torch.tensor(query, dtype=torch.int64).to(dev), torch.tensor([b * t_max + q for b, q in enumerate(query)], dtype=torch.int64).to(dev))
+            self._dense_tables[key] = hit
+        return hit
+
+    def select(self, fresh: torch.Tensor, images: torch.Tensor, rows: torch.Tensor, n_refs: torch.Tensor, topk: int):
+        """Dense-reference selection among banked rows: `fresh` (B, P, C) the encoder's output for the B query crops `images`
+        (B, 3, S, S); rows / n_refs: dense_tables().  Two launches (bd_match_view_sums on the queries, bd_match_select_rows) ->
+        (scores fp32 (B, N_max), sel int32 (B, topk) selected slots in ascending order, src int32 (B (topk + 1),): gather()'s source
+        table of the (B, topk + 1) batch, the query last)."""
+        if not self.has_match_summaries:
+            raise ValueError("the reference bank keeps no match summaries: build it with RefFeatureBank(encoder, match_threshold=0.05)")
+        if self._n == 0:
+            raise ValueError("nothing to select from: the bank is empty")
+        q_sums, q_counts = hip_ops.match_view_sums(fresh, images.contiguous(), self.match_threshold)
+        return hip_ops.match_select_rows(self._msums, self._mcounts, self._n, q_sums, q_counts, rows, n_refs, self._P, topk)
 
     def gather(self, src: torch.Tensor, fresh, lead) -> "features.OperandOnly":
         """One bd_gather_view_rows launch: the operand of len(src) views from bank rows and `fresh` (the encoder's tagged output for

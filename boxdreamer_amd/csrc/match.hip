@@ -69,6 +69,26 @@ __global__ __launch_bounds__(256) void match_sums_kernel(const float* __restrict
     if (tid == 0) counts[v] = (float)cnt;
 }
 
+// The score of one (query, reference) pair from the two views' summaries, by ONE wave; every kernel that scores a pair calls these two,
+// so a pair's score has the same bits whichever entry produced it (bd_dino_match_scores, bd_match_select_rows).
+__device__ __forceinline__ float pair_dot(const float* __restrict__ sq, const float* __restrict__ sr, int D, int lane) {
+    float dot = 0.f;
+    for (int d = lane; d < D; d += 64) dot = fmaf(sq[d], sr[d], dot);
+    return wave_sum(dot);
+}
+
+__device__ __forceinline__ float pair_score(float dot, float cq, float cr, int L) {
+    const float ll = (float)L * (float)L;
+    const float pairs = cq * cr;
+    // a view without foreground: the reference fills EVERY pair with -1e4, so non-finite features of the other view (NaN * 0
+    // in the dot product) do not reach the score
+    if (pairs == 0.f) dot = 0.f;
+    const float invalid = ll - pairs;
+    float m = (dot - 1e4f * invalid) / ll;
+    if (!(m == m) || fabsf(m) == INFINITY) m = 0.f;            // nan_to_num(0, 0, 0)
+    return m;
+}
+
 // one wave per (sample, reference): references are the views != query_view[b], in view order
 __global__ __launch_bounds__(64) void match_scores_kernel(const float* __restrict__ sums, const float* __restrict__ counts,
                                                            const int32_t* __restrict__ query_view, int T, int L, int D,
@@ -76,22 +96,8 @@ __global__ __launch_bounds__(64) void match_scores_kernel(const float* __restric
     const int b = blockIdx.x / (T - 1), n = blockIdx.x % (T - 1), lane = threadIdx.x;
     const int q = query_view[b];
     const int r = n < q ? n : n + 1;
-    const float* sq = sums + ((int64_t)b * T + q) * D;
-    const float* sr = sums + ((int64_t)b * T + r) * D;
-    float dot = 0.f;
-    for (int d = lane; d < D; d += 64) dot = fmaf(sq[d], sr[d], dot);
-    dot = wave_sum(dot);
-    if (lane == 0) {
-        const float ll = (float)L * (float)L;
-        const float pairs = counts[b * T + q] * counts[b * T + r];
-        // a view without foreground: the reference fills EVERY pair with -1e4, so non-finite features of the other view (NaN * 0
-        // in the dot product) do not reach the score
-        if (pairs == 0.f) dot = 0.f;
-        const float invalid = ll - pairs;
-        float m = (dot - 1e4f * invalid) / ll;
-        if (!(m == m) || fabsf(m) == INFINITY) m = 0.f;            // nan_to_num(0, 0, 0)
-        scores[b * (T - 1) + n] = m;
-    }
+    const float dot = pair_dot(sums + ((int64_t)b * T + q) * D, sums + ((int64_t)b * T + r) * D, D, lane);
+    if (lane == 0) scores[b * (T - 1) + n] = pair_score(dot, counts[b * T + q], counts[b * T + r], L);
 }
 
 // top-k mask per row (N <= 1024): k rounds of (largest value, then lowest index), one workgroup per row.  A round picks the best
@@ -130,6 +136,82 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
     }
 }
 
+constexpr int32_t NO_VIEW = 0x7fffffff;  // a `src` entry bd_gather_view_rows skips (outside every bank): its view keeps its bytes
+
+// Dense-reference mode over a bank of view summaries: score, select and compact in ONE launch, one workgroup (4 waves) per sample.
+// Sample b's references are the bank rows rows[b][0 .. n_refs[b]); its query is fresh view b (q_sums / q_counts).
+//   score    one wave per slot, match_scores_kernel's arithmetic (pair_dot, pair_score); a slot past n_refs[b] or a row outside
+//            [0, R) scores -inf, and `rows` is not read past n_refs[b]
+//   top-k    topk_mask_kernel's rounds over the slots [0, n_refs[b])
+//   compact  the picked slots in ascending order -> sel[b], their bank rows followed by -(b + 1) (fresh view b) -> src
+// Inconsistent device data cannot read or write out of bounds: n_refs[b] is clamped into [0, N_max]; when it is below k the
+// remaining entries of sel[b] are -1 and those of src NO_VIEW, as is the src entry of a picked slot whose row is outside the bank.
+__global__ __launch_bounds__(256) void match_select_rows_kernel(const float* __restrict__ bank_sums, const float* __restrict__ bank_counts,
+                                                                 int R, const float* __restrict__ q_sums, const float* __restrict__ q_counts,
+                                                                 const int32_t* __restrict__ rows, const int32_t* __restrict__ n_refs,
+                                                                 int N_max, int L, int D, int k, float* __restrict__ scores,
+                                                                 int32_t* __restrict__ sel, int32_t* __restrict__ src) {
+    __shared__ float val[MAXL];
+    __shared__ int pick[MAXL];
+    __shared__ float wv[4];
+    __shared__ int wi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int N = n_refs[b];
+    N = N < 0 ? 0 : (N > N_max ? N_max : N);
+    const int32_t* row = rows + (int64_t)b * N_max;
+    const float* sq = q_sums + (int64_t)b * D;
+    const float cq = q_counts[b];
+    for (int i = wid; i < N_max; i += 4) {
+        float m = -INFINITY;
+        const int r = i < N ? row[i] : -1;                  // (wave-uniform)
+        if (r >= 0 && r < R) m = pair_score(pair_dot(sq, bank_sums + (int64_t)r * D, D, lane), cq, bank_counts[r], L);
+        if (lane == 0) { val[i] = m; scores[(int64_t)b * N_max + i] = m; }
+    }
+    __syncthreads();
+    float pv = INFINITY;
+    int pi = -1, n_picked = 0;
+    for (int round = 0; round < k; ++round) {
+        float bv = -INFINITY; int bi = 0x7fffffff;
+        for (int i = tid; i < N; i += 256) {
+            const float v = val[i];
+            const bool after = v < pv || (v == pv && i > pi);
+            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
+            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (lane == 0) { wv[wid] = bv; wi[wid] = bi; }
+        __syncthreads();
+        bv = wv[0]; bi = wi[0];
+        for (int w = 1; w < 4; ++w) if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
+        if (bi >= N) break;                                 // (block-uniform) fewer than k slots: nothing is left to pick
+        if (tid == 0) pick[round] = bi;
+        n_picked = round + 1;
+        pv = bv; pi = bi;
+        __syncthreads();                    // wv / wi are rewritten in the next round
+    }
+    __syncthreads();
+    // the picks are distinct slots: a pick's place in ascending order is the number of smaller picks
+    int32_t* out_sel = sel + (int64_t)b * k;
+    int32_t* out_src = src + (int64_t)b * (k + 1);
+    for (int j = tid; j < k; j += 256) {
+        if (j < n_picked) {
+            const int p = pick[j];
+            int rank = 0;
+            for (int m = 0; m < n_picked; ++m) rank += pick[m] < p;
+            const int r = row[p];
+            out_sel[rank] = p;
+            out_src[rank] = r >= 0 && r < R ? r : NO_VIEW;
+        } else {
+            out_sel[j] = -1;
+            out_src[j] = NO_VIEW;
+        }
+    }
+    if (tid == 0) out_src[k] = -(b + 1);
+}
+
 }  // namespace
 
 extern "C" int bd_dino_match_scores(const float* feats, const void* images, int img_dtype, const int32_t* query_view, int B,
@@ -150,6 +232,29 @@ extern "C" int bd_topk_mask(const float* scores, int B, int N, int k, unsigned c
     if (!scores || !mask) return BD_ERR_NULL;
     if (B <= 0 || N <= 0 || N > MAXL || k <= 0 || k > N) return BD_ERR_SHAPE;
     hipLaunchKernelGGL(topk_mask_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, N, k, mask);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_match_view_sums(const float* feats, const void* images, int img_dtype, int V, int L, int D, int H, int W,
+                                  float lum_threshold, float* sums, float* counts, void* stream) {
+    if (!feats || !images || !sums || !counts) return BD_ERR_NULL;
+    if (V < 0 || L <= 0 || L > MAXL || D <= 0 || H <= 0 || W <= 0) return BD_ERR_SHAPE;
+    if (img_dtype != BD_DTYPE_F32 && img_dtype != BD_DTYPE_BF16 && img_dtype != BD_DTYPE_F16) return BD_ERR_DTYPE;
+    if (V == 0) return BD_OK;
+    hipLaunchKernelGGL(match_sums_kernel, dim3(V), dim3(256), 0, (hipStream_t)stream, feats, images, img_dtype, L, D, H, W,
+                       lum_threshold, sums, counts);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_match_select_rows(const float* bank_sums, const float* bank_counts, int R, const float* q_sums, const float* q_counts,
+                                    const int32_t* rows, const int32_t* n_refs, int B, int N_max, int L, int D, int k,
+                                    float* scores, int32_t* sel, int32_t* src, void* stream) {
+    if (!bank_sums || !bank_counts || !q_sums || !q_counts || !rows || !n_refs || !scores || !sel || !src) return BD_ERR_NULL;
+    if (B <= 0 || R < 0 || N_max <= 0 || N_max > MAXL || k <= 0 || k > N_max || L <= 0 || D <= 0) return BD_ERR_SHAPE;
+    hipLaunchKernelGGL(match_select_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, bank_sums, bank_counts, R, q_sums,
+                       q_counts, rows, n_refs, N_max, L, D, k, scores, sel, src);
     BD_CHECK_LAUNCH();
     return BD_OK;
 }

@@ -142,6 +142,24 @@ def filter_by_neighbor_mask(data, neighbor_mask, pose_feat, frames, camera_mask,
     return data, new_pose_feat, new_frames, new_camera_mask, new_rgb, new_masks
 
 
+def filter_by_view_index(data, idx, ar):
+    """filter_by_neighbor_mask's update of the batch dict for a selection that exists as view indices on the device (the banked dense
+    mode, model.py: bd_match_select_rows' slots): idx (B, k + 1) long, the selected references in their original order and the query
+    last; ar = arange(B) on the same device.  The same keys get the same views, through integer indexing: no boolean mask, no
+    nonzero(), nothing waits for the device.  Features are not re-packed here (the bank gathers them) and `original_images`, a host
+    list, is left to the caller.  Returns the new query_idx (B,) long, all k."""
+    B, T = idx.shape
+    rows = ar[:, None]
+    for key in ("bbox_feat", "images", "poses", "original_poses", "intrinsics", "non_ndc_intrinsics", "original_intrinsics", "scale",
+                "bbox_3d", "bbox_proj_crop"):
+        if key in data:
+            data[key] = data[key][rows, idx]
+    qi = torch.full((B,), T - 1, dtype=torch.long, device=idx.device)
+    data["query_idx"] = qi
+    data["camera_mask"] = torch.arange(T, device=idx.device)[None, :] == qi[:, None]
+    return qi
+
+
 def process_dense_input(data, pose_feat, frames, camera_mask, rgb_feature, image_masks, dense_cfg):
     if _get(dense_cfg, "filter") == "dino" and _get(dense_cfg, "filter_enable"):
         q = camera_mask.to(torch.int32).argmax(dim=1)

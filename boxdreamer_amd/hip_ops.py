@@ -243,6 +243,39 @@ def gather_view_rows(bank16, bank_views, fresh16, n_fresh, src, out16, n_views, 
     return out16
 
 
+def match_view_sums(feats, images, threshold, sums=None, counts=None):
+    """bd_match_view_sums: feats fp32 (V, L, D), images (V, 3, H, W) -> (sums fp32 (V, D), counts fp32 (V,)): each view's foreground
+    feature sum and patch count, what a pair's dense-reference score is made of (csrc/match.hip).  `sums` / `counts`: where to write
+    them (contiguous views of at least V rows), allocated when None."""
+    lib = _lib.load()
+    V, L, D = feats.shape
+    H, W = images.shape[-2:]
+    if feats.dtype != torch.float32 or not feats.is_contiguous() or not images.is_contiguous() or images.shape[0] != V:
+        raise ValueError("match_view_sums needs contiguous fp32 (V, L, D) features and contiguous (V, 3, H, W) images of the same V")
+    if sums is None:
+        sums = torch.empty((V, D), dtype=torch.float32, device=feats.device)
+        counts = torch.empty((V,), dtype=torch.float32, device=feats.device)
+    check(lib.bd_match_view_sums(ptr(feats), ptr(images), _lib.dtype_id(images), int(V), int(L), int(D), int(H), int(W), float(threshold),
+                                 ptr(sums), ptr(counts), stream()), "bd_match_view_sums")
+    return sums, counts
+
+
+def match_select_rows(bank_sums, bank_counts, n_bank, q_sums, q_counts, rows, n_refs, L, k):
+    """bd_match_select_rows: one launch -> (scores fp32 (B, N_max), sel int32 (B, k), src int32 (B * (k + 1),)).  rows: device int32
+    (B, N_max) bank row of every reference slot; n_refs: device int32 (B,); n_bank: rows of the bank that are in use."""
+    lib = _lib.load()
+    B, N_max = rows.shape
+    D = q_sums.shape[1]
+    dev = q_sums.device
+    scores = torch.empty((B, N_max), dtype=torch.float32, device=dev)
+    sel = torch.empty((B, int(k)), dtype=torch.int32, device=dev)
+    src = torch.empty((B * (int(k) + 1),), dtype=torch.int32, device=dev)
+    check(lib.bd_match_select_rows(ptr(bank_sums), ptr(bank_counts), int(n_bank), ptr(q_sums), ptr(q_counts), ptr(rows), ptr(n_refs),
+                                   int(B), int(N_max), int(L), int(D), int(k), ptr(scores), ptr(sel), ptr(src), stream()),
+          "bd_match_select_rows")
+    return scores, sel, src
+
+
 def im2col_images(images, patch=14, kpad=640, *, prec="bf16"):
     lib = _lib.load()
     images = images.contiguous()

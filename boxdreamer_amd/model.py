@@ -17,7 +17,7 @@ from . import _lib, calibrate, features, pnp
 from .box_utils import recover_bb8_corners_chw, solve_poses_device, solve_poses_host
 from .cache import merge_cached_features
 from .config import setup_camera_params, validate_model_config
-from .dense import process_dense_input, process_multi_round
+from .dense import filter_by_view_index, process_dense_input, process_multi_round
 from .encoder import DinoV2Wrapper
 
 
@@ -103,6 +103,7 @@ class BoxDreamer(nn.Module):
         self._pose_pin = None
         self._d2h_pin, self._d2h_done = None, None
         self._aranges = {}
+        self._dense_query_bad, self._slots_host = None, None
 
     def calibrate(self, data) -> dict:
         """Run the precision self-check / promotion on (the first samples of) a batch dict now (forward() does it once by itself)."""
@@ -247,6 +248,7 @@ class BoxDreamer(nn.Module):
         counts = self._view_counts(data, B, T)
         dense = self.dense_cfg is not None and _get(self.dense_cfg, "enable", False)
         bank, bank_rows = self._check_mode(data, B, T, counts, dense)
+        dense_plan = self._dense_bank_plan(bank, bank_rows, counts, query_idx, B, T) if dense and bank is not None else None
 
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)                            # BoxDreamerModel.py:279-282
@@ -277,6 +279,19 @@ class BoxDreamer(nn.Module):
             # pred_bbox's query slot is written straight from the static heat map, the corners get their own tensors)
             query_ret, decoded = heat, (kn.clone(), kp_px.clone())
             self.decoder.mask_error = None          # query_idx indexes one view per sample by construction
+        elif dense_plan is not None:
+            # dense-reference mode over the bank: the query is the one view encoded; the references are scored, selected and gathered
+            # from the bank's rows, and the decoder runs on the uniform (B, k + 1) batch
+            rgb_feature, record, idx = self._banked_dense_features(data, images, bank, dense_plan, query_idx, qi)
+            if sig is not None:
+                data["hip_precision"].update(record)
+            B, T = idx.shape
+            qi = filter_by_view_index(data, idx, ar)
+            images, pose_feat, camera_mask = data["images"], data["bbox_feat"], data["camera_mask"]
+            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None)
+            if self._dense_query_bad is not None:       # a device-side query_idx that is not the table's -1 slot: reported with the D2H
+                err = self.decoder.mask_error
+                self.decoder.mask_error = self._dense_query_bad if err is None else (err | self._dense_query_bad)
         else:
             rgb_feature, record = self._eager_features(data, images, counts, bank, bank_rows)
             if sig is not None:
@@ -314,10 +329,15 @@ class BoxDreamer(nn.Module):
 
         pred_poses = data["poses"].clone()
         syncs = []
+        # the selected slots travel with the corners' D2H when the host needs them (original_images is a host list)
+        slots = data["dense_ref_slots"] if dense_plan is not None and "original_images" in data else None
+        self._slots_host = None
         if not self.training:
-            pred_poses = self._process_evaluation(pred_poses, data, query_ret, ar, qi, decoded, syncs, write_pred_bbox)
+            pred_poses = self._process_evaluation(pred_poses, data, query_ret, ar, qi, decoded, syncs, write_pred_bbox, slots)
         else:
             write_pred_bbox()
+        if slots is not None:
+            self._repack_original_images(data, dense_plan, slots, syncs)
         data["pred_poses"] = pred_poses
         data["pred_intrinsics"] = data["intrinsics"]
         self.host_syncs_per_forward = syncs
@@ -333,19 +353,77 @@ class BoxDreamer(nn.Module):
         err = self.decoder.mask_error
         self.decoder.mask_error = beyond if err is None else (err | beyond)
 
+    def _dense_bank_plan(self, bank, rows, counts, query_idx, B: int, T: int):
+        """Host side of the banked dense-reference mode, before any launch: (reference rows [B][N_max], n_refs, N_max, query slot per
+        sample, k).  The table names every reference by bank row and the query by its one -1; a host `query_idx` must agree with it (a
+        device one is compared on the device and reported with the corners' D2H, as in the ragged mode)."""
+        if not bank.has_match_summaries:
+            raise ValueError("dense_cfg.enable with a ref_bank needs the bank's match summaries: build it with "
+                             "RefFeatureBank(encoder, match_threshold=0.05)")
+        host_q = None
+        if isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda:
+            host_q = query_idx.reshape(-1).tolist()
+        elif not isinstance(query_idx, torch.Tensor):
+            host_q = list(query_idx)
+        k = int(_get(self.dense_cfg, "filter_topk"))
+        return _lib.dense_bank_tables(rows, counts if counts is not None else [T] * B, k, host_q) + (k,)
+
+    def _banked_dense_features(self, data, images, bank, plan, query_idx, qi):
+        """(features.OperandOnly of (B, k + 1, P, C), this forward's record, view indices (B, k + 1) of the kept views: the selected
+        references in slot order, the query last).  The B query crops go through the encoder in ONE predict call; bd_match_view_sums
+        summarises them, ONE bd_match_select_rows launch scores every reference against its query from the bank's summaries, picks
+        the k best and writes the source table of ONE bd_gather_view_rows launch.  Images in banked slots are never read; nothing
+        here waits for the device."""
+        ref_rows, n_refs, n_max, query, k = plan
+        B, T = images.shape[:2]
+        refreshed = bank.ensure_fresh()
+        rows_d, n_refs_d, q_d, q_flat = bank.dense_tables(ref_rows, n_refs, n_max, query, T, images.device)
+        crops = images.reshape(B * T, *images.shape[2:]).index_select(0, q_flat)
+        fresh = self.rgb_encoder.predict(crops)
+        scores, sel, src = bank.select(fresh, crops, rows_d, n_refs_d, k)
+        feats = bank.gather(src, fresh, (B, k + 1))
+        data["dense_ref_slots"], data["dense_ref_scores"] = sel, scores
+        self._dense_query_bad = (qi != q_d).any() if isinstance(query_idx, torch.Tensor) and query_idx.is_cuda else None
+        record = self._lanes_record(B, k + 1, None) if isinstance(self.decoder, BETR) else {}
+        record["ref_bank"] = {"banked_views": B * k, "encoded_views": B, "scored_views": sum(n_refs), "refreshed": bool(refreshed)}
+        ref = sel.long()
+        ref = ref + (ref >= q_d[:, None]).long()                # reference slot -> view slot: the query's own slot is skipped
+        return feats, record, torch.cat([ref, q_d[:, None]], dim=1)
+
+    def _repack_original_images(self, data, plan, slots, syncs) -> None:
+        """`original_images` ([T][B] host list) keeps the selected views, the query last (data_processing.py:150-176) -- on the host,
+        from the slots that came back with the corners' D2H (or, where no such copy ran, from one of their own)."""
+        host = getattr(self, "_slots_host", None)
+        if host is None:
+            host = slots.cpu().tolist()
+            syncs.append(f"dense_ref_slots D2H ({slots.numel() * 4} bytes; original_images is re-packed on the host)")
+        self._slots_host = None
+        query, org = plan[3], data["original_images"]
+        k = len(host[0])
+        new = [[] for _ in range(k + 1)]
+        for b, q in enumerate(query):
+            for j, s in enumerate(host[b]):
+                new[j].append(org[int(s) + (int(s) >= q)][b])
+            new[k].append(org[q][b])
+        data["original_images"] = new
+
     def _check_mode(self, data, B: int, T: int, counts, dense: bool):
         """One batch names its references ONE way: refuse, before any launch, the combinations that are not implemented.  Returns
         (cache.RefFeatureBank, its validated host table of bank rows; -1: encode this slot), or (None, None) without a bank."""
         bank, rows = data.get("ref_bank"), data.get("ref_rows")
         ragged, banked, cached, betr = counts is not None, bank is not None or rows is not None, "cached_rgb_feat" in data, isinstance(self.decoder, BETR)
-        if ragged and dense:
-            raise NotImplementedError("view_counts together with dense_cfg.enable (ragged dense-reference mode) is not implemented")
         if ragged and cached:
             raise NotImplementedError("view_counts together with cached_rgb_feat (ragged feature cache) is not implemented")
+        if ragged and dense and not banked:
+            raise NotImplementedError("view_counts together with dense_cfg.enable needs a ref_bank: the ragged dense-reference mode is "
+                                      "implemented over the reference bank only")
         if ragged and not betr:
             raise NotImplementedError("view_counts needs the BETR decoder")
-        if banked and dense:
-            raise NotImplementedError("ref_bank together with dense_cfg.enable (banked dense-reference mode) is not implemented")
+        if banked and dense and _get(self.dense_cfg, "multi_round", False):
+            raise NotImplementedError("ref_bank together with dense_cfg.multi_round (multi-round decode over the bank) is not implemented")
+        if banked and dense and not (_get(self.dense_cfg, "filter") == "dino" and _get(self.dense_cfg, "filter_enable")):
+            raise NotImplementedError("ref_bank together with dense_cfg.enable is implemented for the DINO filter only "
+                                      "(dense_cfg.filter = 'dino' with dense_cfg.filter_enable)")
         if banked and cached:
             raise NotImplementedError("ref_bank together with cached_rgb_feat: give the references one way or the other")
         if banked and not betr:
@@ -407,7 +485,7 @@ class BoxDreamer(nn.Module):
             self._graph_key = key
         return self._graph(images, pose_feat, qi)
 
-    def _process_evaluation(self, pred_poses, data, query_ret, ar, qi, decoded=None, syncs=None, behind_the_d2h=None):
+    def _process_evaluation(self, pred_poses, data, query_ret, ar, qi, decoded=None, syncs=None, behind_the_d2h=None, slots=None):
         """prediction_utils.py:63-101 for bb8/heatmap: decode corners on the GPU, ONE D2H (corners + 3-D box + K + the decoder's deferred
         mask verdict in one buffer), host PnP."""
         B = query_ret.shape[0]
@@ -439,6 +517,8 @@ class BoxDreamer(nn.Module):
             # ONE D2H into a pinned buffer, asynchronously; everything the device can do without the poses is enqueued behind it, and only
             # then does the host wait (for the copy's event, not for the stream) -- round 6: the device used to idle through the host PnP
             packed = torch.cat([kp_px.reshape(-1), bbox_3d.reshape(-1), K.reshape(-1), flag])
+            if slots is not None:       # (small integers: exact in fp32)
+                packed = torch.cat([packed, slots.reshape(-1).float()])
             if packed.is_cuda:
                 if self._d2h_pin is None or self._d2h_pin.numel() != packed.numel():
                     self._d2h_pin = torch.empty(packed.numel(), dtype=torch.float32, pin_memory=True)
@@ -452,9 +532,11 @@ class BoxDreamer(nn.Module):
                 device_work_independent_of_the_poses()
                 host = packed.numpy()
             syncs.append(f"corners + 3-D box + K + mask verdict: ONE D2H of {host.size * 4} bytes, then the host PnP of {B} poses")
-            bad = bool(host[-1] != 0.0)
-            n1, n2 = B * 16, B * 16 + B * 24
-            poses = torch.from_numpy(solve_poses_host(host[:n1].reshape(B, 8, 2), host[n1:n2].reshape(B, 8, 3), host[n2:-1].reshape(B, 3, 3)))
+            n1, n2, n3 = B * 16, B * 16 + B * 24, B * 16 + B * 24 + B * 9
+            bad = bool(host[n3] != 0.0)
+            if slots is not None:
+                self._slots_host = host[n3 + 1:].reshape(B, -1).astype("int64").tolist()
+            poses = torch.from_numpy(solve_poses_host(host[:n1].reshape(B, 8, 2), host[n1:n2].reshape(B, 8, 3), host[n2:n3].reshape(B, 3, 3)))
             data["pose_solver"] = ("host:cv2.solvePnP" if pnp._HAVE_CV2
                                    else "host:bd_solve_pnp_host (native threads, DLT + LM; parity vs OpenCV un-pinned)")
         if bad:

@@ -364,6 +364,34 @@ int bd_dino_match_scores(const float* feats, const void* images, int img_dtype, 
  * unordered and never selected: callers pass NaN-free rows (bd_dino_match_scores writes none). */
 int bd_topk_mask(const float* scores, int B, int N, int k, unsigned char* mask, void* stream);
 
+/* Dense-reference mode over a bank of cached views (cache.RefFeatureBank): a pair's score needs only each view's foreground feature
+ * sum (D floats) and foreground patch count, so a view is summarised ONCE, when it enters the bank, and a forward scores, selects and
+ * names its references without the views' features or crops.
+ *
+ * bd_match_view_sums: the per-view pass of bd_dino_match_scores (the same kernel) over V free-standing views.  feats: fp32 [V, L, D];
+ * images: [V, 3, H, W] (img_dtype BD_DTYPE_*); sums: fp32 [V, D]; counts: fp32 [V].  A view's sums / counts are bit-identical to the
+ * scratch bd_dino_match_scores fills for it.  The same checks as bd_dino_match_scores; V < 0 BD_ERR_SHAPE, V == 0 BD_OK without a
+ * launch. */
+int bd_match_view_sums(const float* feats, const void* images, int img_dtype, int V, int L, int D, int H, int W,
+                       float lum_threshold, float* sums, float* counts, void* stream);
+
+/* bd_match_select_rows: score, top-k and compaction in ONE launch, one workgroup per sample.  bank_sums [R, D] / bank_counts [R]: the
+ * summaries of the bank's views; q_sums [B, D] / q_counts [B]: those of the B query views; rows: device int32 [B, N_max], the bank
+ * row of every reference slot; n_refs: device int32 [B], k <= n_refs[b] <= N_max <= 1024 references per sample.
+ * scores: fp32 [B, N_max], bit-identical to bd_dino_match_scores' score of the same pair (same summation order, zero-pairs rule and
+ * nan_to_num); -inf for the slots n >= n_refs[b], which are never read through `rows` and never selected, and for a `rows` entry
+ * outside [0, R).  sel: int32 [B, k], the selected slots in ascending order -- bd_topk_mask's rule: largest score, ties to the lower
+ * slot, -inf an ordinary value.  src: int32 [B * (k + 1)], bd_gather_view_rows' source table of the (B, k + 1) batch: per sample the
+ * selected bank rows in slot order, then -(b + 1), fresh view b (the query).
+ * Inconsistent device data reads and writes nothing out of bounds: n_refs[b] is clamped into [0, N_max]; where that leaves fewer
+ * than k slots the remaining entries of sel[b] are -1 and their src entries 0x7fffffff, which bd_gather_view_rows skips, as is the
+ * src entry of a selected slot whose row is outside the bank.
+ * Checked before any launch: NULL pointers BD_ERR_NULL; B <= 0, R < 0, N_max <= 0, N_max > 1024, k <= 0, k > N_max, L <= 0, D <= 0
+ * BD_ERR_SHAPE. */
+int bd_match_select_rows(const float* bank_sums, const float* bank_counts, int R, const float* q_sums, const float* q_counts,
+                         const int32_t* rows, const int32_t* n_refs, int B, int N_max, int L, int D, int k,
+                         float* scores, int32_t* sel, int32_t* src, void* stream);
+
 /* Eval-step pose metrics: the per-sample values of Metrics.compute_metrics, src/lightning/utils/metrics/metric_utils.py:97-128
  * (query_pose_error :162-211, process_single_bs_2d :255-306 with project_optimized :224-239, process_single_bs_add :331-424).
  * Per pose b (the query view, gathered by the caller): pred_poses / original_poses fp32 [n_poses, 4, 4], scale fp32 [n_poses, 3],
