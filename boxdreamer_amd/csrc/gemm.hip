@@ -870,6 +870,8 @@ extern "C" int bd_gemm(const bd_gemm_args* args, int prec, void* stream) {
     const int kmult = prec == BD_PREC_FP8 ? 128 : 64;
     const int esz = prec == BD_PREC_FP8 ? 1 : 2;
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % kmult) != 0) return BD_ERR_SHAPE;
+    // a leading dimension below the row's length: consecutive rows would overlap (host arithmetic only, nothing is read from the device)
+    if (a.lda < a.K || a.ldw < a.K || a.ldo < a.N || (a.resid && a.ldr < a.N) || (a.ln_op_out && a.ln_op_ld < a.N)) return BD_ERR_SHAPE;
     if (((a.lda * esz) % 16) || ((a.ldw * esz) % 16) || ((uintptr_t)a.A & 15) || ((uintptr_t)a.W & 15)) return BD_ERR_ALIGN;
     if ((prec == BD_PREC_BF16X3 || prec == BD_PREC_F16X3 || prec == BD_PREC_F16C8) && ((a.a_plane % 8) || (a.w_plane % 8))) return BD_ERR_ALIGN;
     if (a.addtab && a.tab_rows <= 0) return BD_ERR_SHAPE;

@@ -141,6 +141,9 @@ const char* bd_target_arch(void); /* "gfx950" */
  *   and the 14x14/s14 patch-embed conv as an im2col GEMM (layers/patch_embed.py:65,75).
  * A: [M, K] 16-bit row-major (lda elements); W: [N, K] 16-bit row-major (nn.Linear layout).
  * K must be a multiple of 64 (128 for BD_PREC_FP8; callers zero-pad); M, N arbitrary.
+ * Leading dimensions may exceed the row length (rows inside a wider buffer, planes further apart than rows * ld) but never fall below
+ * it: lda < K, ldw < K, ldo < N, ldr < N with a residual, or ln_op_ld < N with ln_op_out would make consecutive rows overlap and
+ * return BD_ERR_SHAPE before any launch (a host check of the arguments; nothing is read from the device).
  * map(r) = r if rpg_in == 0 else (r / rpg_in) * rpg_out + r % rpg_in + row_off. */
 typedef struct bd_gemm_args {
     const void* A; int64_t lda; int64_t a_plane;   /* a_plane: elements between hi/lo planes (BF16X3) */
