@@ -127,6 +127,9 @@ EXPORTS = [
     "bd_attention_varlen", "bd_query_substitute_varlen", "bd_gather_query_rows_f32_varlen", "bd_gather_query_tokens_varlen",
     "bd_decoder_workspace_bytes_ragged", "bd_decoder_forward_ragged", "bd_gather_view_rows",
     "bd_match_view_sums", "bd_match_select_rows",
+    "bd_assemble_entry_tokens", "bd_decoder_entry_tokens_workspace_bytes", "bd_decoder_entry_tokens",
+    "bd_decoder_entry_workspace_bytes", "bd_decoder_forward_entry", "bd_decoder_entry_workspace_bytes_ragged",
+    "bd_decoder_forward_entry_ragged",
 ]
 
 _lib = None
@@ -203,6 +206,16 @@ def load() -> C.CDLL:
     lib.bd_gather_view_rows.argtypes = [vp, i64, i, vp, i64, i, vp, vp, i64, i, i, i, i, vp, vp, vp, vp]
     lib.bd_match_view_sums.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, vp]
     lib.bd_match_select_rows.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp]
+    lib.bd_assemble_entry_tokens.argtypes = [vp, i, vp, i, vp, vp, vp, vp, i, i, i, vp]
+    lib.bd_decoder_entry_tokens_workspace_bytes.argtypes = [C.POINTER(BetrWeights), i, i]
+    lib.bd_decoder_entry_tokens_workspace_bytes.restype = sz
+    lib.bd_decoder_entry_tokens.argtypes = [C.POINTER(BetrWeights), vp, i, vp, i64, i, i, vp, vp, sz, i, vp]
+    lib.bd_decoder_entry_workspace_bytes.argtypes = [C.POINTER(BetrWeights), i, i, i, i]
+    lib.bd_decoder_entry_workspace_bytes.restype = sz
+    lib.bd_decoder_forward_entry.argtypes = [C.POINTER(BetrWeights), vp, i, vp, vp, i64, vp, i, i, i, vp, vp, vp, sz, i, i, vp]
+    lib.bd_decoder_entry_workspace_bytes_ragged.argtypes = [C.POINTER(BetrWeights), i, i, i]
+    lib.bd_decoder_entry_workspace_bytes_ragged.restype = sz
+    lib.bd_decoder_forward_entry_ragged.argtypes = [C.POINTER(BetrWeights), vp, i, vp, vp, i64, vp, vp, i, i, i, i, vp, vp, vp, sz, i, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:
@@ -483,6 +496,23 @@ def dense_bank_tables(rows, counts, topk: int, query_idx=None):
         query.append(q)
         out.append(refs + [-1] * (n_max - len(refs)))
     return out, n_refs, n_max, query
+
+
+def entry_bank_queries(rows, counts, query_idx=None):
+    """The query slot per sample of a batch over a bank that keeps decoder-entry tokens (cache.RefFeatureBank with decoder=), from a
+    validated `ref_rows` table (check_ref_rows).  Such a bank holds finished token rows, so the one view a forward encodes is the
+    query: exactly one valid slot per sample is -1, and it equals the host `query_idx[b]` when one is given (dense_bank_tables'
+    rule, which does the rest of the validation).  ValueError otherwise."""
+    for b, (row, c) in enumerate(zip(rows, counts)):
+        fresh = [t for t in range(c) if row[t] < 0]
+        if not fresh:
+            raise ValueError(f"ref_rows[{b}] names no slot to encode (-1) among its {c} views: the query view is encoded in every forward")
+        stray = [t for t in fresh if query_idx is None or t != int(query_idx[b])]
+        if len(fresh) > 1 and stray:
+            raise ValueError(f"ref_rows[{b}][{stray[-1 if query_idx is None else 0]}] = -1 at a reference slot: an entry bank takes no freshly "
+                             f"encoded references (slots {fresh} of sample {b} are -1; a bank built with decoder= holds the references' "
+                             "finished token rows and a forward encodes the query only -- add() the reference with its heat maps first)")
+    return dense_bank_tables(rows, counts, 1, query_idx)[3]
 
 
 def attention_work_list(counts, heads: int, tokens_per_view: int, q_block: int, query_only: bool = False):

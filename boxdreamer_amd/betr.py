@@ -205,6 +205,115 @@ class BETR(nn.Module):
             self._ragged_index[key] = hit
         return hit
 
+    def _one_hot_query(self, masks, B: int, T: int, counts, views, dev):
+        """The one-hot check of `masks` as `validate_inputs` asks for it (forward()'s rule), then the query view per sample, int32 [B]."""
+        if masks.dtype != torch.bool or masks.shape != (B, T):
+            raise ValueError("masks must be a (B, T) bool tensor")
+        if self.validate_inputs and not torch.cuda.is_current_stream_capturing():
+            bad = masks.sum(dim=1) != 1
+            if counts is not None:       # ... and among the sample's own views (a padded slot is never a view)
+                valid = torch.arange(T, device=dev)[None, :] < (views.view_start[1:] - views.view_start[:-1])[:, None]
+                bad = bad | (masks & ~valid).any(dim=1)
+            bad = bad.any()
+            if self.validate_inputs == "deferred":
+                self.mask_error = bad                  # stays on the device; the caller raises (no sync here)
+            elif bool(bad):
+                raise ValueError("masks must mark exactly one query view per sample" +
+                                 (", among the sample's view_counts views" if counts is not None else ""))
+        return masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
+
+    @torch.no_grad()
+    def entry_tokens(self, pose_feat, pretrain_rgb_feat, out=None):
+        """The decoder-ENTRY token rows of free-standing views (bd_decoder_entry_tokens; betr.py:313-329, :367-399):
+        x = bbox_emb(patchify(pose_feat)) + pos + adapter(feat), the row forward() builds for a reference view before its first block.
+        pose_feat (N, 8, H, W); pretrain_rgb_feat (N, P, C) from the HIP encoder (with its operand copy, in this decoder's feature
+        class: ValueError otherwise -- nothing is re-cast for a bank) -> fp32 (N, P, d_model), written into `out` when given.  What
+        cache.RefFeatureBank(decoder=...) keeps per reference and forward_entry() consumes."""
+        _lib.require_gpu()
+        lib = _lib.load()
+        only = isinstance(pretrain_rgb_feat, features.OperandOnly)
+        dev = _lib.same_device(pose_feat, pretrain_rgb_feat.operand if only else pretrain_rgb_feat, out)
+        prec = self.hip_precision
+        pid = _lib.prec_id(prec)
+        w = self._weights(dev, prec).struct
+        P, D, N = w.grid * w.grid, w.dim, int(pose_feat.shape[0])
+        if pose_feat.dim() != 4 or tuple(pose_feat.shape[1:]) != (self.box_dim, self.img_size, self.img_size):
+            raise ValueError(f"pose_feat must be (N, {self.box_dim}, {self.img_size}, {self.img_size}), got {tuple(pose_feat.shape)}")
+        if tuple(pretrain_rgb_feat.shape) != (N, P, D):
+            raise ValueError(f"pretrain_rgb_feat must be ({N}, {P}, {D}), got {tuple(pretrain_rgb_feat.shape)}")
+        fcls = self.feats_class(prec)
+        feats16 = features.resolve(pretrain_rgb_feat, fcls, _lib.planes(fcls) * N * P * D, dev)
+        if feats16 is None:
+            raise ValueError(f"entry tokens need the HIP encoder's operand copy of the features in this decoder's feature class ({fcls}); "
+                             "these carry none (computed elsewhere, copied or sliced), or one of another class")
+        if out is None:
+            out = torch.empty((N, P, D), dtype=torch.float32, device=dev)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (N, P, D) or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous fp32 ({N}, {P}, {D}) tensor")
+        ws = self._workspace(lib.bd_decoder_entry_tokens_workspace_bytes(w, N, pid), dev)
+        hip_ops.decoder_entry_tokens(w, pose_feat.contiguous(), feats16, operand.plane_offset(feats16, fcls), out, ws, prec=pid)
+        return out
+
+    @torch.no_grad()
+    def forward_entry(self, entry_rows, n_rows, src, query_feat, masks, img_size=None, view_counts=None):
+        """forward() on banked decoder-entry tokens (bd_decoder_forward_entry): no heat map is read, patchified or embedded.
+        entry_rows: fp32 (capacity, P, d_model), cache.RefFeatureBank.entry_tokens, its first n_rows rows in use; src: device int32
+        [n_views], the source table of the batch's views in sample order -- a reference by its bank row, sample b's query as -(b + 1)
+        (RefFeatureBank.tables / select); query_feat (B, P, C): the encoder's output for the B query crops, in sample order; masks
+        (B, T) bool: the query position per sample (T: the batch's view slots); view_counts: as in forward(), a ragged batch (one
+        lane).  Returns (B, 8, H, W) fp32 in [-1, 1], bit-identical to forward() on the same views; `last_logits` as there."""
+        _lib.require_gpu()
+        lib = _lib.load()
+        B, T = masks.shape
+        counts = None
+        if view_counts is not None:
+            counts = _lib.view_counts_list(view_counts, B)
+            _lib.check_view_counts(counts, T)
+            if all(c == T for c in counts):
+                counts = None
+        only = isinstance(query_feat, features.OperandOnly)
+        dev = _lib.same_device(entry_rows, src, masks, query_feat.operand if only else query_feat)
+        prec = self.hip_precision
+        pid = _lib.prec_id(prec)
+        w = self._weights(dev, prec).struct
+        if counts is None and w.latency_mode != int(self.hip_latency):
+            self._check_not_frozen("switching hip_latency (the workspace layout changes)")
+            w.latency_mode = int(self.hip_latency)
+        P, D = w.grid * w.grid, w.dim
+        H = self.img_size if img_size is None else int(img_size)
+        views = _Views(self, B, T, counts, dev)
+        n_views = views.n_views
+        if entry_rows.dtype != torch.float32 or entry_rows.dim() != 3 or tuple(entry_rows.shape[1:]) != (P, D) or not entry_rows.is_contiguous() \
+                or not 0 <= int(n_rows) <= entry_rows.shape[0]:
+            raise ValueError(f"entry_rows must be a contiguous fp32 (rows >= {int(n_rows)}, {P}, {D}) tensor, got {tuple(entry_rows.shape)} {entry_rows.dtype}")
+        if src.dtype != torch.int32 or src.numel() != n_views or not src.is_contiguous():
+            raise ValueError(f"src must be a contiguous int32 tensor of the batch's {n_views} views, got {tuple(src.shape)} {src.dtype}")
+        if tuple(query_feat.shape) != (B, P, D):
+            raise ValueError(f"query_feat must be ({B}, {P}, {D}), got {tuple(query_feat.shape)}")
+        query_idx = self._one_hot_query(masks, B, T, counts, views, dev)
+        fcls = self.feats_class(prec)
+        feats16 = features.resolve(query_feat, fcls, _lib.planes(fcls) * B * P * D, dev)
+        if feats16 is None:
+            raise ValueError(f"forward_entry needs the HIP encoder's operand copy of the query features in this decoder's feature class ({fcls})")
+        plane = operand.plane_offset(feats16, fcls)
+        logits = torch.empty((B, 8, H, H), dtype=torch.float32, device=dev)
+        heat = torch.empty_like(logits)
+        if counts is None:
+            lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, prec)
+            ws = self._workspace(max(lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, 1),
+                                     lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, lanes)), dev)
+            _lib.check(lib.bd_decoder_forward_entry(w, _lib.ptr(entry_rows), int(n_rows), _lib.ptr(src), _lib.ptr(feats16), plane,
+                                                    _lib.ptr(query_idx), B, T, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(),
+                                                    pid, lanes, _lib.stream()), "bd_decoder_forward_entry")
+        else:
+            ws = self._workspace(lib.bd_decoder_entry_workspace_bytes_ragged(w, n_views, B, pid), dev)
+            _lib.check(lib.bd_decoder_forward_entry_ragged(w, _lib.ptr(entry_rows), int(n_rows), _lib.ptr(src), _lib.ptr(feats16), plane,
+                                                           _lib.ptr(views.view_start), _lib.ptr(query_idx), B, n_views, views.max_views, H,
+                                                           _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, _lib.stream()),
+                       "bd_decoder_forward_entry_ragged")
+        self.last_logits = logits
+        return heat
+
     @torch.no_grad()
     def forward(self, pose_feat, rgbs=None, masks=None, pretrain_rgb_feat=None, image_masks=None, view_counts=None):
         """pose_feat (B,T,8,H,W) in [-1,1]; rgbs (B,T,3,H,W) (shape check only); masks (B,T) bool, one query
@@ -254,20 +363,9 @@ class BETR(nn.Module):
             raise ValueError(f"pretrain_rgb_feat must be (B, T, {P}, {D}), got {shape}")
         if not packed and shape != (B, T, P, D):
             raise ValueError(f"pretrain_rgb_feat must be packed ({n_views}, {P}, {D}) or padded ({B}, {T}, {P}, {D}), got {shape}")
-        if self.validate_inputs and not torch.cuda.is_current_stream_capturing():
-            # the reference writes the query token through `pose_feat[masks] = ...` (betr.py:286-290), which fails unless
-            # every sample marks exactly one view; argmax below would silently pick view 0 for an empty row
-            bad = masks.sum(dim=1) != 1
-            if counts is not None:       # ... and among the sample's own views (a padded slot is never a view)
-                valid = torch.arange(T, device=dev)[None, :] < (views.view_start[1:] - views.view_start[:-1])[:, None]
-                bad = bad | (masks & ~valid).any(dim=1)
-            bad = bad.any()
-            if self.validate_inputs == "deferred":
-                self.mask_error = bad                  # stays on the device; the caller raises (no sync here)
-            elif bool(bad):
-                raise ValueError("masks must mark exactly one query view per sample" +
-                                 (", among the sample's view_counts views" if counts is not None else ""))
-        query_idx = masks.to(torch.int32).argmax(dim=1).to(torch.int32).contiguous()
+        # the reference writes the query token through `pose_feat[masks] = ...` (betr.py:286-290), which fails unless
+        # every sample marks exactly one view; argmax would silently pick view 0 for an empty row
+        query_idx = self._one_hot_query(masks, B, T, counts, views, dev)
         fcls = self.feats_class(prec)
         if only and not packed:
             raise ValueError(f"operand-only features of a ragged batch must be packed ({n_views}, {P}, {D}), got {shape}")

@@ -29,6 +29,9 @@ decoder's feature operand from those rows and the freshly encoded query views:
 With `match_threshold=0.05` the bank also keeps each row's dense-reference match summary (bd_match_view_sums), and a model with
 `dense_cfg.enable` selects its `filter_topk` references among a sample's whole banked database (bd_match_select_rows): the table then
 holds one -1 per sample, at the query.
+With `decoder=model.decoder` the bank also keeps every row's decoder-ENTRY tokens (bd_decoder_entry_tokens): the heat maps of a
+reference are given once, `bank.add(ref_images, bbox_feat=ref_heatmaps)`, and a forward over such a bank reads the query crop and
+nothing else -- `bbox_feat` may be absent from the batch dict (bd_decoder_forward_entry).
 """
 from __future__ import annotations
 
@@ -111,10 +114,20 @@ class RefFeatureBank:
     every row also gets its dense-reference match summary -- the foreground feature sum (C floats) and the foreground patch count of
     bd_match_view_sums, computed from the encoder's fp32 output and the crop before that copy is dropped: 3 KB per view against the
     operand row's ~590 KB.  With them a dense-reference forward (dense_cfg.enable + ref_bank) scores and selects among a sample's
-    whole database without its features or crops (select)."""
+    whole database without its features or crops (select).
 
-    def __init__(self, encoder, keep_images: bool = True, match_threshold: float | None = None):
+    `decoder` (None: none kept, today's bank byte for byte; a betr.BETR): every row also gets its decoder-entry tokens
+    x = bbox_emb(patchify(bbox_feat)) + pos + adapter(feat) (bd_decoder_entry_tokens), computed in add() from the heat maps given there
+    while the encoder's output still exists, in a second store that grows with the first (same row ids): fp32 [rows, P, D],
+    P * D * 4 = 786 432 bytes per view at P = 256, D = 768, on top of the operand row's ~590 KB (the feature rows stay: the refresh
+    path and the dense selection use them).  A decoder then runs on these rows (BETR.forward_entry) without patchifying or embedding
+    a heat map.  The entry rows carry a second stamp -- what they depend on in the decoder: its weights (_signature), precision
+    mode and the promotion of the Linears outside the blocks -- and a mismatch of either stamp makes the bank stale; with
+    keep_images=True the heat maps are kept too, in the dtype they came in, and a refresh re-encodes and re-embeds."""
+
+    def __init__(self, encoder, keep_images: bool = True, match_threshold: float | None = None, decoder=None):
         self.encoder = encoder                                 # a DinoV2Wrapper
+        self.decoder = decoder                                 # a betr.BETR, or None: no entry tokens
         self.keep_images = bool(keep_images)
         self.match_threshold = None if match_threshold is None else float(match_threshold)
         self.refresh_count = 0
@@ -128,6 +141,8 @@ class RefFeatureBank:
         self._pid, self._P, self._C, self._stamp = None, 0, 0, None
         self._images = []       # [(first row, crops (N, 3, S, S))] when keep_images
         self._msums, self._mcounts = None, None                # [cap, C] / [cap] fp32 match summaries (match_threshold)
+        self._x32, self._entry_stamp, self._entry_shape = None, None, None   # [cap, P, D] fp32 decoder-entry tokens, their stamp (decoder)
+        self._heat = []         # [(first row, heat maps (N, 8, S, S))] when keep_images and decoder
 
     def __len__(self) -> int:
         return self._n
@@ -147,6 +162,21 @@ class RefFeatureBank:
         return self.match_threshold is not None
 
     @property
+    def has_entry_tokens(self) -> bool:
+        """Whether every row carries its decoder-entry tokens (the bank was built with a decoder)."""
+        return self.decoder is not None
+
+    @property
+    def entry_tokens(self):
+        """The entry store: fp32 (capacity, P, D), rows [0, len(bank)) in use (None while the bank is empty or keeps none)."""
+        return self._x32
+
+    @property
+    def entry_stamp(self):
+        """(decoder._signature(), precision mode, promotion of its Linears outside the blocks) the entry rows were made under."""
+        return self._entry_stamp
+
+    @property
     def tokens_per_view(self) -> int:
         """P: patch tokens of one view (0 while the bank is empty)."""
         return self._P
@@ -161,11 +191,21 @@ class RefFeatureBank:
         """Bytes of one row in the bank (all planes)."""
         return 0 if self._pid is None else self._P * operand.row_bytes(self._pid, self._C)
 
+    @property
+    def entry_bytes_per_view(self) -> int:
+        """Bytes of one row's decoder-entry tokens (0 when the bank keeps none, or is empty)."""
+        return 0 if self._entry_shape is None else self._entry_shape[0] * self._entry_shape[1] * 4
+
     def _now(self):
         return (self.encoder.model.state_stamp(self.encoder.prec), int(self.encoder.model.feats_class(self.encoder.prec)))
 
+    def _entry_now(self):
+        d = self.decoder
+        misc = int(d.hip_promote_misc)
+        return (d._signature(), str(d.hip_precision), misc | (_lib.PROMOTE_ADAPTER_FC2 if misc & _lib.PROMOTE_ADAPTER_FC1 else 0))
+
     def is_stale(self) -> bool:
-        return self._n > 0 and self._stamp != self._now()
+        return self._n > 0 and (self._stamp != self._now() or (self.has_entry_tokens and self._entry_stamp != self._entry_now()))
 
     def _reserve(self, need: int, dev) -> None:
         if self._t16 is not None and need <= self._cap and self._t16.device == dev:
@@ -181,9 +221,16 @@ class RefFeatureBank:
                 msums[:self._n].copy_(self._msums[:self._n])
                 mcounts[:self._n].copy_(self._mcounts[:self._n])
             self._msums, self._mcounts = msums, mcounts
+        if self.has_entry_tokens:
+            x32 = torch.empty((cap,) + self._entry_shape, dtype=torch.float32, device=dev)
+            if self._x32 is not None:
+                x32[:self._n].copy_(self._x32[:self._n])
+            self._x32 = x32
         self._t16, self._cap = new, cap
 
-    def _append(self, images: torch.Tensor) -> None:
+    ENTRY_CHUNK = 64            # views per bd_decoder_entry_tokens call (its workspace is ~4 MB per view; rows do not depend on the chunking)
+
+    def _append(self, images: torch.Tensor, bbox_feat: torch.Tensor | None = None) -> None:
         if images.device != self.encoder.get_device():
             self.encoder.to_device(images.device)
         feats = self.encoder.predict(images)                   # (N, P, C) fp32, tagged; only the operand copy is kept
@@ -194,6 +241,8 @@ class RefFeatureBank:
         if self._n == 0:
             self._pid, self._P, self._C, self._stamp = _lib.operand_prec(pid), int(P), int(C), self._now()
             self._t16, self._cap, self._msums, self._mcounts = None, 0, None, None
+            if self.has_entry_tokens:
+                self._x32, self._entry_stamp, self._entry_shape = None, self._entry_now(), (int(P), int(self.decoder.d_model))
         elif (_lib.operand_prec(pid), int(P), int(C)) != (self._pid, self._P, self._C):
             raise ValueError(f"the bank holds ({self._P}, {self._C}) views of operand class {self._pid}; got ({P}, {C}) of class {pid}")
         self._reserve(self._n + n, images.device)
@@ -201,20 +250,41 @@ class RefFeatureBank:
         if self.has_match_summaries:       # straight into the rows' place, while the fp32 features still exist
             hip_ops.match_view_sums(feats, images.contiguous(), self.match_threshold, self._msums[self._n:self._n + n],
                                     self._mcounts[self._n:self._n + n])
+        if self.has_entry_tokens:          # straight into the rows' place too, from the encoder's tagged output
+            for i in range(0, n, self.ENTRY_CHUNK):
+                j = min(n, i + self.ENTRY_CHUNK)
+                # (a slice of the tagged features carries no operand copy: the whole output goes in when one call covers it)
+                self.decoder.entry_tokens(bbox_feat[i:j], feats if (i, j) == (0, n) else _slice_views(feats, i, j),
+                                          out=self._x32[self._n + i:self._n + j])
         if self.keep_images:
             self._images.append((self._n, images))
+            if self.has_entry_tokens:
+                self._heat.append((self._n, bbox_feat))
         self._n += n
 
-    def add(self, images: torch.Tensor) -> torch.Tensor:
-        """images (R, 3, S, S) or (B, R, 3, S, S) in [0, 1] -> CPU int64 row ids of the same leading shape.  Earlier ids stay valid."""
+    def add(self, images: torch.Tensor, bbox_feat: torch.Tensor | None = None) -> torch.Tensor:
+        """images (R, 3, S, S) or (B, R, 3, S, S) in [0, 1] -> CPU int64 row ids of the same leading shape.  Earlier ids stay valid.
+        bbox_feat: the views' corner heat maps, (R, 8, S, S) or (B, R, 8, S, S) -- required by a bank that keeps decoder-entry tokens
+        (built with decoder=), refused by one that does not."""
         if images.dim() not in (4, 5):
             raise ValueError(f"expected (R, 3, S, S) or (B, R, 3, S, S), got {tuple(images.shape)}")
         lead = tuple(images.shape[:-3])
+        if self.has_entry_tokens and bbox_feat is None:
+            raise ValueError("this reference bank keeps decoder-entry tokens (it was built with decoder=): add(images, bbox_feat=...) "
+                             "needs the references' heat maps")
+        if bbox_feat is not None and not self.has_entry_tokens:
+            raise ValueError("bbox_feat given to a reference bank that keeps no decoder-entry tokens: build it with "
+                             "RefFeatureBank(encoder, decoder=model.decoder)")
+        if bbox_feat is not None and (tuple(bbox_feat.shape[:-3]) != lead or tuple(bbox_feat.shape[-3:]) != (8,) + tuple(images.shape[-2:])):
+            raise ValueError(f"bbox_feat must be {lead + (8,) + tuple(images.shape[-2:])} for images {tuple(images.shape)}, got "
+                             f"{tuple(bbox_feat.shape)}")
         flat = images.reshape(-1, *images.shape[-3:])
+        heat = bbox_feat.reshape(-1, *bbox_feat.shape[-3:]) if bbox_feat is not None else None
         self.ensure_fresh()                                    # never append rows of a new encoder state to rows of an old one
         n0 = self._n
         if flat.shape[0]:
-            self._append(flat.clone() if self.keep_images else flat)
+            keep = self.keep_images
+            self._append(flat.clone() if keep else flat, None if heat is None else (heat.clone() if keep else heat.contiguous()))
         return torch.arange(n0, self._n, dtype=torch.int64).reshape(lead)
 
     def ensure_fresh(self) -> bool:
@@ -230,13 +300,16 @@ class RefFeatureBank:
             _WARNED_STALE_BANK = True
             warnings.warn("BoxDreamer HIP path: the reference bank was filled under another precision / promotion state of the encoder (the "
                           "load-time calibration ran, or calibrate.set_state was applied, after RefFeatureBank.add); re-encoding its rows "
-                          "from the kept crops, once.", stacklevel=3)
+                          "from the kept crops, once." + (" (An entry-token bank: or under other decoder weights / another promotion "
+                          "state of the decoder; its entry rows are re-embedded from the kept heat maps.)" if self.has_entry_tokens else ""),
+                          stacklevel=3)
         # the new store is built on the side and swapped in when every row is there: a re-encode that fails part-way (out of memory,
         # say) leaves the rows and the kept crops as they were, and the failure is what the caller sees
-        new = RefFeatureBank(self.encoder, keep_images=True, match_threshold=self.match_threshold)
-        for _, img in self._images:                            # in row order: ids are unchanged
-            new._append(img)
-        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images", "_msums", "_mcounts"):
+        new = RefFeatureBank(self.encoder, keep_images=True, match_threshold=self.match_threshold, decoder=self.decoder)
+        heat = self._heat if self.has_entry_tokens else [(None, None)] * len(self._images)
+        for (_, img), (_, hm) in zip(self._images, heat):      # in row order: ids are unchanged
+            new._append(img, hm)
+        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images", "_msums", "_mcounts", "_x32", "_entry_stamp", "_entry_shape", "_heat"):
             setattr(self, k, getattr(new, k))
         self.refresh_count += 1
         return True
@@ -256,6 +329,30 @@ class RefFeatureBank:
             for b, t, r in banked:
                 images[b, t] = self.image_of(r).to(images.dtype)
         return images
+
+    def real_heatmaps(self, rows, n: int, like: torch.Tensor) -> torch.Tensor:
+        """(n, T, 8, S, S) heat maps that go with real_crops' images `like` (n, T, 3, S, S) in the precision self-check of an entry-token
+        bank's batch: every banked slot holds the heat maps the bank kept, in their dtype; the other slots -- the queries, whose heat
+        maps no decoder reads (their token rows are the query token's) -- hold zeros, whatever the batch dict has there."""
+        if not self.keep_images:
+            raise RuntimeError("the precision self-check needs the reference heat maps of the samples it measures on, and the reference "
+                               "bank kept none (keep_images=False): run model.calibrate(data) on a batch with real images (or one "
+                               "plain forward) first")
+        t = like.shape[1]
+        dtype = self._heat[0][1].dtype if self._heat else like.dtype
+        out = torch.zeros((n, t, 8) + tuple(like.shape[-2:]), dtype=dtype, device=like.device)
+        for b in range(n):
+            for s in range(t):
+                if rows[b][s] >= 0:
+                    out[b, s] = self.heatmaps_of(rows[b][s]).to(out.device)
+        return out
+
+    def heatmaps_of(self, row: int) -> torch.Tensor:
+        """The kept heat maps of a row (8, S, S) (keep_images=True, an entry-token bank)."""
+        for r0, hm in self._heat:
+            if r0 <= row < r0 + hm.shape[0]:
+                return hm[row - r0]
+        raise KeyError(f"row {row}: no heat maps kept")
 
     def image_of(self, row: int) -> torch.Tensor:
         """The kept crop of a row (3, S, S) (keep_images=True)."""
@@ -328,6 +425,16 @@ class RefFeatureBank:
         hip_ops.gather_view_rows(self._t16 if self._n else None, self._n, f16, n_fresh, src, out16, n_views, P, C, prec=pid)
         stamp = self._stamp[0] if self._stamp is not None else features.stamp_of(fresh)
         return features.OperandOnly(lead + (P, C), out16, pid, stamp)
+
+
+def _slice_views(feats: torch.Tensor, i: int, j: int) -> torch.Tensor:
+    """Views [i, j) of the encoder's tagged (N, P, C) output, with the same rows of its operand copy attached."""
+    f16, pid = features.require_tag(feats)
+    n, P, C = feats.shape
+    out16 = operand.empty(pid, (j - i) * P, C, feats.device)
+    for dst, src in zip(operand.row_planes(out16, pid, (j - i) * P), operand.row_planes(f16, pid, n * P)):
+        dst.copy_(src[i * P:j * P])
+    return features.attach(feats[i:j].contiguous(), out16, pid, features.stamp_of(feats))
 
 
 def merge_cached_features(encoder, images: torch.Tensor, cached: torch.Tensor, valid: torch.Tensor) -> torch.Tensor:

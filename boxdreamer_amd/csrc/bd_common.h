@@ -443,6 +443,11 @@ int& bd_concurrent_launches();
 int bd_attention_q_forms(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch, int seq, int heads, int head_dim,
                          float scale, const int32_t* q_view, int q_len, int prec, int latency_forms, void* stream);
 
+// layout.hip: bd_assemble_entry_tokens for a sub-batch lane: rgb_fresh holds the fresh views [fresh_first, fresh_first + n_fresh) of the
+// numbering `src` uses (the lane's own samples' queries); an entry that names another fresh view leaves its view untouched
+int bd_assemble_entry_tokens_from(const float* bank_x, int bank_views, const float* rgb_fresh, int fresh_first, int n_fresh, const float* pos,
+                                  const float* query_token, const int32_t* src, float* x_out, int n_views, int P, int dim, void* stream);
+
 // trace.hip
 int bd_trace_open(hipStream_t s, int kind, int M, int N, int K);
 void bd_trace_close(hipStream_t s, int slot);

@@ -697,3 +697,210 @@ extern "C" int bd_decoder_forward_lanes(const bd_betr_weights* w, const void* bb
                                   align256(carve_decoder(w, b, T, prec, nullptr).bytes), wprec, s);
     });
 }
+
+// ----------------------------------------------------------------------------------------------------------------------------
+// Decoder-entry tokens kept in a bank (include/boxdreamer_hip.h).  A reference's entry row -- bbox_emb(patchify(bbox_feat)) + pos +
+// adapter(feat), betr.py:313-329 and :367-399 -- is row-wise and independent of the query: bd_decoder_entry_tokens computes it once,
+// with decoder_chain's own five launches, and bd_decoder_forward_entry runs the adapter on the query rows alone, assembles the token
+// stream from the banked rows in one launch and goes on with decoder_chain's block stack and head.
+namespace {
+
+// operand classes of the Linears outside the blocks, as decoder_chain derives them (per-Linear promotion, include/boxdreamer_hip.h)
+struct MiscClasses { int a1, a2, be, bp; };
+inline MiscClasses misc_classes(const bd_betr_weights* w, int prec) {
+    const int pm0 = (prec == BD_PREC_F16C8 || prec == BD_PREC_FP8) ? w->promote_misc : 0;
+    const int pmisc = (pm0 & BD_PROMOTE_ADAPTER_FC1) ? (pm0 | BD_PROMOTE_ADAPTER_FC2) : pm0;
+    return {lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC1), lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC2),
+            lin_class(prec, pmisc, BD_PROMOTE_BBOX_EMB), lin_class(prec, pmisc, BD_PROMOTE_BBOX_PROJ)};
+}
+
+// K6 adapter on M rows: rgb = LN_noaffine(fc2(gelu(fc1(feat))))  (betr.py:313-317); feats16 arrives in the class of adapter fc1
+int adapter_rows(const bd_betr_weights* w, const MiscClasses& c, const void* feats16, int64_t feats16_plane, int M, void* t1, float* t2,
+                 float* rgb, int prec, void* stream) {
+    const int D = w->dim;
+    const int64_t pD = (int64_t)M * D;
+    {
+        bd_gemm_args g = gemm_args(feats16, D, feats16_plane, w->adapter_fc1, D, D, t1, D, pD, handoff_kind(c.a1, c.a2), M, D, BD_ACT_GELU);
+        BD_TRY(bd_gemm(&g, c.a1, stream));
+    }
+    {
+        bd_gemm_args g = gemm_args(t1, D, pD, w->adapter_fc2, D, D, t2, D, 0, 1, M, D, BD_ACT_NONE);
+        BD_TRY(bd_gemm(&g, c.a2, stream));
+    }
+    return bd_layernorm(t2, D, nullptr, nullptr, w->adapter_ln_eps, nullptr, 0, rgb, D, M, D, 0, 0, 0, prec, stream);
+}
+
+struct TokBufs { void *a_heat, *t1; float *t2, *rgb; size_t bytes; };
+TokBufs carve_entry_tokens(const bd_betr_weights* w, int64_t n_views, int prec, void* ws) {
+    Carver c{(unsigned char*)ws, 0};
+    const int np = planes_of(prec), D = w->dim;
+    const int64_t M = n_views * w->grid * w->grid;
+    TokBufs t;
+    t.a_heat = c.take((size_t)M * w->kpad * 2 * np);
+    t.t1 = c.take((size_t)M * D * 2 * np);
+    t.t2 = (float*)c.take((size_t)M * D * 4);
+    t.rgb = (float*)c.take((size_t)M * D * 4);
+    t.bytes = c.off + 256;
+    return t;
+}
+
+// the entry decoder's buffers: the adapter's on the B * P query rows (t2 doubles as the last block's compact stream, as in
+// decoder_chain), the head's, and the block buffers on all n_views * P rows -- no heat-map patch operand
+struct EntryBufs { void *t1, *qtok; float *t2, *rgb, *proj; BlockBufs blk; size_t bytes; };
+EntryBufs carve_entry_views(const bd_betr_weights* w, int64_t n_views, int B, int prec, void* ws) {
+    Carver c{(unsigned char*)ws, 0};
+    const int np = planes_of(prec), P = w->grid * w->grid, D = w->dim;
+    const int64_t Mb = n_views * P, Mq = (int64_t)B * P;
+    const int F = w->patch * w->patch * w->box_dim;
+    EntryBufs d;
+    d.t1 = c.take((size_t)Mq * D * 2 * np);
+    d.t2 = (float*)c.take((size_t)Mq * D * 4);
+    d.rgb = (float*)c.take((size_t)Mq * D * 4);
+    d.qtok = c.take((size_t)Mq * D * 2 * np);
+    d.proj = (float*)c.take((size_t)Mq * F * 4);
+    d.blk = carve_block(c, Mb, D, np, w->latency_mode != 0);
+    d.bytes = c.off + 256;
+    return d;
+}
+
+inline bool bad_betr_shape(const bd_betr_weights* w, int size) {
+    return size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 || w->kpad < w->patch * w->patch * w->box_dim;
+}
+
+// decoder_chain with its token stream assembled from banked entry rows: the same Stack, the same plan, the same head.
+int entry_chain(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src, const void* feats16, int64_t feats16_plane,
+                const int32_t* view_start, const int32_t* query_idx, int first, int B, int n_views, int T, int size, float* logits,
+                float* heat, void* workspace, size_t workspace_bytes, int wprec, void* stream) {
+    const int prec = gemm_prec(wprec);
+    const EntryBufs d = carve_entry_views(w, n_views, B, prec, workspace);
+    if (workspace_bytes < d.bytes) return BD_ERR_WORKSPACE;
+    const int P = w->grid * w->grid, D = w->dim, F = w->patch * w->patch * w->box_dim;
+    const int Mb = n_views * P, Mq = B * P;
+    Stack s{};
+    s.blocks = w->blocks; s.depth = w->depth; s.b = d.blk;
+    s.M = Mb; s.batch = B; s.seq = T * P; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.rms_eps = w->rms_eps;
+    s.lat = !view_start && w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
+    s.view_start = view_start; s.n_views = n_views; s.max_views = T;
+    std::vector<BlockPlan> sched;
+    BD_TRY(plan_stack(s, wprec, sched));
+    if (d.blk.sk && hipMemsetAsync(d.blk.sk, 0, d.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
+    const MiscClasses c = misc_classes(w, prec);
+    // K6 on the query views only, then the stream: banked rows as they are, the query rows (query_token + rgb) + pos  (betr.py:286-290)
+    BD_TRY(adapter_rows(w, c, feats16, feats16_plane, Mq, d.t1, d.t2, d.rgb, prec, stream));
+    // (`first`: a sub-batch lane's samples are [first, first + B) of the batch, and src names their queries by the batch's numbering)
+    BD_TRY(bd_assemble_entry_tokens_from(bank_x, bank_views, d.rgb, first, B, w->pos_table, w->query_token, src, d.blk.x, n_views, P, D, stream));
+    for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
+    // K10: head on the query view's tokens (no final norm, betr.py:298-306)
+    BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c.bp, stream));
+    {
+        bd_gemm_args g = gemm_args(d.qtok, D, (int64_t)Mq * D, w->bbox_proj, D, F, d.proj, F, 0, 1, Mq, D, BD_ACT_NONE);
+        BD_TRY(bd_gemm(&g, c.bp, stream));
+    }
+    return bd_unpatchify_sigmoid(d.proj, logits, heat, B, w->box_dim, size, w->patch, stream);
+}
+
+int entry_forward_one(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src, const void* feats16,
+                      int64_t feats16_plane, const int32_t* query_idx, int first, int B, int T, int size, float* logits, float* heat,
+                      void* workspace, size_t workspace_bytes, int wprec, void* stream) {
+    if (!w || !src || !feats16 || !query_idx || !workspace || !w->blocks || (!logits && !heat) || (bank_views > 0 && !bank_x)) return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (B <= 0 || T <= 0 || bank_views < 0 || bad_betr_shape(w, size)) return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    return entry_chain(w, bank_x, bank_views, src, feats16, feats16_plane, nullptr, query_idx, first, B, B * T, T, size, logits, heat, workspace,
+                       workspace_bytes, wprec, stream);
+}
+
+}  // namespace
+
+extern "C" size_t bd_decoder_entry_tokens_workspace_bytes(const bd_betr_weights* w, int n_views, int prec) {
+    if (!w || n_views <= 0 || bad_prec(prec)) return 0;
+    return carve_entry_tokens(w, n_views, gemm_prec(prec), nullptr).bytes;
+}
+
+extern "C" int bd_decoder_entry_tokens(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
+                                       int64_t feats16_plane, int n_views, int size, float* x_out, void* workspace,
+                                       size_t workspace_bytes, int wprec, void* stream) {
+    if (!w || !bbox_feat || !feats16 || !x_out || !workspace) return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (in_dtype < 0 || in_dtype > 2) return BD_ERR_DTYPE;
+    if (n_views <= 0 || bad_betr_shape(w, size) || (int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    const int prec = gemm_prec(wprec);
+    const TokBufs t = carve_entry_tokens(w, n_views, prec, workspace);
+    if (workspace_bytes < t.bytes) return BD_ERR_WORKSPACE;
+    const int P = w->grid * w->grid, D = w->dim, M = n_views * P;
+    const MiscClasses c = misc_classes(w, prec);
+    BD_TRY(adapter_rows(w, c, feats16, feats16_plane, M, t.t1, t.t2, t.rgb, prec, stream));
+    // K7+K8: heatmap patch embedding fused with  + rgb + pos  (betr.py:324-329, 367-399)
+    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, t.a_heat, (int64_t)M * w->kpad, n_views, w->box_dim, size, w->patch, w->kpad, c.be, stream));
+    bd_gemm_args g = gemm_args(t.a_heat, w->kpad, (int64_t)M * w->kpad, w->bbox_emb, w->kpad, D, x_out, D, 0, 1, M, w->kpad, BD_ACT_NONE);
+    g.addtab = w->pos_table; g.tab_rows = P;
+    g.resid = t.rgb; g.ldr = D;
+    return bd_gemm(&g, c.be, stream);
+}
+
+extern "C" size_t bd_decoder_entry_workspace_bytes_ragged(const bd_betr_weights* w, int n_views, int B, int prec) {
+    if (!w || B <= 0 || n_views < B || bad_prec(prec)) return 0;
+    return carve_entry_views(w, n_views, B, gemm_prec(prec), nullptr).bytes;
+}
+
+extern "C" size_t bd_decoder_entry_workspace_bytes(const bd_betr_weights* w, int B, int T, int prec, int lanes) {
+    if (!w || B <= 0 || T <= 0 || bad_prec(prec)) return 0;
+    const int nl = lane_count(lanes, B);
+    size_t total = 0;
+    for (int l = 0; l < nl; ++l) {
+        const int b = lane_units(B, nl, l);
+        total += align256(carve_entry_views(w, (int64_t)b * T, b, gemm_prec(prec), nullptr).bytes);
+    }
+    return total;
+}
+
+extern "C" int bd_decoder_forward_entry(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src,
+                                        const void* feats16, int64_t feats16_plane, const int32_t* query_idx, int B, int T, int size,
+                                        float* logits, float* heat, void* workspace, size_t workspace_bytes, int wprec, int lanes,
+                                        void* stream) {
+    const int nl = lane_count(lanes, B);
+    if (nl <= 1 || !w) return entry_forward_one(w, bank_x, bank_views, src, feats16, feats16_plane, query_idx, 0, B, T, size, logits, heat,
+                                                workspace, workspace_bytes, wprec, stream);
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (!src || !feats16 || !query_idx || !workspace) return BD_ERR_NULL;
+    if (T <= 0) return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    if (workspace_bytes < bd_decoder_entry_workspace_bytes(w, B, T, wprec, nl)) return BD_ERR_WORKSPACE;
+    const int prec = gemm_prec(wprec);
+    const int fcls = misc_classes(w, prec).a1;       // the class the adapter's first Linear reads feats16 in
+    const int64_t PD = (int64_t)w->grid * w->grid * w->dim, map_elems = (int64_t)w->box_dim * size * size;
+    const auto lane_bytes = [&](int b) { return align256(carve_entry_views(w, (int64_t)b * T, b, prec, nullptr).bytes); };
+    return run_lanes(nl, (hipStream_t)stream, [&](int l, hipStream_t s) {
+        int first = 0;
+        size_t woff = 0;
+        for (int j = 0; j < l; ++j) {
+            first += lane_units(B, nl, j);
+            woff += lane_bytes(lane_units(B, nl, j));
+        }
+        const int b = lane_units(B, nl, l);
+        const void* f16 = nullptr;
+        int64_t plane = feats16_plane;
+        operand_slice(feats16, feats16_plane, fcls, (int64_t)first * PD, &f16, &plane);     // (one query view per sample)
+        return entry_forward_one(w, bank_x, bank_views, src + (int64_t)first * T, f16, plane, query_idx + first, first, b, T, size,
+                                 logits ? logits + first * map_elems : nullptr, heat ? heat + first * map_elems : nullptr,
+                                 (unsigned char*)workspace + woff, lane_bytes(b), wprec, s);
+    });
+}
+
+extern "C" int bd_decoder_forward_entry_ragged(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src,
+                                               const void* feats16, int64_t feats16_plane, const int32_t* view_start,
+                                               const int32_t* query_view, int B, int n_views, int max_views, int size, float* logits,
+                                               float* heat, void* workspace, size_t workspace_bytes, int wprec, void* stream) {
+    if (!w || !src || !feats16 || !view_start || !query_view || !workspace || !w->blocks || (!logits && !heat) || (bank_views > 0 && !bank_x))
+        return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (B <= 0 || bank_views < 0 || n_views < B || max_views <= 0 || max_views > n_views - (B - 1) || (int64_t)max_views * B < n_views ||
+        bad_betr_shape(w, size))
+        return BD_ERR_SHAPE;
+    if ((w->grid * w->grid) % 128 || w->dim / w->heads != 96) return BD_ERR_SHAPE;      // what bd_attention_varlen takes
+    if ((int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    return entry_chain(w, bank_x, bank_views, src, feats16, feats16_plane, view_start, query_view, 0, B, n_views, max_views, size, logits, heat,
+                       workspace, workspace_bytes, wprec, stream);
+}

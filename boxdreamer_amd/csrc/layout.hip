@@ -357,6 +357,59 @@ __global__ __launch_bounds__(256) void gather_view_rows_kernel(const GatherViewA
         if (dst[i]) *(u32x4*)dst[i] = v[i];
 }
 
+// ---------------------------------------------------------------- decoder-entry token rows of a batch from a bank (bd_assemble_entry_tokens)
+// gather_view_rows_kernel's shape on ONE fp32 run per view: the grid is (view, block of GATHER_PER_WG 16-byte chunks), src[view] is
+// uniform over the workgroup, an entry outside its table ends the workgroup before it touches memory.  A banked view is moved as bits;
+// a fresh view is the query view: (query_token + rgb) + pos, query_sub_kernel's association order (no product: nothing to contract).
+struct AssembleArgs {
+    const float* bank;       // [bank_views, view_elems]
+    const float* rgb;        // [n_fresh, view_elems]
+    const float* pos;        // [view_elems]
+    const float* qtok;       // [dim]
+    const int32_t* src;
+    float* out;              // [n_views, view_elems]
+    int64_t view_elems;      // P * dim, a multiple of 4
+    int dim, bank_views, n_fresh;
+    int fresh_first;         // rgb holds the fresh views [fresh_first, fresh_first + n_fresh) of the table's numbering (a sub-batch lane's own)
+    unsigned blocks_per_view;
+};
+
+__global__ __launch_bounds__(256) void assemble_entry_tokens_kernel(const AssembleArgs a) {
+    const unsigned view = blockIdx.x / a.blocks_per_view, blk = blockIdx.x - view * a.blocks_per_view;
+    const int s = a.src[view];
+    const bool fresh = s < 0;
+    const int64_t sv = fresh ? -(int64_t)s - 1 - a.fresh_first : (int64_t)s;
+    if (sv < 0 || sv >= (int64_t)(fresh ? a.n_fresh : a.bank_views)) return;       // inconsistent entry: the view's output stays untouched
+    const float* from = (fresh ? a.rgb : a.bank) + sv * a.view_elems;
+    float* to = a.out + (int64_t)view * a.view_elems;
+    u32x4 v[GATHER_UNROLL];
+    int64_t e[GATHER_UNROLL];
+#pragma unroll
+    for (int i = 0; i < GATHER_UNROLL; ++i) {
+        e[i] = ((int64_t)blk * GATHER_PER_WG + i * 256 + threadIdx.x) * 4;
+        if (e[i] < a.view_elems) v[i] = *(const u32x4*)(from + e[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < GATHER_UNROLL; ++i) {
+        if (e[i] >= a.view_elems) continue;
+        if (fresh) {
+            const float4 p = *(const float4*)(a.pos + e[i]);
+            const float rr[4] = {__uint_as_float(v[i].x), __uint_as_float(v[i].y), __uint_as_float(v[i].z), __uint_as_float(v[i].w)};
+            const float pp[4] = {p.x, p.y, p.z, p.w};
+            float o[4];
+            int d = (int)(e[i] % a.dim);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = (a.qtok[d] + rr[j]) + pp[j];
+                if (++d == a.dim) d = 0;
+            }
+            *(float4*)(to + e[i]) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+            *(u32x4*)(to + e[i]) = v[i];
+        }
+    }
+}
+
 inline unsigned nblk(int64_t total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
@@ -542,6 +595,43 @@ extern "C" int bd_gather_view_rows(const void* bank16, int64_t bank_plane, int b
     hipLaunchKernelGGL(gather_view_rows_kernel, dim3((unsigned)(bpv * n_views)), dim3(256), 0, (hipStream_t)stream, a);
     BD_CHECK_LAUNCH();
     return BD_OK;
+}
+
+// The decoder's entry token rows of one batch from banked reference rows and the query views' adapter output -- what replaces
+// patchifying and embedding every reference's heat maps again for every query (betr.py:313-329, :367-399).  See include/boxdreamer_hip.h.
+int bd_assemble_entry_tokens_from(const float* bank_x, int bank_views, const float* rgb_fresh, int fresh_first, int n_fresh, const float* pos,
+                                  const float* query_token, const int32_t* src, float* x_out, int n_views, int P, int dim, void* stream) {
+    if (!src || !x_out || !pos || !query_token || (bank_views > 0 && !bank_x) || (n_fresh > 0 && !rgb_fresh)) return BD_ERR_NULL;
+    if (bank_views < 0 || fresh_first < 0 || n_fresh < 0 || n_views < 0 || P <= 0 || dim <= 0) return BD_ERR_SHAPE;
+    const int64_t elems = (int64_t)P * dim;
+    if (elems % 4) return BD_ERR_ALIGN;
+    const auto misaligned = [](const void* p) { return ((uintptr_t)p & 15) != 0; };
+    if (misaligned(bank_x) || misaligned(rgb_fresh) || misaligned(pos) || misaligned(query_token) || misaligned(x_out) || ((uintptr_t)src & 3))
+        return BD_ERR_ALIGN;
+    // x_out must not overlap an input: a view written early would be read back as another view's source
+    const auto overlap = [&](const void* q, int64_t nq) {
+        const int64_t np = elems * 4 * n_views;
+        return np > 0 && nq > 0 && (uintptr_t)x_out < (uintptr_t)q + (uintptr_t)nq && (uintptr_t)q < (uintptr_t)x_out + (uintptr_t)np;
+    };
+    if (overlap(bank_x, elems * 4 * bank_views) || overlap(rgb_fresh, elems * 4 * n_fresh) || overlap(pos, elems * 4) ||
+        overlap(query_token, (int64_t)dim * 4) || overlap(src, (int64_t)n_views * 4))
+        return BD_ERR_SHAPE;
+    if (n_views == 0) return BD_OK;
+    const int64_t bpv = (elems / 4 + GATHER_PER_WG - 1) / GATHER_PER_WG;
+    if (bpv * n_views > 0x7fffffffLL) return BD_ERR_SHAPE;
+    AssembleArgs a{};
+    a.bank = bank_x; a.rgb = rgb_fresh; a.pos = pos; a.qtok = query_token; a.src = src; a.out = x_out;
+    a.view_elems = elems; a.dim = dim; a.bank_views = bank_views; a.n_fresh = n_fresh; a.fresh_first = fresh_first;
+    a.blocks_per_view = (unsigned)bpv;
+    hipLaunchKernelGGL(assemble_entry_tokens_kernel, dim3((unsigned)(bpv * n_views)), dim3(256), 0, (hipStream_t)stream, a);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_assemble_entry_tokens(const float* bank_x, int bank_views, const float* rgb_fresh, int n_fresh, const float* pos,
+                                        const float* query_token, const int32_t* src, float* x_out, int n_views, int P, int dim,
+                                        void* stream) {
+    return bd_assemble_entry_tokens_from(bank_x, bank_views, rgb_fresh, 0, n_fresh, pos, query_token, src, x_out, n_views, P, dim, stream);
 }
 
 extern "C" int bd_unpatchify_sigmoid(const float* proj, float* logits, float* heat, int B, int channels, int size,

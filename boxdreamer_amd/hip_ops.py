@@ -243,6 +243,33 @@ def gather_view_rows(bank16, bank_views, fresh16, n_fresh, src, out16, n_views, 
     return out16
 
 
+def assemble_entry_tokens(bank_x, bank_views, rgb_fresh, n_fresh, pos, query_token, src, x_out, n_views, P, dim):
+    """bd_assemble_entry_tokens: x_out view v = bank_x view src[v] (src[v] >= 0, moved as bits) or, for the fresh view f = -(src[v] + 1),
+    (query_token + rgb_fresh[f]) + pos -- the decoder's entry token rows of a batch, one launch.  bank_x fp32 [bank_views, P, dim],
+    rgb_fresh fp32 [n_fresh, P, dim] (either may be None when its view count is 0), pos fp32 [P, dim], query_token fp32 [dim], src
+    device int32 [n_views], x_out fp32 [n_views, P, dim].  Returns x_out."""
+    lib = _lib.load()
+    check(lib.bd_assemble_entry_tokens(ptr(bank_x), int(bank_views), ptr(rgb_fresh), int(n_fresh), ptr(pos), ptr(query_token), ptr(src),
+                                       ptr(x_out), int(n_views), int(P), int(dim), stream()), "bd_assemble_entry_tokens")
+    return x_out
+
+
+def decoder_entry_tokens(weights, bbox_feat, feats16, feats16_plane, x_out, workspace, *, prec):
+    """bd_decoder_entry_tokens: the decoder-entry token rows of free-standing views.  weights: the decoder's _lib.BetrWeights struct;
+    bbox_feat [n_views, 8, S, S] (bf16 / fp16 / fp32, contiguous); feats16: the encoder's operand copy of the same views in the class
+    of the adapter's first Linear (plane offset feats16_plane); x_out: fp32 [n_views * P, dim]; workspace: a uint8 tensor of at least
+    bd_decoder_entry_tokens_workspace_bytes(weights, n_views, prec) bytes.  Returns x_out."""
+    lib = _lib.load()
+    if bbox_feat.dim() != 4 or not bbox_feat.is_contiguous() or x_out.dtype != torch.float32 or not x_out.is_contiguous():
+        raise ValueError("decoder_entry_tokens needs contiguous (n_views, 8, S, S) heat maps and a contiguous fp32 output")
+    n_views, size = int(bbox_feat.shape[0]), int(bbox_feat.shape[-1])
+    if x_out.numel() != n_views * weights.grid * weights.grid * weights.dim:
+        raise ValueError(f"x_out holds {x_out.numel()} elements, {n_views} views need {n_views * weights.grid * weights.grid * weights.dim}")
+    check(lib.bd_decoder_entry_tokens(weights, ptr(bbox_feat), _lib.dtype_id(bbox_feat), ptr(feats16), int(feats16_plane), n_views, size,
+                                      ptr(x_out), ptr(workspace), workspace.numel(), prec_id(prec), stream()), "bd_decoder_entry_tokens")
+    return x_out
+
+
 def match_view_sums(feats, images, threshold, sums=None, counts=None):
     """bd_match_view_sums: feats fp32 (V, L, D), images (V, 3, H, W) -> (sums fp32 (V, D), counts fp32 (V,)): each view's foreground
     feature sum and patch count, what a pair's dense-reference score is made of (csrc/match.hip).  `sums` / `counts`: where to write

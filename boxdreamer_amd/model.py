@@ -111,17 +111,21 @@ class BoxDreamer(nn.Module):
         B, T = images.shape[:2]
         mask = torch.zeros((B, T), dtype=torch.bool, device=images.device)
         mask[torch.arange(B, device=images.device), data["query_idx"].to(images.device).long()] = True
-        bbox_feat = data["bbox_feat"]
+        bank = data.get("ref_bank")
+        entry = bank is not None and getattr(bank, "has_entry_tokens", False)
+        bbox_feat = data.get("bbox_feat") if entry else data["bbox_feat"]      # (an entry-token bank's batch needs none)
         counts = self._view_counts(data, B, T)
         if counts is not None:       # ragged batch: the first sample with its own view count (its padded slots are never read)
-            images, bbox_feat, mask = images[:1, :counts[0]], bbox_feat[:1, :counts[0]], mask[:1, :counts[0]]
-        bank = data.get("ref_bank")
+            images, mask = images[:1, :counts[0]], mask[:1, :counts[0]]
+            bbox_feat = bbox_feat[:1, :counts[0]] if bbox_feat is not None else None
         if bank is not None and data.get("ref_rows") is not None:
-            # a banked batch: every sample the self-check measures on takes its references from the crops the bank kept
+            # a banked batch: every sample the self-check measures on takes its references from the crops the bank kept (and, an
+            # entry-token bank's, their heat maps from the ones it kept: the batch's own are never read and may be absent)
             rows = _lib.ref_rows_table(data["ref_rows"], B, T)
             _lib.check_ref_rows(rows, counts if counts is not None else [T] * B, len(bank))
             n = min(calibrate.MAX_SAMPLES, images.shape[0])
-            images, bbox_feat, mask = bank.real_crops(images, rows, n), bbox_feat[:n], mask[:n]
+            images, mask = bank.real_crops(images, rows, n), mask[:n]
+            bbox_feat = bank.real_heatmaps(rows, n, images) if entry else bbox_feat[:n]
         if images.device != self.rgb_encoder.get_device():
             self.rgb_encoder.to_device(images.device)
         if self.hip_promotion_file and self.hip_calibrate and calibrate.load_state(self.hip_promotion_file, self.rgb_encoder, self.decoder):
@@ -243,11 +247,16 @@ class BoxDreamer(nn.Module):
         qi = query_idx.to(dev).long()
         camera_mask = self._arange(T, dev)[None, :] == qi[:, None]
         data["camera_mask"] = camera_mask.clone()
-        pose_feat = data["bbox_feat"]
+        pose_feat = data.get("bbox_feat")
         # ragged batch: per-sample view counts (host ints).  None: the uniform batch, today's path bit for bit
         counts = self._view_counts(data, B, T)
         dense = self.dense_cfg is not None and _get(self.dense_cfg, "enable", False)
         bank, bank_rows = self._check_mode(data, B, T, counts, dense)
+        # a bank that keeps decoder-entry tokens: the decoder runs on its rows and reads no heat map (bbox_feat may be absent)
+        entry = bank is not None and bank.has_entry_tokens
+        if pose_feat is None and not entry:
+            raise KeyError("bbox_feat")
+        entry_query = self._entry_bank_plan(bank, bank_rows, counts, query_idx, B, T) if entry else None
         dense_plan = self._dense_bank_plan(bank, bank_rows, counts, query_idx, B, T) if dense and bank is not None else None
 
         if images.device != self.rgb_encoder.get_device():
@@ -287,11 +296,21 @@ class BoxDreamer(nn.Module):
                 data["hip_precision"].update(record)
             B, T = idx.shape
             qi = filter_by_view_index(data, idx, ar)
-            images, pose_feat, camera_mask = data["images"], data["bbox_feat"], data["camera_mask"]
-            query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None)
+            images, pose_feat, camera_mask = data["images"], data.get("bbox_feat"), data["camera_mask"]
+            if entry:       # (rgb_feature: the queries' encoder output and the source table bd_match_select_rows wrote)
+                query_ret = self.decoder.forward_entry(bank.entry_tokens, len(bank), rgb_feature[1], rgb_feature[0], camera_mask, images.shape[-1])
+            else:
+                query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None)
             if self._dense_query_bad is not None:       # a device-side query_idx that is not the table's -1 slot: reported with the D2H
                 err = self.decoder.mask_error
                 self.decoder.mask_error = self._dense_query_bad if err is None else (err | self._dense_query_bad)
+        elif entry:
+            # plain banked batch, uniform or ragged, over an entry-token bank: the B query crops are the one thing encoded, the decoder
+            # assembles its token stream from the bank's rows (BETR.forward_entry)
+            query_ret, record = self._entry_forward(images, counts, bank, bank_rows, camera_mask)
+            if sig is not None:
+                data["hip_precision"].update(record)
+            self._defer_table_query_check(query_idx, qi, entry_query)
         else:
             rgb_feature, record = self._eager_features(data, images, counts, bank, bank_rows)
             if sig is not None:
@@ -323,7 +342,11 @@ class BoxDreamer(nn.Module):
         # BoxDreamerModel.py:341-344 (`pred_bbox[camera_mask] = query_ret`): the same write through (sample, view) indices -- a boolean-mask
         # assignment runs nonzero() and waits for the device.  In eval the copy (the largest device operation of the dict contract: bbox_feat's
         # 154 MB at configs[1]) is enqueued BEHIND the corners' D2H, so that the device has it to do while the host solves the poses.
+        # Over an entry-token bank `bbox_feat` may be absent: nothing to clone, the decoder's output goes out as `pred_query_bbox`.
         def write_pred_bbox():
+            if "bbox_feat" not in data:
+                data["pred_query_bbox"] = query_ret
+                return
             data["pred_bbox"] = data["bbox_feat"].clone()
             data["pred_bbox"][ar, qi] = query_ret.to(data["pred_bbox"].dtype)
 
@@ -353,6 +376,50 @@ class BoxDreamer(nn.Module):
         err = self.decoder.mask_error
         self.decoder.mask_error = beyond if err is None else (err | beyond)
 
+    @staticmethod
+    def _host_query(query_idx):
+        """query_idx as host ints when it lives on the host (a device tensor: None -- it is checked on the device)."""
+        if isinstance(query_idx, torch.Tensor):
+            return None if query_idx.is_cuda else query_idx.reshape(-1).tolist()
+        return list(query_idx)
+
+    def _entry_bank_plan(self, bank, rows, counts, query_idx, B: int, T: int):
+        """Host side of a forward over an entry-token bank, before any launch: the table names every reference by bank row and the query
+        by its one -1 (the dense table's rule); returns the query slot per sample.  A host `query_idx` must agree with the table; a
+        device one is compared on the device and reported with the corners' D2H."""
+        if bank.decoder is not self.decoder:
+            raise ValueError("ref_bank keeps the entry tokens of another decoder than this model's")
+        return _lib.entry_bank_queries(rows, counts if counts is not None else [T] * B, self._host_query(query_idx))
+
+    def _defer_table_query_check(self, query_idx, qi, query) -> None:
+        """A device-side query_idx that is not the table's -1 slot travels with the decoder's deferred mask verdict (no sync here)."""
+        if not (isinstance(query_idx, torch.Tensor) and query_idx.is_cuda):
+            return
+        key = ("query", tuple(query), str(qi.device))
+        q_d = self._aranges.get(key)
+        if q_d is None:
+            if len(self._aranges) >= 256:
+                self._aranges.clear()
+            q_d = self._aranges[key] = torch.tensor(query, dtype=torch.int64).to(qi.device)
+        bad = (qi != q_d).any()
+        err = self.decoder.mask_error
+        self.decoder.mask_error = bad if err is None else (err | bad)
+
+    def _entry_forward(self, images, counts, bank, bank_rows, camera_mask):
+        """(the decoder's output, this forward's record) of a plain banked batch over an entry-token bank: a stale bank is refreshed first,
+        the B query crops go through the encoder in ONE predict call, and BETR.forward_entry runs the adapter on their rows, assembles
+        the token stream from the bank's entry rows (ONE bd_assemble_entry_tokens launch; bank.tables' source table) and runs the
+        blocks.  No heat map, no image of a banked slot and no feature row of the bank is read."""
+        B, T = images.shape[:2]
+        refreshed = bank.ensure_fresh()
+        cts = counts if counts is not None else [T] * B
+        src, encode, n_fresh = bank.tables(bank_rows, cts, T, images.device)
+        fresh = self.rgb_encoder.predict(images.reshape(B * T, *images.shape[2:]).index_select(0, encode))
+        record = self._lanes_record(B, T, counts)
+        record["ref_bank"] = {"banked_views": sum(cts) - n_fresh, "encoded_views": n_fresh, "refreshed": bool(refreshed), "entry_tokens": True}
+        heat = self.decoder.forward_entry(bank.entry_tokens, len(bank), src, fresh, camera_mask, images.shape[-1], view_counts=counts)
+        return heat, record
+
     def _dense_bank_plan(self, bank, rows, counts, query_idx, B: int, T: int):
         """Host side of the banked dense-reference mode, before any launch: (reference rows [B][N_max], n_refs, N_max, query slot per
         sample, k).  The table names every reference by bank row and the query by its one -1; a host `query_idx` must agree with it (a
@@ -360,13 +427,8 @@ class BoxDreamer(nn.Module):
         if not bank.has_match_summaries:
             raise ValueError("dense_cfg.enable with a ref_bank needs the bank's match summaries: build it with "
                              "RefFeatureBank(encoder, match_threshold=0.05)")
-        host_q = None
-        if isinstance(query_idx, torch.Tensor) and not query_idx.is_cuda:
-            host_q = query_idx.reshape(-1).tolist()
-        elif not isinstance(query_idx, torch.Tensor):
-            host_q = list(query_idx)
         k = int(_get(self.dense_cfg, "filter_topk"))
-        return _lib.dense_bank_tables(rows, counts if counts is not None else [T] * B, k, host_q) + (k,)
+        return _lib.dense_bank_tables(rows, counts if counts is not None else [T] * B, k, self._host_query(query_idx)) + (k,)
 
     def _banked_dense_features(self, data, images, bank, plan, query_idx, qi):
         """(features.OperandOnly of (B, k + 1, P, C), this forward's record, view indices (B, k + 1) of the kept views: the selected
@@ -381,11 +443,14 @@ class BoxDreamer(nn.Module):
         crops = images.reshape(B * T, *images.shape[2:]).index_select(0, q_flat)
         fresh = self.rgb_encoder.predict(crops)
         scores, sel, src = bank.select(fresh, crops, rows_d, n_refs_d, k)
-        feats = bank.gather(src, fresh, (B, k + 1))
+        # (an entry-token bank: the decoder takes the source table itself, no feature row is gathered)
+        feats = (fresh, src) if bank.has_entry_tokens else bank.gather(src, fresh, (B, k + 1))
         data["dense_ref_slots"], data["dense_ref_scores"] = sel, scores
         self._dense_query_bad = (qi != q_d).any() if isinstance(query_idx, torch.Tensor) and query_idx.is_cuda else None
         record = self._lanes_record(B, k + 1, None) if isinstance(self.decoder, BETR) else {}
         record["ref_bank"] = {"banked_views": B * k, "encoded_views": B, "scored_views": sum(n_refs), "refreshed": bool(refreshed)}
+        if bank.has_entry_tokens:
+            record["ref_bank"]["entry_tokens"] = True
         ref = sel.long()
         ref = ref + (ref >= q_d[:, None]).long()                # reference slot -> view slot: the query's own slot is skipped
         return feats, record, torch.cat([ref, q_d[:, None]], dim=1)

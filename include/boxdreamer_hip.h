@@ -320,6 +320,21 @@ int bd_gather_view_rows(const void* bank16, int64_t bank_plane, int bank_views, 
                         const int32_t* src, void* out16, int64_t out_plane, int n_views, int P, int dim, int prec,
                         const float* bank32, const float* fresh32, float* out32, void* stream);
 
+/* Assembles the decoder's ENTRY token rows of one batch (uniform or ragged) -- x = bbox_emb(patchify(bbox_feat)) + pos + adapter(feat),
+ * betr.py:313-329 and :367-399 -- from a device-resident bank of finished reference rows (bd_decoder_entry_tokens) and the adapter
+ * output of the views encoded in this forward, which are the query views: their rows are the query-token substitution of
+ * bd_query_substitute (betr.py:286-290).  bank_x: fp32 [bank_views, P, dim]; rgb_fresh: fp32 [n_fresh, P, dim] (the adapter's
+ * LayerNorm output); pos: fp32 [P, dim]; query_token: fp32 [dim]; src: device int32 [n_views]; x_out: fp32 [n_views, P, dim].
+ * Output view v with s = src[v]:  s >= 0: x_out[v] = bank_x[s], moved as 16-byte vectors (NaN payloads pass through);
+ * s < 0, f = -(s + 1): x_out[v][tok][d] = (query_token[d] + rgb_fresh[f][tok][d]) + pos[tok][d] -- bd_query_substitute's
+ * association order, the same bits.  bd_gather_view_rows' src convention and its rule for inconsistent device data: an entry
+ * s >= bank_views, or f >= n_fresh, leaves that view's output bytes untouched and the other views are written.
+ * Checked before any launch: NULL pointers (bank_x / rgb_fresh may be NULL when their view count is 0) BD_ERR_NULL; negative counts,
+ * P <= 0, dim <= 0, x_out overlapping an input BD_ERR_SHAPE; P * dim % 4 != 0 or a pointer that is not 16-byte aligned (src: 4-byte)
+ * BD_ERR_ALIGN; n_views == 0 returns BD_OK without a launch.  One launch; the grid is sized by the batch's views. */
+int bd_assemble_entry_tokens(const float* bank_x, int bank_views, const float* rgb_fresh, int n_fresh, const float* pos,
+                             const float* query_token, const int32_t* src, float* x_out, int n_views, int P, int dim, void* stream);
+
 /* BETR.unpatchify + 2*sigmoid-1 (betr.py:230-247, 432-435): proj fp32 [B*P, p*p*c] ->
  * logits, heat fp32 [B, c, size, size]. */
 int bd_unpatchify_sigmoid(const float* proj, float* logits, float* heat, int B, int channels, int size,
@@ -570,6 +585,42 @@ int bd_decoder_forward_lanes(const bd_betr_weights* w /*[host]*/, const void* bb
                              const void* feats16, int64_t feats16_plane, const int32_t* query_idx, int B,
                              int T, int size, float* logits, float* heat, void* workspace,
                              size_t workspace_bytes, int prec, int lanes, void* stream);
+
+/* Decoder-entry tokens kept in a bank (cache.RefFeatureBank with decoder=): a reference's entry row
+ *     x[v] = bbox_emb(patchify(bbox_feat[v])) + pos + LN(adapter_fc2(gelu(adapter_fc1(feat[v]))))        (betr.py:313-329, :367-399)
+ * is row-wise and independent of the query, so it is computed ONCE, when the reference enters the bank, and a forward neither reads
+ * bbox_feat nor re-embeds it.
+ *
+ * bd_decoder_entry_tokens: the entry rows of n_views free-standing views -> x_out, caller-owned fp32 [n_views * P, dim].  bbox_feat:
+ * [n_views, c, size, size] (in_dtype BD_DTYPE_*); feats16: the encoder's operand copy of the same views, in the class of adapter fc1
+ * (bd_betr_weights.promote_misc).  Exactly the five launches with which bd_decoder_forward builds its token stream (adapter fc1,
+ * adapter fc2, the no-affine LayerNorm, bd_patchify_heatmaps, the bbox_emb GEMM with its pos-table / residual epilogue) on
+ * M = n_views * P rows, in the same operand classes: a row's bits equal the row bd_decoder_forward's stream holds for that view before
+ * the query substitution.  No query row is touched.  workspace: bd_decoder_entry_tokens_workspace_bytes(w, n_views, prec) bytes. */
+size_t bd_decoder_entry_tokens_workspace_bytes(const bd_betr_weights* w /*[host]*/, int n_views, int prec);
+int bd_decoder_entry_tokens(const bd_betr_weights* w /*[host]*/, const void* bbox_feat, int in_dtype, const void* feats16,
+                            int64_t feats16_plane, int n_views, int size, float* x_out, void* workspace, size_t workspace_bytes,
+                            int prec, void* stream);
+
+/* bd_decoder_forward_entry: BETR.forward (betr.py:249-308) on banked entry rows.  bank_x: fp32 [bank_views, P, dim], rows of
+ * bd_decoder_entry_tokens; src: device int32 [B * T], bd_assemble_entry_tokens' source table of the batch -- per sample its
+ * references by bank row and its query view as -(b + 1); feats16: the encoder's operand copy of the B QUERY views, in sample order;
+ * query_idx: device int32 [B], the slot src marks as the sample's query.  The adapter (fc1, fc2, LayerNorm; betr.py:313-317) runs on
+ * the B * P query rows only, ONE bd_assemble_entry_tokens launch writes the token stream, then the block stack and the head of
+ * bd_decoder_forward run as planned there: no patchify launch, no bbox_emb GEMM, no bbox_feat.  Outputs are bit-identical to
+ * bd_decoder_forward on the same views (latency_mode: within the mode's tolerance, as ever).  `lanes`: bd_decoder_forward_lanes'
+ * sub-batch lanes (lane l reads src from its first sample's views on); <= 1 is one lane on `stream`.
+ * bd_decoder_forward_entry_ragged: the same on a ragged batch -- view_start / query_view / n_views / max_views and their constraints
+ * are bd_decoder_forward_ragged's, src is int32 [n_views] -- as ONE lane. */
+size_t bd_decoder_entry_workspace_bytes(const bd_betr_weights* w /*[host]*/, int B, int T, int prec, int lanes);
+int bd_decoder_forward_entry(const bd_betr_weights* w /*[host]*/, const float* bank_x, int bank_views, const int32_t* src,
+                             const void* feats16, int64_t feats16_plane, const int32_t* query_idx, int B, int T, int size,
+                             float* logits, float* heat, void* workspace, size_t workspace_bytes, int prec, int lanes, void* stream);
+size_t bd_decoder_entry_workspace_bytes_ragged(const bd_betr_weights* w /*[host]*/, int n_views, int B, int prec);
+int bd_decoder_forward_entry_ragged(const bd_betr_weights* w /*[host]*/, const float* bank_x, int bank_views, const int32_t* src,
+                                    const void* feats16, int64_t feats16_plane, const int32_t* view_start, const int32_t* query_view,
+                                    int B, int n_views, int max_views, int size, float* logits, float* heat, void* workspace,
+                                    size_t workspace_bytes, int prec, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Launch tracing (measurement aid for bench.py; off by default; the only library state).
