@@ -129,7 +129,7 @@ EXPORTS = [
     "bd_match_view_sums", "bd_match_select_rows",
     "bd_assemble_entry_tokens", "bd_decoder_entry_tokens_workspace_bytes", "bd_decoder_entry_tokens",
     "bd_decoder_entry_workspace_bytes", "bd_decoder_forward_entry", "bd_decoder_entry_workspace_bytes_ragged",
-    "bd_decoder_forward_entry_ragged",
+    "bd_decoder_forward_entry_ragged", "bd_solve_pnp_wave",
 ]
 
 _lib = None
@@ -192,6 +192,7 @@ def load() -> C.CDLL:
     lib.bd_topk_mask.argtypes = [vp, i, i, i, vp, vp]
     lib.bd_solve_pnp.argtypes = [vp, vp, vp, i, i, i, vp, vp]
     lib.bd_solve_pnp_host.argtypes = [vp, vp, vp, i, i, i, vp, i]
+    lib.bd_solve_pnp_wave.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
     lib.bd_pose_metrics_workspace_bytes.argtypes = [i, i]
     lib.bd_pose_metrics_workspace_bytes.restype = sz
     lib.bd_pose_metrics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp, vp]

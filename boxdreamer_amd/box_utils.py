@@ -83,9 +83,19 @@ def solve_poses_host(kp_px: np.ndarray, bbox_3d: np.ndarray, K: np.ndarray, work
     return out
 
 
-def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tensor, iters: int = 30) -> torch.Tensor:
-    """kp_px [N,n,2], bbox_3d [N,n,3], K [N,3,3] on the GPU -> poses [N,4,4] on the GPU ([R|t], zeros on failure):
-    `bd_solve_pnp`, one pose per thread in fp64 -- the corners never leave the device ("next" row f3)."""
+PNP_DEVICE_FORMS = ("thread", "wave")
+
+
+def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tensor, iters: int = 30, form: str = "thread",
+                       want_rms: bool = False):
+    """kp_px [N,n,2], bbox_3d [N,n,3], K [N,3,3] on the GPU -> poses [N,4,4] on the GPU ([R|t], zeros on failure) -- the corners never
+    leave the device ("next" row f3).  form="thread": `bd_solve_pnp`, one pose per thread in fp64.  form="wave": `bd_solve_pnp_wave`, one
+    wavefront per pose (same algorithm, same minimum); with want_rms=True it returns (poses, rms_px), rms_px [N] fp32 = root mean square
+    of the pixel reprojection error of each returned pose (0 where the solve failed)."""
+    if form not in PNP_DEVICE_FORMS:
+        raise ValueError(f"solve_poses_device: form must be one of {PNP_DEVICE_FORMS}, got {form!r}")
+    if want_rms and form != "wave":
+        raise ValueError("solve_poses_device: want_rms=True needs form='wave' (bd_solve_pnp has no rms_px output)")
     _lib.require_gpu()
     lib = _lib.load()
     kp = kp_px.float().contiguous()
@@ -93,6 +103,11 @@ def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tens
     Kd = K.to(kp.device).float().contiguous()
     n, npts = kp.shape[0], kp.shape[1]
     out = torch.empty((n, 4, 4), dtype=torch.float32, device=kp.device)
+    if form == "wave":
+        rms = torch.empty((n,), dtype=torch.float32, device=kp.device) if want_rms else None
+        _lib.check(lib.bd_solve_pnp_wave(_lib.ptr(kp), _lib.ptr(p3), _lib.ptr(Kd), n, npts, iters, _lib.ptr(out), _lib.ptr(rms),
+                                         _lib.stream()), "bd_solve_pnp_wave")
+        return (out, rms) if want_rms else out
     _lib.check(lib.bd_solve_pnp(_lib.ptr(kp), _lib.ptr(p3), _lib.ptr(Kd), n, npts, iters, _lib.ptr(out), _lib.stream()),
                "bd_solve_pnp")
     return out

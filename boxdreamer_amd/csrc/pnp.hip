@@ -6,6 +6,9 @@
 // poses) disappears from the serving loop.  The work is tiny (~2e5 flops per pose) and latency-bound: no attempt is
 // made to spread one pose over a wavefront.  PARITY against OpenCV is un-pinned (no cv2 in the image); the kernel is
 // tested against the numpy form, which it follows step by step.
+// That is the THREAD form (bd_solve_pnp): its per-thread arrays live in scratch memory and 32 poses are half a wavefront on one CU.  The
+// WAVE form (bd_solve_pnp_wave, pnp_wave_kernel below) gives every pose a wavefront and a workgroup of its own: the same algorithm with the
+// state in LDS, the 12 x 12 eigen-problem as 6 simultaneous rotations per step and the Jacobian's six perturbed poses side by side.
 #include "bd_common.h"
 #include <cmath>
 #include <thread>
@@ -278,6 +281,407 @@ __global__ __launch_bounds__(64) void pnp_kernel(const float* __restrict__ kp, c
     solve_one_pose(kp + (size_t)id * n * 2, pts3 + (size_t)id * n * 3, Kmat + (size_t)id * 9, n, iters, poses + (size_t)id * 16);
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// The wave form: ONE wavefront (64 lanes) per pose, solve_one_pose's algorithm step for step in fp64.  The solver is written as a
+// DRIVER (pnp_wave_solve) around PHASES.  A phase is a function of (lane, shared state): it reads what earlier phases left in the
+// shared state and writes locations no other lane of the same phase reads; `run(phase)` executes it on all 64 lanes between two
+// barriers.  Driver code between the phases is executed by every lane on the same shared values in the same order, so every lane holds
+// the same bits; the values that decide a branch or a loop exit go through run.uniform() (v_readfirstlane) on top of that.  Nothing is
+// indexed dynamically outside the shared state (LDS): the kernel has no scratch.  Every sum runs in index order without atomics, and a
+// workgroup is one pose, so a pose's bits do not depend on the batch.  On the host the same driver runs with a runner that loops over
+// the 64 lanes (tools/pnp_wave_hostcheck.cpp: the index arithmetic under the address / undefined-behaviour sanitizers, no GPU).
+struct WaveState {
+    double p4[MAXPTS * 4];            // (X, Y, Z, 1) per point
+    double p2n[MAXPTS * 2];           // normalised image coordinates
+    double A[2][144], V[2][144];      // Jacobi: read one copy, write the other
+    double cs[24];                    // per index i of the current Jacobi step: cc[i], ss[i]
+    double Rt[6][12];                 // [R | t] of the six perturbed poses
+    double r[2][MAXPTS * 2];          // residuals at x / at the candidate (the roles swap on an accepted step)
+    double J[MAXPTS * 2 * 6];
+    double Hg[27];                    // J^T J (21 distinct entries, upper triangle by rows), then g (6)
+    float out[16];
+};
+
+// partner of index i in step r (0..10) of the round-robin ordering of 12 indices: 6 disjoint pairs per step, every pair once per sweep
+__host__ __device__ inline int rr_partner(int i, int r) {
+    if (i == 11) return r;
+    if (i == r) return 11;
+    const int p = 2 * r - i;
+    return p < 0 ? p + 11 : (p >= 11 ? p - 11 : p);
+}
+// e-th entry (row-major) of the upper triangle, diagonal included, of an N x N matrix
+template <int N> __host__ __device__ inline void tri_entry(int e, int& i, int& j) {
+    i = 0;
+    for (int k = 0; k < N - 1; ++k)
+        if (e >= N - i) { e -= N - i; ++i; }
+    j = i + e;
+}
+
+__host__ __device__ inline void rvec_from_R_static(const double* R, double* rv) {      // rvec_from_R without a dynamic index
+    double c = (R[0] + R[4] + R[8] - 1.0) / 2.0;
+    c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+    const double th = acos(c);
+    if (th < 1e-8) { rv[0] = rv[1] = rv[2] = 0.0; return; }
+    if (3.14159265358979323846 - th < 1e-4) {
+        double A[9];
+        for (int i = 0; i < 9; ++i) A[i] = (R[i] + (i % 4 == 0 ? 1.0 : 0.0)) / 2.0;
+        int k = 0;
+        double dk = A[0];
+        if (A[4] > dk) { k = 1; dk = A[4]; }
+        if (A[8] > dk) { k = 2; dk = A[8]; }
+        const double d = sqrt(dk > 1e-12 ? dk : 1e-12);
+        for (int i = 0; i < 3; ++i) rv[i] = (k == 0 ? A[i * 3] : (k == 1 ? A[i * 3 + 1] : A[i * 3 + 2])) / d * th;
+        return;
+    }
+    const double f = th / (2.0 * sin(th));
+    rv[0] = (R[7] - R[5]) * f; rv[1] = (R[2] - R[6]) * f; rv[2] = (R[3] - R[1]) * f;
+}
+
+// solve6 with every index static (the pivot row is swapped in through selects): H, g, d stay in registers
+__host__ __device__ inline bool solve6_static(double (&H)[36], double (&g)[6], double (&d)[6]) {
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        int piv = c;
+        double best = fabs(H[c * 6 + c]);
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) if (fabs(H[r * 6 + c]) > best) { piv = r; best = fabs(H[r * 6 + c]); }
+        if (best < 1e-300) return false;
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const bool sw = piv == r;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { const double a = H[c * 6 + k], b = H[r * 6 + k]; H[c * 6 + k] = sw ? b : a; H[r * 6 + k] = sw ? a : b; }
+            const double a = g[c], b = g[r]; g[c] = sw ? b : a; g[r] = sw ? a : b;
+        }
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const double f = H[r * 6 + c] / H[c * 6 + c];
+#pragma unroll
+            for (int k = c; k < 6; ++k) H[r * 6 + k] -= f * H[c * 6 + k];
+            g[r] -= f * g[c];
+        }
+    }
+#pragma unroll
+    for (int r = 5; r >= 0; --r) {
+        double s = g[r];
+#pragma unroll
+        for (int k = r + 1; k < 6; ++k) s -= H[r * 6 + k] * d[k];
+        d[r] = s / H[r * 6 + r];
+    }
+    return true;
+}
+
+// One pose by one "wave" of 64 lanes.  Returns false where solve_one_pose leaves zeros; on success S.out holds the 4 x 4 pose and
+// *rms_out the root mean square of the PIXEL reprojection error of that pose (of its fp32 rounding, which is what the caller gets).  `run(f)` executes f(lane) for lane = 0 .. 63 with a
+// barrier before and after; `run.uniform(b)` returns b, the same in every lane.
+template <class Run>
+__host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, const float* kp, const float* pts3, const float* Kp, int n,
+                                               int iters, double* rms_out) {
+    const double fx = Kp[0], fy = Kp[4], cx = Kp[2], cy = Kp[5];
+    const int m = 2 * n;
+    // ---- 1. normalise: lane = point
+    run([&](int lane) {
+        if (lane >= n) return;
+        for (int c = 0; c < 3; ++c) S.p4[lane * 4 + c] = pts3[lane * 3 + c];
+        S.p4[lane * 4 + 3] = 1.0;
+        S.p2n[2 * lane] = ((double)kp[lane * 2] - cx) / fx;
+        S.p2n[2 * lane + 1] = ((double)kp[lane * 2 + 1] - cy) / fy;
+    });
+    bool ok = true;
+    double mean[3] = {0, 0, 0};
+    for (int i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) mean[c] += S.p4[i * 4 + c] / n;
+        ok = ok && finite_d(S.p2n[2 * i]) && finite_d(S.p2n[2 * i + 1]);
+    }
+    if (!run.uniform(ok)) return false;
+    // ---- 2. DLT: A^T A, a lane owns entries lane, lane + 64, lane + 128 and sums over the points in index order; V = I
+    run([&](int lane) {
+        for (int e = lane; e < 144; e += 64) {
+            const int a = e / 12, b = e % 12, ba = a / 4, bb = b / 4, ca = a % 4, cb = b % 4;
+            double s = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const double Xa = S.p4[i * 4 + ca], Xb = S.p4[i * 4 + cb], u = S.p2n[2 * i], v = S.p2n[2 * i + 1];
+                const double r1a = ba == 0 ? Xa : (ba == 2 ? -u * Xa : 0.0), r1b = bb == 0 ? Xb : (bb == 2 ? -u * Xb : 0.0);
+                const double r2a = ba == 1 ? Xa : (ba == 2 ? -v * Xa : 0.0), r2b = bb == 1 ? Xb : (bb == 2 ? -v * Xb : 0.0);
+                s += r1a * r1b + r2a * r2b;
+            }
+            S.A[0][e] = s;
+            S.V[0][e] = a == b ? 1.0 : 0.0;
+        }
+    });
+    // ---- Jacobi on the 12 x 12: round-robin ordering, the 6 disjoint rotations of a step applied at once (A <- J^T A J, V <- V J)
+    int cur = 0;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int i = 0; i < 12; ++i) {
+            diag += S.A[cur][i * 12 + i] * S.A[cur][i * 12 + i];
+            for (int j = i + 1; j < 12; ++j) off += S.A[cur][i * 12 + j] * S.A[cur][i * 12 + j];
+        }
+        if (run.uniform(off <= 1e-60 || off <= 1e-32 * diag)) break;
+        for (int step = 0; step < 11; ++step) {
+            run([&](int lane) {                       // rotation of the pair that index `lane` belongs to
+                if (lane >= 12) return;
+                const int ip = rr_partner(lane, step), p = lane < ip ? lane : ip, q = lane < ip ? ip : lane;
+                const double apq = S.A[cur][p * 12 + q];
+                double c = 1.0, s = 0.0;
+                if (apq != 0.0) {
+                    const double theta = (S.A[cur][q * 12 + q] - S.A[cur][p * 12 + p]) / (2.0 * apq);
+                    const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    c = 1.0 / sqrt(t * t + 1.0);
+                    s = t * c;
+                }
+                S.cs[2 * lane] = c;
+                S.cs[2 * lane + 1] = lane == p ? -s : s;
+            });
+            run([&](int lane) {
+                for (int e = lane; e < 78; e += 64) {            // A: upper triangle, mirrored
+                    int i, j;
+                    tri_entry<12>(e, i, j);
+                    const int ip = rr_partner(i, step), jp = rr_partner(j, step);
+                    const double ci = S.cs[2 * i], si = S.cs[2 * i + 1], cj = S.cs[2 * j], sj = S.cs[2 * j + 1];
+                    const double* A = S.A[cur];
+                    const double v = ci * (cj * A[i * 12 + j] + sj * A[i * 12 + jp]) + si * (cj * A[ip * 12 + j] + sj * A[ip * 12 + jp]);
+                    S.A[cur ^ 1][i * 12 + j] = v;
+                    S.A[cur ^ 1][j * 12 + i] = v;
+                }
+                for (int e = lane; e < 144; e += 64) {
+                    const int k = e / 12, j = e % 12, jp = rr_partner(j, step);
+                    S.V[cur ^ 1][e] = S.cs[2 * j] * S.V[cur][e] + S.cs[2 * j + 1] * S.V[cur][k * 12 + jp];
+                }
+            });
+            cur ^= 1;
+        }
+    }
+    int kmin = 0;
+    double wmin = S.A[cur][0];
+    for (int i = 1; i < 12; ++i) { const double w = S.A[cur][i * 12 + i]; if (w < wmin) { wmin = w; kmin = i; } }
+    double P[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) P[i] = S.V[cur][i * 12 + kmin];
+    // ---- 3. nearest rotation to M = P[:, :3] (every lane, in registers)
+    double M[9], MtM[9], V3[9], s2[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[i * 3 + j] = P[i * 4 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s += M[k * 3 + i] * M[k * 3 + j];
+            MtM[i * 3 + j] = s;
+        }
+    jacobi_eig<3>(MtM, V3, s2);
+    auto order = [&](int a, int b) {                           // descending: solve_one_pose's `ord` sort as compare-and-swaps
+        if (s2[b] > s2[a]) {
+            const double t = s2[a]; s2[a] = s2[b]; s2[b] = t;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { const double u = V3[i * 3 + a]; V3[i * 3 + a] = V3[i * 3 + b]; V3[i * 3 + b] = u; }
+        }
+    };
+    order(0, 1); order(0, 2); order(1, 2);
+    double sig[3], U[9];
+    const double* Vs = V3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sig[c] = sqrt(s2[c] > 0 ? s2[c] : 0.0);
+    if (!run.uniform(sig[2] > 0.0)) return false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s += M[i * 3 + k] * Vs[k * 3 + c];
+            U[i * 3 + c] = s / sig[c];
+        }
+    double R[9], t[3];
+    auto UVt = [&]() {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s += U[i * 3 + c] * Vs[j * 3 + c];
+                R[i * 3 + j] = s;
+            }
+    };
+    UVt();
+    // ---- 4. sign fixes
+    double scale = (sig[0] + sig[1] + sig[2]) / 3.0;
+    if (det3(R) < 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = -R[i];
+        scale = -scale;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = P[i * 4 + 3] / scale;
+    const double zc = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + t[2];
+    if (zc < 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = -R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = -t[i];
+        if (det3(R) < 0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) U[i * 3 + 2] = -U[i * 3 + 2];
+            UVt();
+        }
+    }
+    // ---- 5. / 6. Levenberg-Marquardt on (rvec, t)
+    double x[6];
+    rvec_from_R_static(R, x);
+    x[3] = t[0]; x[4] = t[1]; x[5] = t[2];
+    const double fgm = sqrt(fabs(fx * fy)), wx = fgm > 0 ? fabs(fx) / fgm : 1.0, wy = fgm > 0 ? fabs(fy) / fgm : 1.0;
+    int rb = 0;
+    double tr[3];
+    auto residuals_into = [&](int buf) {                       // lane = point: residuals of the pose (R, tr) into S.r[buf]
+        run([&](int lane) {
+            if (lane >= n) return;
+            const double X = S.p4[lane * 4], Y = S.p4[lane * 4 + 1], Z = S.p4[lane * 4 + 2];
+            const double pcx = R[0] * X + R[1] * Y + R[2] * Z + tr[0], pcy = R[3] * X + R[4] * Y + R[5] * Z + tr[1],
+                         pcz = R[6] * X + R[7] * Y + R[8] * Z + tr[2];
+            S.r[buf][2 * lane] = (pcx / pcz - S.p2n[2 * lane]) * wx;
+            S.r[buf][2 * lane + 1] = (pcy / pcz - S.p2n[2 * lane + 1]) * wy;
+        });
+    };
+    rodrigues(x, R);
+    tr[0] = x[3]; tr[1] = x[4]; tr[2] = x[5];
+    residuals_into(rb);
+    double e0 = 0.0;
+    bool fin = true;
+    for (int i = 0; i < m; ++i) { const double v = S.r[rb][i]; fin = fin && finite_d(v); e0 += v * v; }
+    if (!run.uniform(fin)) return false;
+    double lam = 1e-3;
+    bool fresh = true;                                         // x moved: J, J^T J and g are rebuilt (a rejected step keeps them)
+    for (int it = 0; it < iters; ++it) {
+        if (fresh) {
+            run([&](int lane) {                                // lanes 0 .. 5: [R | t] of x + h e_lane
+                double xd[6], Rd[9];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) xd[k] = x[k] + (k == lane ? 1e-6 : 0.0);
+                rodrigues(xd, Rd);
+                if (lane >= 6) return;
+#pragma unroll
+                for (int k = 0; k < 9; ++k) S.Rt[lane][k] = Rd[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) S.Rt[lane][9 + k] = xd[3 + k];
+            });
+            run([&](int lane) {                                // 6 perturbations x n points over the lanes
+                for (int w = lane; w < 6 * n; w += 64) {
+                    const int j = w / n, i = w - j * n;
+                    const double* Q = S.Rt[j];
+                    const double X = S.p4[i * 4], Y = S.p4[i * 4 + 1], Z = S.p4[i * 4 + 2];
+                    const double pcx = Q[0] * X + Q[1] * Y + Q[2] * Z + Q[9], pcy = Q[3] * X + Q[4] * Y + Q[5] * Z + Q[10],
+                                 pcz = Q[6] * X + Q[7] * Y + Q[8] * Z + Q[11];
+                    const double d0 = ((pcx / pcz - S.p2n[2 * i]) * wx - S.r[rb][2 * i]) / 1e-6;
+                    const double d1 = ((pcy / pcz - S.p2n[2 * i + 1]) * wy - S.r[rb][2 * i + 1]) / 1e-6;
+                    S.J[(2 * i) * 6 + j] = finite_d(d0) ? d0 : 0.0;
+                    S.J[(2 * i + 1) * 6 + j] = finite_d(d1) ? d1 : 0.0;
+                }
+            });
+            run([&](int lane) {                                // one lane per distinct entry of J^T J and of g, rows in index order
+                if (lane < 21) {
+                    int a, b;
+                    tri_entry<6>(lane, a, b);
+                    double h = 0.0;
+                    for (int i = 0; i < m; ++i) h += S.J[i * 6 + a] * S.J[i * 6 + b];
+                    S.Hg[lane] = h;
+                } else if (lane < 27) {
+                    const int a = lane - 21;
+                    double s = 0.0;
+                    for (int i = 0; i < m; ++i) s += S.J[i * 6 + a] * S.r[rb][i];
+                    S.Hg[lane] = -s;
+                }
+            });
+            fresh = false;
+        }
+        double H[36], g[6], stp[6];
+        {
+            int e = 0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a)
+#pragma unroll
+                for (int b = a; b < 6; ++b, ++e) { H[a * 6 + b] = S.Hg[e]; H[b * 6 + a] = S.Hg[e]; }
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a) { g[a] = S.Hg[21 + a]; H[a * 6 + a] += lam * (H[a * 6 + a] + 1e-12); }
+        if (!run.uniform(solve6_static(H, g, stp))) break;
+        double xn[6], e1 = 0.0, sn = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { xn[k] = x[k] + stp[k]; sn += stp[k] * stp[k]; }
+        rodrigues(xn, R);
+        tr[0] = xn[3]; tr[1] = xn[4]; tr[2] = xn[5];
+        residuals_into(rb ^ 1);
+        for (int i = 0; i < m; ++i) e1 += S.r[rb ^ 1][i] * S.r[rb ^ 1][i];      // (a non-finite residual makes e1 < e0 false)
+        if (run.uniform(e1 < e0)) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) x[k] = xn[k];
+            rb ^= 1;
+            e0 = e1;
+            lam = lam * 0.3 > 1e-9 ? lam * 0.3 : 1e-9;
+            fresh = true;
+            if (run.uniform(sqrt(sn) < 1e-10)) break;
+        } else {
+            lam *= 10.0;
+        }
+    }
+    rodrigues(x, R);
+    // ---- the pose, and its pixel reprojection error: lane = point, summed in index order
+    run([&](int lane) {
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) S.out[i * 4 + j] = (float)R[i * 3 + j];
+                S.out[i * 4 + 3] = (float)x[3 + i];
+                S.out[12 + i] = 0.f;
+            }
+            S.out[15] = 1.f;
+        }
+        if (lane >= n) return;
+        double Q[9], tq[3];                                    // the pose as it is returned: rounded to fp32
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Q[i] = (double)(float)R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tq[i] = (double)(float)x[3 + i];
+        const double X = S.p4[lane * 4], Y = S.p4[lane * 4 + 1], Z = S.p4[lane * 4 + 2];
+        const double pcx = Q[0] * X + Q[1] * Y + Q[2] * Z + tq[0], pcy = Q[3] * X + Q[4] * Y + Q[5] * Z + tq[1],
+                     pcz = Q[6] * X + Q[7] * Y + Q[8] * Z + tq[2];
+        const double du = (double)kp[lane * 2] - (fx * (pcx / pcz) + cx), dv = (double)kp[lane * 2 + 1] - (fy * (pcy / pcz) + cy);
+        S.r[rb ^ 1][lane] = du * du + dv * dv;
+    });
+    double ss = 0.0;
+    for (int i = 0; i < n; ++i) ss += S.r[rb ^ 1][i];
+    *rms_out = sqrt(ss / n);
+    return true;
+}
+
+struct WaveRun {
+    template <class F> __device__ __forceinline__ void operator()(F f) const {
+        __syncthreads();                        // one wave per workgroup: the wait for its own LDS traffic, and a fence
+        f((int)threadIdx.x);
+        __syncthreads();
+    }
+    __device__ __forceinline__ bool uniform(bool b) const { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+};
+
+// grid = n_poses, ONE wave per workgroup: a wave that shared a barrier with the waves of other poses could wait for ever on a pose
+// that needs fewer sweeps or LM iterations
+__global__ __launch_bounds__(64) void pnp_wave_kernel(const float* __restrict__ kp, const float* __restrict__ pts3,
+                                                      const float* __restrict__ Kmat, int n, int iters, float* __restrict__ poses,
+                                                      float* __restrict__ rms_px) {
+    __shared__ WaveState S;
+    const size_t id = blockIdx.x;
+    const int lane = threadIdx.x;
+    double rms = 0.0;
+    const bool ok = pnp_wave_solve(WaveRun(), S, kp + id * n * 2, pts3 + id * n * 3, Kmat + id * 9, n, iters, &rms);
+    if (lane < 16) poses[id * 16 + lane] = ok ? S.out[lane] : 0.f;
+    if (rms_px && lane == 0) rms_px[id] = ok ? (float)rms : 0.f;
+}
+
 }  // namespace
 
 // Host worker threads of bd_solve_pnp_host, kept between calls (round 6: starting seven std::threads per call was ~0.25 ms of the 0.36 ms
@@ -363,6 +767,17 @@ extern "C" int bd_solve_pnp(const float* kp_px, const float* pts3, const float* 
     if (n_poses <= 0 || n_points < 6 || n_points > MAXPTS || iters < 0) return BD_ERR_SHAPE;
     hipLaunchKernelGGL(pnp_kernel, dim3((n_poses + 63) / 64), dim3(64), 0, (hipStream_t)stream, kp_px, pts3, K, n_poses,
                        n_points, iters, poses);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+// The wave form: one wavefront and one workgroup per pose (pnp_wave_kernel).  rms_px (fp32 [n_poses], may be NULL): root mean square of the
+// pixel reprojection error of the returned pose over its n_points points, 0 where the solve fails.
+extern "C" int bd_solve_pnp_wave(const float* kp_px, const float* pts3, const float* K, int n_poses, int n_points, int iters,
+                                 float* poses, float* rms_px, void* stream) {
+    if (!kp_px || !pts3 || !K || !poses) return BD_ERR_NULL;
+    if (n_poses <= 0 || n_points < 6 || n_points > MAXPTS || iters < 0) return BD_ERR_SHAPE;
+    hipLaunchKernelGGL(pnp_wave_kernel, dim3(n_poses), dim3(64), 0, (hipStream_t)stream, kp_px, pts3, K, n_points, iters, poses, rms_px);
     BD_CHECK_LAUNCH();
     return BD_OK;
 }

@@ -50,7 +50,13 @@ class BoxDreamer(nn.Module):
         module_configs = validate_model_config(module_configs)
         self.bbox_representation = module_configs["bbox_representation"]
         self.dense_cfg = module_configs.get("dense_cfg", None)
-        self.pnp_on_device = bool(module_configs.get("pnp_on_device", False))
+        # False: host PnP (the default); True: bd_solve_pnp (one pose per thread); "wave": bd_solve_pnp_wave (one wavefront per pose)
+        self.pnp_on_device = module_configs.get("pnp_on_device", False)
+        if isinstance(self.pnp_on_device, str):
+            if self.pnp_on_device != "wave":
+                raise ValueError(f"config['modules']['pnp_on_device'] must be False, True or 'wave', got {self.pnp_on_device!r}")
+        else:
+            self.pnp_on_device = bool(self.pnp_on_device)
         module_configs, self.camera_dim, self.rotation_length = setup_camera_params(module_configs)
         self.module_configs = module_configs
 
@@ -562,8 +568,9 @@ class BoxDreamer(nn.Module):
         flag = (err if err is not None else torch.zeros((), dtype=torch.bool, device=kp_px.device)).float().reshape(1)
         # PnP stays on the host CPU (north_star; box_utils.py:139-199): OpenCV's solvePnP when cv2 is importable, else this repo's
         # restatement of its ITERATIVE algorithm -- whose parity against OpenCV is UN-PINNED in this image;
-        # `pose_solver` says which one produced `pred_poses`.  The HIP solver (bd_solve_pnp, row f3) is opt-in:
-        # config["modules"]["pnp_on_device"] = True (then only the mask verdict crosses to the host).
+        # `pose_solver` says which one produced `pred_poses`.  The HIP solver (row f3) is opt-in: config["modules"]["pnp_on_device"] =
+        # True (bd_solve_pnp, one pose per thread) or "wave" (bd_solve_pnp_wave, one wavefront per pose, which also leaves each pose's
+        # pixel reprojection RMS in data["pred_pose_rms_px"]); then only the mask verdict crosses to the host.
         def device_work_independent_of_the_poses():
             if behind_the_d2h is not None:
                 behind_the_d2h()
@@ -573,8 +580,12 @@ class BoxDreamer(nn.Module):
 
         if self.pnp_on_device:
             device_work_independent_of_the_poses()
-            poses = solve_poses_device(kp_px, bbox_3d, K)
-            data["pose_solver"] = "hip:bd_solve_pnp (DLT + LM, parity vs OpenCV un-pinned)"
+            if self.pnp_on_device == "wave":
+                poses, data["pred_pose_rms_px"] = solve_poses_device(kp_px, bbox_3d, K, form="wave", want_rms=True)
+                data["pose_solver"] = "hip:bd_solve_pnp_wave (one wavefront per pose, DLT + LM; parity vs OpenCV un-pinned)"
+            else:
+                poses = solve_poses_device(kp_px, bbox_3d, K)
+                data["pose_solver"] = "hip:bd_solve_pnp (DLT + LM, parity vs OpenCV un-pinned)"
             bad = bool(flag.item()) if err is not None else False
             if err is not None:
                 syncs.append("mask verdict D2H (4 bytes; pnp_on_device)")

@@ -358,9 +358,18 @@ int bd_render_corner_heatmaps(const float* corners, int n_groups, int group, int
  * the algorithm of cv2.solvePnP(SOLVEPNP_ITERATIVE) for non-planar points as restated in boxdreamer_amd/pnp.py
  * (replaces the per-sample host loop of src/models/utils/box_utils.py:139-199).  kp_px: fp32 [n_poses, n_points, 2] pixel
  * coordinates; pts3: fp32 [n_poses, n_points, 3]; K: fp32 [n_poses, 3, 3]; poses: fp32 [n_poses, 4, 4] = [R|t; 0 0 0 1],
- * all zeros where the solve fails.  6 <= n_points <= 64. */
+ * all zeros where the solve fails.  6 <= n_points <= 64.
+ * (One wavefront per pose instead of one thread: bd_solve_pnp_wave below.) */
 int bd_solve_pnp(const float* kp_px, const float* pts3, const float* K, int n_poses, int n_points, int iters,
                  float* poses, void* stream);
+/* The same solve with ONE WAVEFRONT per pose (grid = n_poses workgroups of 64 lanes, all state in LDS and registers, fp64, every sum
+ * in a fixed order: a pose's bits do not depend on n_poses or on its place in the batch); replaces the same per-sample host loop of
+ * src/models/utils/box_utils.py:139-199.  Same argument contract as bd_solve_pnp: 6 <= n_points <= 64, BD_ERR_NULL / BD_ERR_SHAPE
+ * before any launch, an all-zero 4 x 4 where the solve fails.  It lands on the same minimum as bd_solve_pnp[_host], not on the same
+ * bits (the 12 x 12 Jacobi runs in a round-robin order).  rms_px: fp32 [n_poses], may be NULL: root mean square over the n_points
+ * points of the PIXEL reprojection error sqrt(sum((u - u^)^2 + (v - v^)^2) / n_points) of the returned pose, 0 where it fails. */
+int bd_solve_pnp_wave(const float* kp_px, const float* pts3, const float* K, int n_poses, int n_points, int iters,
+                      float* poses, float* rms_px /* may be NULL */, void* stream);
 /* The same solver on the HOST (all pointers are host pointers, no GPU work): `n_threads` worker threads share the poses
  * (<= 0: one per 4 poses, at most 16).  The default pose solver of the facade when OpenCV is not importable -- the PnP post-solve
  * stays on the host CPU (north_star), without the per-sample Python loop of src/models/utils/box_utils.py:139-199. */
