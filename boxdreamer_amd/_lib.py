@@ -130,6 +130,7 @@ EXPORTS = [
     "bd_assemble_entry_tokens", "bd_decoder_entry_tokens_workspace_bytes", "bd_decoder_entry_tokens",
     "bd_decoder_entry_workspace_bytes", "bd_decoder_forward_entry", "bd_decoder_entry_workspace_bytes_ragged",
     "bd_decoder_forward_entry_ragged", "bd_solve_pnp_wave",
+    "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
 ]
 
 _lib = None
@@ -193,6 +194,10 @@ def load() -> C.CDLL:
     lib.bd_solve_pnp.argtypes = [vp, vp, vp, i, i, i, vp, vp]
     lib.bd_solve_pnp_host.argtypes = [vp, vp, vp, i, i, i, vp, i]
     lib.bd_solve_pnp_wave.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
+    lib.bd_solve_pnp_ransac_workspace_bytes.argtypes = [i, i]
+    lib.bd_solve_pnp_ransac_workspace_bytes.restype = sz
+    lib.bd_solve_pnp_ransac_wave.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, i, vp, vp, vp, vp, vp, sz, vp]
+    lib.bd_solve_pnp_ransac_host.argtypes = [vp, vp, vp, vp, i, i, i, f, f, i, i, vp, vp, vp, vp, i]
     lib.bd_pose_metrics_workspace_bytes.argtypes = [i, i]
     lib.bd_pose_metrics_workspace_bytes.restype = sz
     lib.bd_pose_metrics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp, vp]

@@ -113,6 +113,49 @@ def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tens
     return out
 
 
+RANSAC_MAX_ROUNDS = 8                  # 64 observations: MAXPTS of csrc/pnp.hip
+_PICKS = {}                            # (n_rounds, n_trials, seed, device) -> int32 [n_trials, 6] on that device
+
+
+def ransac_picks_device(n_rounds: int, n_trials: int, seed: int, device) -> torch.Tensor:
+    """pnp.ransac_picks on `device`, built once per (n_rounds, n_trials, seed, device)."""
+    key = (int(n_rounds), int(n_trials), int(seed), str(torch.device(device)))
+    if key not in _PICKS:
+        _PICKS[key] = torch.from_numpy(pnp.ransac_picks(n_rounds, n_trials, seed)).to(device)
+    return _PICKS[key]
+
+
+def solve_poses_ransac_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tensor, n_trials: int = 1000, reproj_err: float = 2.0,
+                              confidence: float = 0.99, seed: int = 0):
+    """RANSAC PnP of the dense multi-round mode on the GPU (`bd_solve_pnp_ransac_wave`: one wavefront per hypothesis, then one per sample).
+    kp_px [N, R, 8, 2] pixels (R <= 8 rounds of the same 8 corners), bbox_3d [N, 8, 3], K [N, 3, 3] ->
+    (poses [N, 4, 4] fp32, zeros on failure; inliers [N, R, 8] bool; rms_px [N] fp32 over the observations used; info [N, 4] int32 =
+    trials used, best hypothesis or -1, entries of the mask, path 0 = inliers / 1 = all observations / 2 = failed), all on the device.
+    Every sample runs the hypotheses of the same sampling table (pnp.ransac_picks(R, n_trials, seed)), kept on the device."""
+    kp = kp_px.float().contiguous()
+    if kp.dim() != 4 or kp.shape[2:] != (8, 2) or not 1 <= kp.shape[1] <= RANSAC_MAX_ROUNDS:
+        raise ValueError(f"solve_poses_ransac_device: kp_px must be [N, R, 8, 2] with 1 <= R <= {RANSAC_MAX_ROUNDS}, got {tuple(kp.shape)}")
+    dev = kp.device
+    N, R = kp.shape[:2]
+    b3 = bbox_3d.to(dev).float().contiguous()
+    Kd = K.to(dev).float().contiguous()
+    if b3.shape != (N, 8, 3) or Kd.shape != (N, 3, 3):
+        raise ValueError(f"solve_poses_ransac_device: bbox_3d {tuple(b3.shape)} / K {tuple(Kd.shape)} do not match {N} samples")
+    _lib.require_gpu()
+    lib = _lib.load()
+    picks = ransac_picks_device(R, n_trials, seed, dev)
+    poses = torch.empty((N, 4, 4), dtype=torch.float32, device=dev)
+    inl = torch.empty((N, R * 8), dtype=torch.uint8, device=dev)
+    rms = torch.empty((N,), dtype=torch.float32, device=dev)
+    info = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.bd_solve_pnp_ransac_workspace_bytes(N, int(n_trials)))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    _lib.check(lib.bd_solve_pnp_ransac_wave(_lib.ptr(kp), _lib.ptr(b3), _lib.ptr(Kd), _lib.ptr(picks), N, R, int(n_trials), float(reproj_err),
+                                            float(confidence), 5, 30, _lib.ptr(poses), _lib.ptr(inl), _lib.ptr(rms), _lib.ptr(info),
+                                            _lib.ptr(ws), ws_bytes, _lib.stream()), "bd_solve_pnp_ransac_wave")
+    return poses, inl.bool().reshape(N, R, 8), rms, info
+
+
 def recover_pose_from_bb8(bbox_feat, bbox_3d, K, bbox_representation="heatmap"):
     """box_utils.py:113-199: (poses [B,T,4,4], normalised corners [B,T,8,2])."""
     B, T = bbox_feat.shape[:2]

@@ -9,6 +9,7 @@
 // That is the THREAD form (bd_solve_pnp): its per-thread arrays live in scratch memory and 32 poses are half a wavefront on one CU.  The
 // WAVE form (bd_solve_pnp_wave, pnp_wave_kernel below) gives every pose a wavefront and a workgroup of its own: the same algorithm with the
 // state in LDS, the 12 x 12 eigen-problem as 6 simultaneous rotations per step and the Jacobian's six perturbed poses side by side.
+// The RANSAC form (bd_solve_pnp_ransac_wave, further below) runs that solver once per hypothesis: the dense multi-round pose.
 #include "bd_common.h"
 #include <cmath>
 #include <thread>
@@ -17,6 +18,8 @@
 #include <functional>
 #include <unistd.h>
 #include <vector>
+#include <memory>
+#include <climits>
 
 namespace {
 
@@ -373,10 +376,11 @@ __host__ __device__ inline bool solve6_static(double (&H)[36], double (&g)[6], d
 
 // One pose by one "wave" of 64 lanes.  Returns false where solve_one_pose leaves zeros; on success S.out holds the 4 x 4 pose and
 // *rms_out the root mean square of the PIXEL reprojection error of that pose (of its fp32 rounding, which is what the caller gets).  `run(f)` executes f(lane) for lane = 0 .. 63 with a
-// barrier before and after; `run.uniform(b)` returns b, the same in every lane.
+// barrier before and after; `run.uniform(b)` returns b, the same in every lane.  Rt64 (may be null): 12 doubles of the caller's, every
+// lane's own copy: the pose BEFORE its rounding to fp32, R row-major then t (the RANSAC scores its hypotheses with it).
 template <class Run>
 __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, const float* kp, const float* pts3, const float* Kp, int n,
-                                               int iters, double* rms_out) {
+                                               int iters, double* rms_out, double* Rt64 = nullptr) {
     const double fx = Kp[0], fy = Kp[4], cx = Kp[2], cy = Kp[5];
     const int m = 2 * n;
     // ---- 1. normalise: lane = point
@@ -629,6 +633,12 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
         }
     }
     rodrigues(x, R);
+    if (Rt64) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) Rt64[i] = R[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) Rt64[9 + i] = x[3 + i];
+    }
     // ---- the pose, and its pixel reprojection error: lane = point, summed in index order
     run([&](int lane) {
         if (lane == 0) {
@@ -680,6 +690,173 @@ __global__ __launch_bounds__(64) void pnp_wave_kernel(const float* __restrict__ 
     const bool ok = pnp_wave_solve(WaveRun(), S, kp + id * n * 2, pts3 + id * n * 3, Kmat + id * 9, n, iters, &rms);
     if (lane < 16) poses[id * 16 + lane] = ok ? S.out[lane] : 0.f;
     if (rms_px && lane == 0) rms_px[id] = ok ? (float)rms : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// RANSAC over the R x 8 corners of the dense multi-round mode (boxdreamer_amd/pnp.py: solve_pnp_ransac with a `picks` table), as two
+// stages around pnp_wave_solve.  Stage 1, one wave per (sample, trial): solve the trial's 6 picked observations, score every observation
+// of the sample against that pose.  Stage 2, one wave per sample: replay the host form's selection over the stored scores, then the
+// final solve on the chosen inliers.  Both are written against `run` like the solver itself, so the host runs the same code with a
+// loop over the lanes (LoopRun: bd_solve_pnp_ransac_host, tools/pnp_ransac_hostcheck.cpp).  Observation i of a sample is round i / 8,
+// corner i % 8.
+struct RansacObs {                    // the observations handed to pnp_wave_solve: a trial's 6, or the compacted inliers
+    float kp[MAXPTS * 2];
+    float p3[MAXPTS * 3];
+};
+struct RansacScore {                  // one hypothesis in the workspace
+    double err_sum;                   // sum of the inliers' pixel errors, in index order (+inf where the solve failed)
+    unsigned long long mask;          // bit i = observation i is an inlier
+    int32_t count;                    // inliers, -1 where the solve failed
+    int32_t pad;
+};
+
+template <class Run>
+__host__ __device__ inline void ransac_gather(const Run& run, RansacObs& G, const float* kp, const float* box, unsigned long long mask, int n_obs) {
+    run([&](int lane) {               // compaction in index order: the slot of an observation is the number of kept ones before it
+        if (lane >= n_obs || !((mask >> lane) & 1ull)) return;
+        const int k = __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+        G.kp[2 * k] = kp[2 * lane];
+        G.kp[2 * k + 1] = kp[2 * lane + 1];
+        for (int c = 0; c < 3; ++c) G.p3[3 * k + c] = box[(lane % 8) * 3 + c];
+    });
+}
+
+// Stage 1.  kp [n_obs, 2], box [8, 3], Kp [3, 3] of the sample; pick6: the trial's 6 observation indices (clamped into [0, n_obs)).
+// margin (host only, may be null): running minimum of |error - thr| over the scored observations.
+template <class Run>
+__host__ __device__ inline void ransac_hypothesis(const Run& run, WaveState& S, RansacObs& G, const float* kp, const float* box, const float* Kp,
+                                                  const int32_t* pick6, int n_obs, double thr, int iters, RansacScore* out, double* margin) {
+    run([&](int lane) {
+        if (lane >= 6) return;
+        int i = pick6[lane];
+        i = i < 0 ? 0 : (i >= n_obs ? n_obs - 1 : i);
+        G.kp[2 * lane] = kp[2 * i];
+        G.kp[2 * lane + 1] = kp[2 * i + 1];
+        for (int c = 0; c < 3; ++c) G.p3[3 * lane + c] = box[(i % 8) * 3 + c];
+    });
+    double Rt[12], rms = 0.0;
+    const bool ok = pnp_wave_solve(run, S, G.kp, G.p3, Kp, 6, iters, &rms, Rt);
+    int count = -1;
+    double tot = __builtin_inf();
+    unsigned long long mask = 0;
+    if (ok) {
+        const double fx = Kp[0], fy = Kp[4], cx = Kp[2], cy = Kp[5];
+        run([&](int lane) {           // lane = observation: pixel error of the fp64 pose; behind the camera is never an inlier
+            if (lane >= n_obs) return;
+            const float* b = box + (lane % 8) * 3;
+            const double X = b[0], Y = b[1], Z = b[2];
+            const double pcx = Rt[0] * X + Rt[1] * Y + Rt[2] * Z + Rt[9], pcy = Rt[3] * X + Rt[4] * Y + Rt[5] * Z + Rt[10],
+                         pcz = Rt[6] * X + Rt[7] * Y + Rt[8] * Z + Rt[11];
+            const double z = fabs(pcz) < 1e-12 ? 1e-12 : pcz;
+            const double du = pcx / z * fx + cx - (double)kp[2 * lane], dv = pcy / z * fy + cy - (double)kp[2 * lane + 1];
+            S.r[0][lane] = pcz > 0 ? sqrt(du * du + dv * dv) : __builtin_inf();
+        });
+        count = 0;
+        tot = 0.0;
+        for (int i = 0; i < n_obs; ++i) {
+            const double e = S.r[0][i];
+            if (e < thr) { ++count; tot += e; mask |= 1ull << i; }
+            if (margin && fabs(e - thr) < *margin) *margin = fabs(e - thr);
+        }
+    }
+    run([&](int lane) {
+        if (lane != 0) return;
+        out->err_sum = tot;
+        out->mask = mask;
+        out->count = count;
+        out->pad = 0;
+    });
+}
+
+// Stage 2.  sc: the sample's n_trials scores.  Outputs of the sample: pose [16], inl [n_obs], rms_px / info (may be null).
+template <class Run>
+__host__ __device__ inline void ransac_final(const Run& run, WaveState& S, RansacObs& G, const float* kp, const float* box, const float* Kp,
+                                             const RansacScore* sc, int n_obs, int n_trials, double confidence, int iters, float* pose,
+                                             unsigned char* inl, float* rms_px, int32_t* info) {
+    // ---- the selection of solve_pnp_ransac, batch by batch (32 trials): S.J is free here, [0, 64) counts and [64, 128) error sums
+    int best = -1, best_cnt = -1, trials = 0;
+    double best_err = __builtin_inf(), need = (double)n_trials;
+    const int n_batches = (n_trials + 31) / 32;
+    for (int b = 0; b < n_batches; ++b) {
+        const int h = n_trials - trials < 32 ? n_trials - trials : 32;
+        run([&](int lane) {
+            if (lane >= h) return;
+            S.J[lane] = (double)sc[trials + lane].count;
+            S.J[64 + lane] = sc[trials + lane].err_sum;
+        });
+        int bi = 0;
+        for (int i = 1; i < h; ++i) if (S.J[i] > S.J[bi]) bi = i;             // highest count, ties: lowest index
+        const int c = (int)S.J[bi];
+        const double e = S.J[64 + bi];
+        if (c > best_cnt || (c == best_cnt && e < best_err)) { best_cnt = c; best_err = e; best = trials + bi; }
+        trials += h;
+        const double w = (double)(best_cnt > 0 ? best_cnt : 0) / (double)n_obs;
+        bool stop = w >= 1.0;
+        if (!stop && w > 0.0) {                                               // trials for `confidence` at this inlier ratio
+            const double miss = 1.0 - w * w * w * w * w * w;
+            need = ceil(log(1.0 - confidence) / log(miss > 1e-300 ? miss : 1e-300));
+        }
+        stop = stop || !((double)trials < (need < (double)n_trials ? need : (double)n_trials));
+        if (run.uniform(stop)) break;
+    }
+    // ---- inliers of the best hypothesis, or every observation
+    const unsigned long long all = n_obs >= 64 ? ~0ull : (1ull << n_obs) - 1ull;
+    unsigned long long mask = best >= 0 ? sc[best].mask & all : 0ull;
+    run([&](int lane) {
+        if (lane < n_obs) S.r[0][lane] = finite_d((double)kp[2 * lane]) && finite_d((double)kp[2 * lane + 1]) ? 0.0 : 1.0;
+    });
+    bool finite = true;
+    for (int i = 0; i < n_obs; ++i) finite = finite && S.r[0][i] == 0.0;
+    unsigned corners = 0;
+    for (int r = 0; r < n_obs / 8; ++r) corners |= (unsigned)(mask >> (8 * r)) & 0xffu;
+    int path = (best_cnt < 6 || __builtin_popcount(corners) < 6 || !finite) ? 1 : 0;
+    path = run.uniform(path != 0) ? 1 : 0;
+    if (path) mask = all;
+    bool ok = false;
+    double rms = 0.0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        ransac_gather(run, G, kp, box, mask, n_obs);
+        ok = pnp_wave_solve(run, S, G.kp, G.p3, Kp, __builtin_popcountll(mask), iters, &rms);
+        if (ok || path) break;
+        path = 1;                                                             // the inliers' solve failed: every observation
+        mask = all;
+    }
+    if (!ok) { path = 2; mask = 0; }
+    run([&](int lane) {
+        if (lane < 16) pose[lane] = ok ? S.out[lane] : 0.f;
+        if (lane < n_obs) inl[lane] = (unsigned char)((mask >> lane) & 1ull);
+        if (lane != 0) return;
+        if (rms_px) *rms_px = ok ? (float)rms : 0.f;
+        if (info) { info[0] = trials; info[1] = best; info[2] = __builtin_popcountll(mask); info[3] = path; }
+    });
+}
+
+struct LoopRun {                      // the 64 lanes of a "wave" one after the other: the host form
+    template <class F> void operator()(F f) const { for (int lane = 0; lane < 64; ++lane) f(lane); }
+    bool uniform(bool b) const { return b; }
+};
+
+// grid = n_samples * n_trials workgroups of one wave; no atomics, no workgroup waits for another
+__global__ __launch_bounds__(64) void pnp_ransac_hyp_kernel(const float* __restrict__ kp, const float* __restrict__ box,
+                                                            const float* __restrict__ Kmat, const int32_t* __restrict__ picks, int n_obs,
+                                                            int n_trials, double thr, int iters, RansacScore* __restrict__ ws) {
+    __shared__ WaveState S;
+    __shared__ RansacObs G;
+    const size_t id = blockIdx.x, s = id / (size_t)n_trials, t = id % (size_t)n_trials;
+    ransac_hypothesis(WaveRun(), S, G, kp + s * n_obs * 2, box + s * 24, Kmat + s * 9, picks + t * 6, n_obs, thr, iters, ws + id, nullptr);
+}
+
+// grid = n_samples workgroups of one wave
+__global__ __launch_bounds__(64) void pnp_ransac_final_kernel(const float* __restrict__ kp, const float* __restrict__ box,
+                                                              const float* __restrict__ Kmat, const RansacScore* __restrict__ ws, int n_obs,
+                                                              int n_trials, double confidence, int iters, float* __restrict__ poses,
+                                                              unsigned char* __restrict__ inliers, float* __restrict__ rms_px,
+                                                              int32_t* __restrict__ info) {
+    __shared__ WaveState S;
+    __shared__ RansacObs G;
+    const size_t s = blockIdx.x;
+    ransac_final(WaveRun(), S, G, kp + s * n_obs * 2, box + s * 24, Kmat + s * 9, ws + s * (size_t)n_trials, n_obs, n_trials, confidence, iters,
+                 poses + s * 16, inliers + s * n_obs, rms_px ? rms_px + s : nullptr, info ? info + s * 4 : nullptr);
 }
 
 }  // namespace
@@ -779,5 +956,77 @@ extern "C" int bd_solve_pnp_wave(const float* kp_px, const float* pts3, const fl
     if (n_poses <= 0 || n_points < 6 || n_points > MAXPTS || iters < 0) return BD_ERR_SHAPE;
     hipLaunchKernelGGL(pnp_wave_kernel, dim3(n_poses), dim3(64), 0, (hipStream_t)stream, kp_px, pts3, K, n_points, iters, poses, rms_px);
     BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+// RANSAC PnP over the n_rounds x 8 corners of the dense multi-round mode (replaces the cv2.solvePnPRansac call and its per-sample
+// loop, src/models/utils/box_utils.py:202-300): pnp_ransac_hyp_kernel scores n_samples x n_trials hypotheses into the workspace,
+// pnp_ransac_final_kernel selects and solves per sample.
+namespace {
+int ransac_args(const void* kp, const void* box, const void* K, const void* picks, const void* poses, const void* inliers, int n_samples,
+                int n_rounds, int n_trials, int hyp_iters, int final_iters) {
+    if (!kp || !box || !K || !picks || !poses || !inliers) return BD_ERR_NULL;
+    if (n_samples <= 0 || n_rounds < 1 || n_rounds * 8 > MAXPTS || n_trials <= 0 || hyp_iters < 0 || final_iters < 0) return BD_ERR_SHAPE;
+    if ((int64_t)n_samples * n_trials > INT_MAX) return BD_ERR_SHAPE;
+    return BD_OK;
+}
+}  // namespace
+
+extern "C" size_t bd_solve_pnp_ransac_workspace_bytes(int n_samples, int n_trials) {
+    if (n_samples <= 0 || n_trials <= 0) return 0;
+    return (size_t)n_samples * (size_t)n_trials * sizeof(RansacScore);
+}
+
+extern "C" int bd_solve_pnp_ransac_wave(const float* kp_px, const float* bbox_3d, const float* K, const int32_t* picks, int n_samples,
+                                        int n_rounds, int n_trials, float reproj_err, float confidence, int hyp_iters, int final_iters,
+                                        float* poses, unsigned char* inliers, float* rms_px, int32_t* info, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    const int rc = ransac_args(kp_px, bbox_3d, K, picks, poses, inliers, n_samples, n_rounds, n_trials, hyp_iters, final_iters);
+    if (rc != BD_OK) return rc;
+    if (!workspace) return BD_ERR_NULL;
+    if (workspace_bytes < bd_solve_pnp_ransac_workspace_bytes(n_samples, n_trials)) return BD_ERR_SHAPE;
+    RansacScore* ws = (RansacScore*)workspace;
+    hipLaunchKernelGGL(pnp_ransac_hyp_kernel, dim3(n_samples * n_trials), dim3(64), 0, (hipStream_t)stream, kp_px, bbox_3d, K, picks,
+                       n_rounds * 8, n_trials, (double)reproj_err, hyp_iters, ws);
+    BD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(pnp_ransac_final_kernel, dim3(n_samples), dim3(64), 0, (hipStream_t)stream, kp_px, bbox_3d, K,
+                       (const RansacScore*)ws, n_rounds * 8, n_trials, (double)confidence, final_iters, poses, inliers, rms_px, info);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+// The same two stages on the HOST through the loop runner (all pointers are host pointers): the hypotheses, then the samples, dealt out
+// in contiguous chunks to the worker pool of bd_solve_pnp_host.  n_threads <= 0: at most 16.
+extern "C" int bd_solve_pnp_ransac_host(const float* kp_px, const float* bbox_3d, const float* K, const int32_t* picks, int n_samples,
+                                        int n_rounds, int n_trials, float reproj_err, float confidence, int hyp_iters, int final_iters,
+                                        float* poses, unsigned char* inliers, float* rms_px, int32_t* info, int n_threads) {
+    const int rc = ransac_args(kp_px, bbox_3d, K, picks, poses, inliers, n_samples, n_rounds, n_trials, hyp_iters, final_iters);
+    if (rc != BD_OK) return rc;
+    const int n_obs = n_rounds * 8, total = n_samples * n_trials;
+    std::vector<RansacScore> ws((size_t)total);
+    RansacScore* wsp = ws.data();
+    int nt = n_threads > 0 ? n_threads : 16;
+    nt = nt > 16 ? 16 : nt;
+    auto stage = [&](int items, const std::function<void(int, WaveState&, RansacObs&)>& item) {
+        const int n = nt > items ? items : nt;
+        auto work = [&, n](int t) {
+            std::unique_ptr<WaveState> S(new WaveState());
+            std::unique_ptr<RansacObs> G(new RansacObs());
+            const int lo = (int)((int64_t)items * t / n), hi = (int)((int64_t)items * (t + 1) / n);
+            for (int i = lo; i < hi; ++i) item(i, *S, *G);
+        };
+        if (n <= 1) work(0); else host_pool_run(n, work);
+    };
+    stage(total, [&](int id, WaveState& S, RansacObs& G) {
+        const size_t s = (size_t)(id / n_trials), t = (size_t)(id % n_trials);
+        ransac_hypothesis(LoopRun(), S, G, kp_px + s * n_obs * 2, bbox_3d + s * 24, K + s * 9, picks + t * 6, n_obs, (double)reproj_err,
+                          hyp_iters, wsp + id, nullptr);
+    });
+    stage(n_samples, [&](int i, WaveState& S, RansacObs& G) {
+        const size_t s = (size_t)i;
+        ransac_final(LoopRun(), S, G, kp_px + s * n_obs * 2, bbox_3d + s * 24, K + s * 9, wsp + s * (size_t)n_trials, n_obs, n_trials,
+                     (double)confidence, final_iters, poses + s * 16, inliers + s * n_obs, rms_px ? rms_px + s : nullptr,
+                     info ? info + s * 4 : nullptr);
+    });
     return BD_OK;
 }

@@ -13,7 +13,9 @@ HIP (csrc/match.hip: one pass over the patch features per view, closed form of t
 the top-k selection; the decoder rounds reuse BETR unchanged.  View selection / re-packing of the batch tensors is torch
 indexing on the device (plumbing).  Pose recovery inside the multi-round mode goes through the host RANSAC PnP (pnp.solve_pnp_ransac:
 the reference's cv2.solvePnPRansac call where cv2 imports, a restatement of the scheme otherwise), whose parity against OpenCV is
-un-pinned in this image.
+un-pinned in this image.  With `pnp_on_device: "wave"` and at most 8 rounds the same scheme runs in HIP instead
+(csrc/pnp.hip: bd_solve_pnp_ransac_wave, one wavefront per hypothesis): corners, box, K and the coarse pose stay on the device;
+data["dense_pose_solver"] names what ran, data["dense_pose_inliers"] / data["dense_pose_rms_px"] say which rounds it kept.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, pnp
-from .box_utils import recover_bb8_corners_chw
+from .box_utils import RANSAC_MAX_ROUNDS, recover_bb8_corners_chw, solve_poses_ransac_device
 
 
 def _get(cfg, key, default=None):
@@ -207,21 +209,36 @@ def fetch_neighbors_by_pose_similarity(gt_poses, pred_pose, topk=5):
     return torch.topk(dist, k=topk, dim=1, largest=False)[1]
 
 
-def recover_pose_from_dense_bb8(query_rets, bbox_3d, K):
+DENSE_SOLVER_HOST = "host:pnp.solve_pnp_ransac (cv2.solvePnPRansac where importable, else its scheme restated; parity vs OpenCV un-pinned)"
+DENSE_SOLVER_WAVE = "hip:bd_solve_pnp_ransac_wave (one wavefront per hypothesis, DLT + LM; parity vs OpenCV un-pinned)"
+
+
+def recover_pose_from_dense_bb8(query_rets, bbox_3d, K, pnp_on_device=False, n_trials=1000, record=None):
     """query_rets (B, R, 8, H, W) heatmaps of R decoder rounds; bbox_3d (B, 8, 3); K (B, 3, 3).  All R*8 decoded corners of
     a sample go into one RANSAC PnP (box_utils.py:202-300: solvePnPRansac at 2 px / 0.99 / 1000 trials, ITERATIVE on failure --
     pnp.solve_pnp_ransac: cv2's own call where importable, else this repo's restatement of the scheme): a round whose corners are off
     is rejected instead of pulling the coarse pose (and with it the fine level's neighbour choice).  Returns poses (B, 1, 4, 4),
-    normalised corners (B, R, 8, 2)."""
+    normalised corners (B, R, 8, 2).  pnp_on_device == "wave" with R <= 8: the HIP form of the scheme (bd_solve_pnp_ransac_wave), nothing
+    leaves the device.  record (a dict, e.g. the batch dict): gets dense_pose_solver, dense_pose_inliers (B, R, 8) bool and
+    dense_pose_rms_px (B,), both on the device."""
     B, R = query_rets.shape[:2]
     norm_kp, kp_px, _ = recover_bb8_corners_chw(query_rets.reshape(B * R, *query_rets.shape[2:]))
+    dev = query_rets.device
+    if pnp_on_device == "wave" and R <= RANSAC_MAX_ROUNDS:
+        poses, inl, rms, _ = solve_poses_ransac_device(kp_px.reshape(B, R, 8, 2), bbox_3d, K, n_trials=n_trials, reproj_err=2.0,
+                                                       confidence=0.99)
+        if record is not None:
+            record["dense_pose_solver"], record["dense_pose_inliers"], record["dense_pose_rms_px"] = DENSE_SOLVER_WAVE, inl, rms
+        return poses.reshape(B, 1, 4, 4), norm_kp.reshape(B, R, 8, 2)
     kp = kp_px.reshape(B, R * 8, 2).cpu().numpy()
     b3 = bbox_3d.float().cpu().numpy()
     Kh = K.float().cpu().numpy()
     poses = np.zeros((B, 1, 4, 4), np.float32)
+    inl = np.zeros((B, R * 8), bool)
+    rms = np.zeros((B,), np.float32)
     for b in range(B):
         try:
-            ok, Rm, t, _ = pnp.solve_pnp_ransac(np.tile(b3[b], (R, 1)), kp[b], Kh[b], reproj_err=2.0, confidence=0.99, max_trials=1000, seed=b)
+            ok, Rm, t, m = pnp.solve_pnp_ransac(np.tile(b3[b], (R, 1)), kp[b], Kh[b], reproj_err=2.0, confidence=0.99, max_trials=n_trials, seed=b)
         except Exception as e:  # noqa: BLE001
             print(f"PnP failed due to exception: {e}")
             continue
@@ -229,14 +246,25 @@ def recover_pose_from_dense_bb8(query_rets, bbox_3d, K):
             poses[b, 0, :3, :3] = Rm
             poses[b, 0, :3, 3] = t
             poses[b, 0, 3, 3] = 1.0
-    return torch.from_numpy(poses).to(query_rets.device), norm_kp.reshape(B, R, 8, 2)
+            inl[b] = m
+            if record is not None and m.any():
+                p3 = np.tile(b3[b], (R, 1)).astype(np.float64)
+                err = pnp._reproj_px(Rm, t, p3[m], kp[b][m].astype(np.float64), Kh[b].astype(np.float64))
+                rms[b] = np.sqrt(np.mean(err * err))
+    if record is not None:
+        record["dense_pose_solver"] = DENSE_SOLVER_HOST
+        record["dense_pose_inliers"] = torch.from_numpy(inl.reshape(B, R, 8)).to(dev)
+        record["dense_pose_rms_px"] = torch.from_numpy(rms).to(dev)
+    return torch.from_numpy(poses).to(dev), norm_kp.reshape(B, R, 8, 2)
 
 
 def process_multi_round(data, pose_feat, frames, camera_mask, rgb_feature, image_masks, decoder, dense_cfg,
-                        bbox_representation="heatmap"):
+                        bbox_representation="heatmap", pnp_on_device=False):
     """Decoder over sub-batches of the references (query appended to each), one PnP over all rounds' corners, optional
     fine round on the references nearest to that pose.  Returns the decoder output of the fine round (tensor) or, without
-    it, the batch dict with the coarse prediction (as the reference does)."""
+    it, the batch dict with the coarse prediction (as the reference does).  pnp_on_device: the model's setting; "wave" runs that PnP
+    on the device when there are at most 8 rounds (recover_pose_from_dense_bb8).  dense_cfg.ransac_trials (optional): its trial count,
+    default 1000 (the reference's iterationsCount)."""
     B = frames.shape[0]
     poses = data["poses"].clone()
     K = data["non_ndc_intrinsics"].clone()
@@ -261,7 +289,9 @@ def process_multi_round(data, pose_feat, frames, camera_mask, rgb_feature, image
             feats = feats.reshape(B * R, *nrf.shape[2:])
         flat = decoder(npf.reshape(B * R, *npf.shape[2:]), nfr.reshape(B * R, *nfr.shape[2:]), ncm.reshape(B * R, -1), feats, None)
         query_rets = flat.reshape(B, R, *flat.shape[1:])
-    query_poses, pred_proj = recover_pose_from_dense_bb8(query_rets, bbox_3d[camera_mask], K[camera_mask])
+    trials = _get(dense_cfg, "ransac_trials")
+    query_poses, pred_proj = recover_pose_from_dense_bb8(query_rets, bbox_3d[camera_mask], K[camera_mask], pnp_on_device=pnp_on_device,
+                                                         n_trials=1000 if trials is None else int(trials), record=data)
     if _get(dense_cfg, "fine_level"):
         idx = fetch_neighbors_by_pose_similarity(poses[~camera_mask].reshape(B, poses.shape[1] - 1, 4, 4), query_poses,
                                                  topk=int(_get(dense_cfg, "fine_topk")))

@@ -326,7 +326,7 @@ class BoxDreamer(nn.Module):
                     data, pose_feat, images, camera_mask, rgb_feature, None, self.dense_cfg)
                 if _get(self.dense_cfg, "multi_round", False):
                     query_ret = process_multi_round(data, pose_feat, images, camera_mask, rgb_feature, None, self.decoder,
-                                                    self.dense_cfg, self.bbox_representation)
+                                                    self.dense_cfg, self.bbox_representation, pnp_on_device=self.pnp_on_device)
                     if isinstance(query_ret, dict):                                   # coarse prediction only: dict is final
                         return query_ret
                 else:

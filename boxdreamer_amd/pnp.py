@@ -244,6 +244,8 @@ def solve_pnp_batched(p3: np.ndarray, p2: np.ndarray, K: np.ndarray, iters: int 
 # Hypotheses are generated and scored in vectorised batches (solve_pnp_batched).  Sampling is deterministic (a Philox counter stream
 # keyed by `seed`): the same corners give the same pose on every box.  OpenCV's own sampler / minimal solver (EPnP on 5 points) are NOT
 # reproduced: parity against its binary is un-pinned, like the rest of this file.
+# The device form (csrc/pnp.hip: bd_solve_pnp_ransac_wave) runs the same scheme from a sampling table (ransac_picks) instead of draws made
+# batch by batch; solve_pnp_ransac(picks=...) is its numpy twin on the same hypotheses, solve_pnp_ransac_native its code run on the host.
 
 def _reproj_px(R, t, p3, p2, K):
     pc = p3 @ np.swapaxes(R, -1, -2) + t[..., None, :]
@@ -253,9 +255,32 @@ def _reproj_px(R, t, p3, p2, K):
     return np.where(z[..., 0] > 0, err, np.inf)            # a point behind the camera is never an inlier
 
 
+def ransac_picks(n_rounds: int, n_trials: int, seed: int = 0) -> np.ndarray:
+    """The sampling table of the RANSAC over n_rounds x 8 corners, int32 [n_trials, 6]: observation i is round i // 8, corner i % 8; a
+    trial draws 6 distinct corners of the 8 and a round for each, an entry is round * 8 + corner.  It depends on (n_rounds, n_trials,
+    seed) only, never on the corners: the device form (csrc/pnp.hip: bd_solve_pnp_ransac_wave) and solve_pnp_ransac(picks=...) run the
+    same hypotheses from it."""
+    n_rounds, n_trials = int(n_rounds), int(n_trials)
+    if n_rounds < 1 or n_trials < 1:
+        raise ValueError(f"ransac_picks: n_rounds and n_trials must be >= 1, got {n_rounds}, {n_trials}")
+    rng = np.random.Generator(np.random.Philox(key=int(seed) & 0xFFFFFFFFFFFFFFFF))
+    corners = np.argsort(rng.random((n_trials, 8)), axis=1)[:, :6]
+    rounds = rng.integers(0, n_rounds, size=(n_trials, 6))
+    return np.ascontiguousarray(rounds * 8 + corners, dtype=np.int32)
+
+
 def solve_pnp_ransac(p3: np.ndarray, p2: np.ndarray, K: np.ndarray, reproj_err: float = 2.0, confidence: float = 0.99,
-                     max_trials: int = 1000, seed: int = 0, batch: int = 32):
-    """(success, R (3,3), t (3,), inlier mask (n,) bool).  p3 (n,3) may repeat 3-D points (several 2-D observations of one corner)."""
+                     max_trials: int = 1000, seed: int = 0, batch: int = 32, picks=None, want_trials: bool = False):
+    """(success, R (3,3), t (3,), inlier mask (n,) bool).  p3 (n,3) may repeat 3-D points (several 2-D observations of one corner).
+    picks (int [>= max_trials, 6] observation indices, e.g. ransac_picks): the hypotheses' samples instead of this function's own draws
+    (the cv2 branch has its own sampler and ignores them).  want_trials=True appends the number of trials that were run."""
+    if want_trials:
+        count = []
+        return (*_solve_pnp_ransac(p3, p2, K, reproj_err, confidence, max_trials, seed, batch, picks, count), sum(count))
+    return _solve_pnp_ransac(p3, p2, K, reproj_err, confidence, max_trials, seed, batch, picks, None)
+
+
+def _solve_pnp_ransac(p3, p2, K, reproj_err, confidence, max_trials, seed, batch, picks, count):
     p3 = np.asarray(p3, np.float64)
     p2 = np.asarray(p2, np.float64)
     K = np.asarray(K, np.float64)
@@ -285,8 +310,11 @@ def solve_pnp_ransac(p3: np.ndarray, p2: np.ndarray, K: np.ndarray, reproj_err: 
     trials, need = 0, max_trials
     while trials < min(need, max_trials):
         h = min(batch, max_trials - trials)
-        corners = np.argsort(rng.random((h, n_corners)), axis=1)[:, :S]               # S distinct corners per hypothesis
-        pick = np.stack([[obs[c][int(rng.integers(len(obs[c])))] for c in row] for row in corners])      # one observation of each
+        if picks is not None:
+            pick = np.asarray(picks)[trials:trials + h]
+        else:
+            corners = np.argsort(rng.random((h, n_corners)), axis=1)[:, :S]           # S distinct corners per hypothesis
+            pick = np.stack([[obs[c][int(rng.integers(len(obs[c])))] for c in row] for row in corners])      # one observation of each
         ok, R, t = solve_pnp_batched(p3[pick], p2[pick], np.broadcast_to(K, (h, 3, 3)), iters=5)
         err = _reproj_px(R, t, p3[None], p2[None], K)                                     # (h, n)
         inl = err < reproj_err
@@ -296,6 +324,8 @@ def solve_pnp_ransac(p3: np.ndarray, p2: np.ndarray, K: np.ndarray, reproj_err: 
             if cnt[i] > best_cnt or (cnt[i] == best_cnt and tot[i] < best_err):
                 best_cnt, best_err, best_mask = int(cnt[i]), float(tot[i]), inl[i].copy()
         trials += h
+        if count is not None:
+            count.append(h)
         w = max(best_cnt, 0) / n
         if w >= 1.0:
             break
@@ -309,3 +339,27 @@ def solve_pnp_ransac(p3: np.ndarray, p2: np.ndarray, K: np.ndarray, reproj_err: 
         ok, R, t = solve_pnp_iterative(p3, p2, K)
         return ok, R, t, np.ones(n, bool)
     return True, R, t, best_mask
+
+
+def solve_pnp_ransac_native(kp_px, bbox_3d, K, picks, reproj_err: float = 2.0, confidence: float = 0.99, hyp_iters: int = 5,
+                            final_iters: int = 30, workers: int = 0):
+    """The two-stage RANSAC of the HIP library on the HOST (csrc/pnp.hip: bd_solve_pnp_ransac_host -- the code of the device form run
+    through a loop over the lanes, on the worker pool of bd_solve_pnp_host).  kp_px [N, R, 8, 2] pixels, bbox_3d [N, 8, 3], K [N, 3, 3],
+    picks int32 [n_trials, 6] (ransac_picks) -> (poses [N, 4, 4] fp32, zeros on failure; inliers [N, R * 8] bool; rms_px [N] fp32;
+    info [N, 4] int32 = trials used, best hypothesis or -1, entries of the mask, path 0 = inliers / 1 = all observations / 2 = failed).
+    Not the default host path (solve_pnp_ransac is): the twin the device form is tested against."""
+    from . import _lib
+    lib = _lib.load()
+    kp, b3, Kh = (np.ascontiguousarray(a, np.float32) for a in (kp_px, bbox_3d, K))
+    pk = np.ascontiguousarray(picks, np.int32)
+    N, R = kp.shape[0], kp.shape[1]
+    if kp.shape != (N, R, 8, 2) or b3.shape != (N, 8, 3) or Kh.shape != (N, 3, 3) or pk.ndim != 2 or pk.shape[1] != 6:
+        raise ValueError(f"solve_pnp_ransac_native: shapes {kp.shape}, {b3.shape}, {Kh.shape}, {pk.shape}")
+    poses = np.zeros((N, 4, 4), np.float32)
+    inl = np.zeros((N, R * 8), np.uint8)
+    rms = np.zeros((N,), np.float32)
+    info = np.zeros((N, 4), np.int32)
+    _lib.check(lib.bd_solve_pnp_ransac_host(kp.ctypes.data, b3.ctypes.data, Kh.ctypes.data, pk.ctypes.data, N, R, pk.shape[0],
+                                            float(reproj_err), float(confidence), int(hyp_iters), int(final_iters), poses.ctypes.data,
+                                            inl.ctypes.data, rms.ctypes.data, info.ctypes.data, int(workers)), "bd_solve_pnp_ransac_host")
+    return poses, inl.astype(bool), rms, info

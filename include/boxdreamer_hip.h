@@ -376,6 +376,42 @@ int bd_solve_pnp_wave(const float* kp_px, const float* pts3, const float* K, int
 int bd_solve_pnp_host(const float* kp_px /*[host]*/, const float* pts3 /*[host]*/, const float* K /*[host]*/, int n_poses, int n_points,
                       int iters, float* poses /*[host]*/, int n_threads);
 
+/* RANSAC PnP over the n_rounds x 8 corners of the dense multi-round mode, on the GPU (additive in ABI 9): replaces the
+ * cv2.solvePnPRansac call, its ITERATIVE fall-back and the per-sample host loop around them, src/models/utils/box_utils.py:202-300.
+ * Observation i of a sample is round i / 8, corner i % 8 (n_rounds * 8 <= 64).  Two launches on `stream`:
+ *   pnp_ransac_hyp_kernel    n_samples * n_trials workgroups of one wavefront: the trial's 6 picked observations are solved with
+ *                            bd_solve_pnp_wave's solver (hyp_iters LM iterations; the host scheme uses 5), every observation is scored by its
+ *                            fp64 pixel error against reproj_err (a point behind the camera is never an inlier); per hypothesis the
+ *                            workspace gets the inlier count (-1: solve failed), the inliers' error sum in index order and a 64-bit mask;
+ *   pnp_ransac_final_kernel  one wavefront per sample: the selection of boxdreamer_amd/pnp.py solve_pnp_ransac in batches of 32 trials
+ *                            (a batch's best = highest count, ties to the lowest index; it replaces the running best on a higher count
+ *                            or an equal count with a lower error sum; need = ceil(log(1 - confidence) / log(max(1 - w^6, 1e-300)))
+ *                            at inlier ratio w; stop at trials >= min(need, n_trials) or w >= 1), then the solve (final_iters; 30 in the
+ *                            host scheme) of the best hypothesis' inliers compacted in index order -- of ALL observations when the best count
+ *                            is below 6, the inliers cover fewer than 6 distinct corners, an observation is not finite, or that solve fails.
+ * No atomics, no workgroup waits for another, every sum in index order: a sample's bits depend neither on n_samples nor on its row.
+ * picks: DEVICE int32 [n_trials, 6] observation indices (boxdreamer_amd/pnp.py: ransac_picks); an entry outside [0, n_rounds * 8) is
+ * clamped into it.  poses: fp32 [n_samples, 4, 4], zeros on failure; inliers: uint8 [n_samples, n_rounds * 8], the observations the pose was
+ * solved on (all zero on failure); rms_px (may be NULL): fp32 [n_samples], pixel RMS of the pose over those observations, 0 on failure;
+ * info (may be NULL): int32 [n_samples, 4] = trials used, index of the best hypothesis or -1, set entries of `inliers`, path
+ * (0 = inliers, 1 = all observations, 2 = failed).  workspace: bd_solve_pnp_ransac_workspace_bytes(n_samples, n_trials) device bytes.
+ * Before any launch: BD_ERR_NULL for a NULL pointer other than rms_px / info; BD_ERR_SHAPE for n_samples <= 0, n_rounds outside
+ * [1, 8], n_trials <= 0, negative iteration counts, n_samples * n_trials above INT_MAX or a workspace that is too small.
+ * Parity against OpenCV's solvePnPRansac (its own sampler and minimal solver) is un-pinned, like the host form's. */
+size_t bd_solve_pnp_ransac_workspace_bytes(int n_samples, int n_trials);
+int bd_solve_pnp_ransac_wave(const float* kp_px /* [n_samples, n_rounds, 8, 2] */, const float* bbox_3d /* [n_samples, 8, 3] */,
+                             const float* K /* [n_samples, 3, 3] */, const int32_t* picks /* device [n_trials, 6] */, int n_samples,
+                             int n_rounds, int n_trials, float reproj_err, float confidence, int hyp_iters, int final_iters, float* poses,
+                             unsigned char* inliers /* [n_samples, n_rounds * 8] */, float* rms_px /* may be NULL */,
+                             int32_t* info /* [n_samples, 4], may be NULL */, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two stages on the HOST (all pointers are host pointers, no GPU work, no workspace): the lanes of a wavefront run in a loop,
+ * hypotheses and samples are dealt out to the worker threads of bd_solve_pnp_host (n_threads <= 0: 16).  Same checks, same outputs;
+ * replaces the same lines of src/models/utils/box_utils.py:202-300.  Not the default host path of the dense mode
+ * (pnp.solve_pnp_ransac is): the twin the device form is tested against. */
+int bd_solve_pnp_ransac_host(const float* kp_px, const float* bbox_3d, const float* K, const int32_t* picks, int n_samples, int n_rounds,
+                             int n_trials, float reproj_err, float confidence, int hyp_iters, int final_iters, float* poses,
+                             unsigned char* inliers, float* rms_px /* may be NULL */, int32_t* info /* may be NULL */, int n_threads);
+
 /* Dense-reference mode ("next" row f4): DINO-feature reference selection, src/models/utils/matching.py:64-174
  * (`dino_matching`, called from process_dense_input, src/models/utils/data_processing.py:179-225).
  * feats: fp32 [B, T, L, D] patch features of every view (the encoder output); images: [B, T, 3, H, W] RGB crops in [0, 1]
