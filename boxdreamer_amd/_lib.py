@@ -131,6 +131,7 @@ EXPORTS = [
     "bd_decoder_entry_workspace_bytes", "bd_decoder_forward_entry", "bd_decoder_entry_workspace_bytes_ragged",
     "bd_decoder_forward_entry_ragged", "bd_solve_pnp_wave",
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
+    "bd_round_sources", "bd_pose_select_rows",
 ]
 
 _lib = None
@@ -212,6 +213,8 @@ def load() -> C.CDLL:
     lib.bd_gather_view_rows.argtypes = [vp, i64, i, vp, i64, i, vp, vp, i64, i, i, i, i, vp, vp, vp, vp]
     lib.bd_match_view_sums.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, vp]
     lib.bd_match_select_rows.argtypes = [vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp]
+    lib.bd_round_sources.argtypes = [vp, vp, i, i, i, i, i, i, i, vp, vp, vp]
+    lib.bd_pose_select_rows.argtypes = [vp, i, vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
     lib.bd_assemble_entry_tokens.argtypes = [vp, i, vp, i, vp, vp, vp, vp, i, i, i, vp]
     lib.bd_decoder_entry_tokens_workspace_bytes.argtypes = [C.POINTER(BetrWeights), i, i]
     lib.bd_decoder_entry_tokens_workspace_bytes.restype = sz

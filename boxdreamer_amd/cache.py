@@ -32,6 +32,8 @@ holds one -1 per sample, at the query.
 With `decoder=model.decoder` the bank also keeps every row's decoder-ENTRY tokens (bd_decoder_entry_tokens): the heat maps of a
 reference are given once, `bank.add(ref_images, bbox_feat=ref_heatmaps)`, and a forward over such a bank reads the query crop and
 nothing else -- `bbox_feat` may be absent from the batch dict (bd_decoder_forward_entry).
+With `keep_poses=True` the bank also keeps every row's pose, `bank.add(ref_images, poses=ref_poses)`: the object's whole database --
+features, match summaries, entry tokens, poses -- over which `dense_cfg.multi_round` runs (dense.process_multi_round_bank).
 """
 from __future__ import annotations
 
@@ -116,6 +118,11 @@ class RefFeatureBank:
     operand row's ~590 KB.  With them a dense-reference forward (dense_cfg.enable + ref_bank) scores and selects among a sample's
     whole database without its features or crops (select).
 
+    `keep_poses` (False: none kept, today's bank byte for byte): every row also gets its view's pose, given in add(..., poses=...), as
+    fp32 [rows, 4, 4] in a store that grows with the others (same row ids): 64 bytes per view.  With them the bank is an object's whole
+    database and a dense MULTI-ROUND forward (dense_cfg.multi_round + ref_bank) runs over it: the fine level picks the references
+    nearest to the coarse pose from these rows (bd_pose_select_rows), and the short last round is padded with `zero_row`.
+
     `decoder` (None: none kept, today's bank byte for byte; a betr.BETR): every row also gets its decoder-entry tokens
     x = bbox_emb(patchify(bbox_feat)) + pos + adapter(feat) (bd_decoder_entry_tokens), computed in add() from the heat maps given there
     while the encoder's output still exists, in a second store that grows with the first (same row ids): fp32 [rows, P, D],
@@ -125,10 +132,11 @@ class RefFeatureBank:
     mode and the promotion of the Linears outside the blocks -- and a mismatch of either stamp makes the bank stale; with
     keep_images=True the heat maps are kept too, in the dtype they came in, and a refresh re-encodes and re-embeds."""
 
-    def __init__(self, encoder, keep_images: bool = True, match_threshold: float | None = None, decoder=None):
+    def __init__(self, encoder, keep_images: bool = True, match_threshold: float | None = None, decoder=None, keep_poses: bool = False):
         self.encoder = encoder                                 # a DinoV2Wrapper
         self.decoder = decoder                                 # a betr.BETR, or None: no entry tokens
         self.keep_images = bool(keep_images)
+        self.keep_poses = bool(keep_poses)
         self.match_threshold = None if match_threshold is None else float(match_threshold)
         self.refresh_count = 0
         self._tables = {}       # (ref_rows of the valid slots, counts, T_max, device) -> device tables of one gather launch
@@ -136,13 +144,15 @@ class RefFeatureBank:
         self.clear()
 
     def clear(self) -> None:
-        """Drop every row (ids start again at 0) and the kept crops."""
+        """Drop every row (ids start again at 0), the kept crops and the kept poses."""
         self._t16, self._cap, self._n = None, 0, 0
         self._pid, self._P, self._C, self._stamp = None, 0, 0, None
         self._images = []       # [(first row, crops (N, 3, S, S))] when keep_images
         self._msums, self._mcounts = None, None                # [cap, C] / [cap] fp32 match summaries (match_threshold)
         self._x32, self._entry_stamp, self._entry_shape = None, None, None   # [cap, P, D] fp32 decoder-entry tokens, their stamp (decoder)
         self._heat = []         # [(first row, heat maps (N, 8, S, S))] when keep_images and decoder
+        self._poses = None      # [>= cap, 4, 4] fp32 object-to-camera poses of the rows (keep_poses)
+        self._zero_row = None   # the row of the all-zero view, once a multi-round forward asked for it (zero_row)
 
     def __len__(self) -> int:
         return self._n
@@ -165,6 +175,54 @@ class RefFeatureBank:
     def has_entry_tokens(self) -> bool:
         """Whether every row carries its decoder-entry tokens (the bank was built with a decoder)."""
         return self.decoder is not None
+
+    @property
+    def has_poses(self) -> bool:
+        """Whether every row carries its view's pose (the bank was built with keep_poses=True): what the dense multi-round mode
+        needs, whose fine level picks the references nearest to the coarse pose (bd_pose_select_rows)."""
+        return self.keep_poses
+
+    @property
+    def poses(self):
+        """The pose store: fp32 (>= capacity, 4, 4), rows [0, len(bank)) in use (None while the bank is empty or keeps none)."""
+        return self._poses
+
+    def poses_of(self, row: int) -> torch.Tensor:
+        """The kept pose of a row, fp32 (4, 4) on the device (keep_poses=True)."""
+        if not self.has_poses or not 0 <= int(row) < self._n:
+            raise KeyError(f"row {row}: no pose kept")
+        return self._poses[int(row)]
+
+    @property
+    def zero_row(self) -> int:
+        """The bank row of the all-zero view that pads the last round of a multi-round decode (dense.sub_batchify pads with views whose
+        features AND heat maps are zero): zero bytes in every plane of the operand class, a zero match summary, a zero pose and, in an
+        entry-token bank, bd_decoder_entry_tokens of zero features and zero heat maps.  Made on first use, once per bank (clear()
+        forgets it); an ordinary row to every kernel, but never re-encoded from a crop -- a zero IMAGE does not encode to zero
+        features -- so a refresh re-makes it in place (ensure_fresh)."""
+        if self._zero_row is None:
+            if self._n == 0:
+                raise ValueError("an empty reference bank has no operand class yet: add() references before asking for its zero view")
+            self.ensure_fresh()
+            self._append_zero()
+        return self._zero_row
+
+    def _append_zero(self) -> None:
+        dev, P, C, z = self._t16.device, self._P, self._C, self._n
+        self._reserve(z + 1, dev)
+        for plane in operand.row_planes(self._t16, self._pid, (z + 1) * P):
+            plane[z * P:].zero_()
+        if self.has_match_summaries:
+            self._msums[z].zero_()
+            self._mcounts[z].zero_()
+        if self.has_poses:
+            self._poses[z].zero_()
+        if self.has_entry_tokens:
+            d = self.decoder
+            zeros = features.OperandOnly((1, P, C), operand.empty(self._pid, P, C, dev, zero=True), self._pid, self._stamp[0])
+            d.entry_tokens(torch.zeros((1, d.box_dim, d.img_size, d.img_size), dtype=torch.float32, device=dev), zeros, out=self._x32[z:z + 1])
+        self._zero_row = z
+        self._n += 1
 
     @property
     def entry_tokens(self):
@@ -208,6 +266,7 @@ class RefFeatureBank:
         return self._n > 0 and (self._stamp != self._now() or (self.has_entry_tokens and self._entry_stamp != self._entry_now()))
 
     def _reserve(self, need: int, dev) -> None:
+        self._reserve_poses(need, dev)
         if self._t16 is not None and need <= self._cap and self._t16.device == dev:
             return
         cap = max(need, 2 * self._cap, 8)
@@ -227,6 +286,15 @@ class RefFeatureBank:
                 x32[:self._n].copy_(self._x32[:self._n])
             self._x32 = x32
         self._t16, self._cap = new, cap
+
+    def _reserve_poses(self, need: int, dev) -> None:
+        """The pose store has a capacity of its own (a refresh rebuilds the other stores and leaves this one alone)."""
+        if not self.has_poses or (self._poses is not None and need <= self._poses.shape[0] and self._poses.device == dev):
+            return
+        poses = torch.zeros((max(need, 2 * (0 if self._poses is None else self._poses.shape[0]), 8), 4, 4), dtype=torch.float32, device=dev)
+        if self._poses is not None:
+            poses[:self._n].copy_(self._poses[:self._n])
+        self._poses = poses
 
     ENTRY_CHUNK = 64            # views per bd_decoder_entry_tokens call (its workspace is ~4 MB per view; rows do not depend on the chunking)
 
@@ -262,13 +330,24 @@ class RefFeatureBank:
                 self._heat.append((self._n, bbox_feat))
         self._n += n
 
-    def add(self, images: torch.Tensor, bbox_feat: torch.Tensor | None = None) -> torch.Tensor:
+    def add(self, images: torch.Tensor, bbox_feat: torch.Tensor | None = None, poses: torch.Tensor | None = None) -> torch.Tensor:
         """images (R, 3, S, S) or (B, R, 3, S, S) in [0, 1] -> CPU int64 row ids of the same leading shape.  Earlier ids stay valid.
         bbox_feat: the views' corner heat maps, (R, 8, S, S) or (B, R, 8, S, S) -- required by a bank that keeps decoder-entry tokens
-        (built with decoder=), refused by one that does not."""
+        (built with decoder=), refused by one that does not.  poses: the views' poses, (R, 4, 4) or (B, R, 4, 4) of any float dtype
+        (kept as fp32) -- required by a bank that keeps poses (keep_poses=True), refused by one that does not."""
         if images.dim() not in (4, 5):
             raise ValueError(f"expected (R, 3, S, S) or (B, R, 3, S, S), got {tuple(images.shape)}")
         lead = tuple(images.shape[:-3])
+        if self.has_poses and poses is None:
+            raise ValueError("this reference bank keeps poses (it was built with keep_poses=True): add(images, poses=...) needs the "
+                             "references' poses")
+        if poses is not None and not self.has_poses:
+            raise ValueError("poses given to a reference bank that keeps none: build it with RefFeatureBank(encoder, keep_poses=True)")
+        if poses is not None and (not isinstance(poses, torch.Tensor) or not poses.dtype.is_floating_point
+                                  or tuple(poses.shape) != lead + (4, 4)):
+            raise ValueError(f"poses must be a float tensor of shape {lead + (4, 4)} for images {tuple(images.shape)}, got "
+                             f"{tuple(poses.shape) if isinstance(poses, torch.Tensor) else type(poses).__name__}"
+                             f"{' ' + str(poses.dtype) if isinstance(poses, torch.Tensor) else ''}")
         if self.has_entry_tokens and bbox_feat is None:
             raise ValueError("this reference bank keeps decoder-entry tokens (it was built with decoder=): add(images, bbox_feat=...) "
                              "needs the references' heat maps")
@@ -285,6 +364,8 @@ class RefFeatureBank:
         if flat.shape[0]:
             keep = self.keep_images
             self._append(flat.clone() if keep else flat, None if heat is None else (heat.clone() if keep else heat.contiguous()))
+            if poses is not None:
+                self._poses[n0:self._n].copy_(poses.reshape(-1, 4, 4))
         return torch.arange(n0, self._n, dtype=torch.int64).reshape(lead)
 
     def ensure_fresh(self) -> bool:
@@ -308,8 +389,13 @@ class RefFeatureBank:
         new = RefFeatureBank(self.encoder, keep_images=True, match_threshold=self.match_threshold, decoder=self.decoder)
         heat = self._heat if self.has_entry_tokens else [(None, None)] * len(self._images)
         for (_, img), (_, hm) in zip(self._images, heat):      # in row order: ids are unchanged
+            if self._zero_row == new._n:                       # the zero view keeps its row: zero features, its entry tokens re-made
+                new._append_zero()
             new._append(img, hm)
-        for k in ("_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images", "_msums", "_mcounts", "_x32", "_entry_stamp", "_entry_shape", "_heat"):
+        if self._zero_row == new._n:
+            new._append_zero()
+        # (the poses are no function of the encoder or the decoder: the store stays as it is, under the same row ids)
+        for k in ("_zero_row", "_t16", "_cap", "_n", "_pid", "_P", "_C", "_stamp", "_images", "_msums", "_mcounts", "_x32", "_entry_stamp", "_entry_shape", "_heat"):
             setattr(self, k, getattr(new, k))
         self.refresh_count += 1
         return True

@@ -16,6 +16,9 @@ the reference's cv2.solvePnPRansac call where cv2 imports, a restatement of the 
 un-pinned in this image.  With `pnp_on_device: "wave"` and at most 8 rounds the same scheme runs in HIP instead
 (csrc/pnp.hip: bd_solve_pnp_ransac_wave, one wavefront per hypothesis): corners, box, K and the coarse pose stay on the device;
 data["dense_pose_solver"] names what ran, data["dense_pose_inliers"] / data["dense_pose_rms_px"] say which rounds it kept.
+Over a reference bank that keeps poses (cache.RefFeatureBank(keep_poses=True)) the multi-round decode runs from the bank's rows
+(process_multi_round_bank; csrc/rounds.hip: bd_round_sources, bd_pose_select_rows, restated here for the CPU as round_sources_host /
+pose_select_rows_host): only the query crops are encoded, the results are those of process_multi_round bit for bit.
 """
 from __future__ import annotations
 
@@ -209,7 +212,77 @@ def fetch_neighbors_by_pose_similarity(gt_poses, pred_pose, topk=5):
     return torch.topk(dist, k=topk, dim=1, largest=False)[1]
 
 
-DENSE_SOLVER_HOST = "host:pnp.solve_pnp_ransac (cv2.solvePnPRansac where importable, else its scheme restated; parity vs OpenCV un-pinned)"
+# ------------------------------------------------------------------------------------------- multi-round decode over a bank
+# CPU restatements (plain Python / numpy fp64) of the two kernels of csrc/rounds.hip: what their tests compare against.
+
+NO_VIEW = 0x7fffffff        # a source-table entry bd_gather_view_rows skips
+
+
+def _candidate_row(rows_b, slot, n_bank):
+    if not 0 <= slot < len(rows_b):
+        return NO_VIEW
+    r = int(rows_b[slot])
+    return r if 0 <= r < n_bank else NO_VIEW
+
+
+def round_sources_host(rows, cand, n_bank, sub, zero_row, per_round_query):
+    """bd_round_sources on the host: rows [B][N_max], cand [B][k] (lists or tensors) -> (src, view), flat int lists of
+    B * R * (sub + 1) entries, R = ceil(k / sub)."""
+    rows, cand = torch.as_tensor(rows).tolist(), torch.as_tensor(cand).tolist()
+    k = len(cand[0])
+    R = -(-k // sub)
+    src, view = [], []
+    for b, (rb, cb) in enumerate(zip(rows, cand)):
+        for r in range(R):
+            for j in range(sub):
+                c = r * sub + j
+                src.append(_candidate_row(rb, int(cb[c]), n_bank) if c < k else int(zero_row))
+                view.append(c if c < k else -1)
+            src.append(-((b * R + r if per_round_query else b) + 1))
+            view.append(k)
+    return src, view
+
+
+def pose_distance_host(pred, pose) -> float:
+    """bd_pose_select_rows' distance of two (4, 4) poses in fp64, in the kernel's summation order (include/boxdreamer_hip.h)."""
+    p, g = np.asarray(pred, dtype=np.float64), np.asarray(pose, dtype=np.float64)
+    tr = np.float64(0.0)
+    for i in range(3):
+        for j in range(3):
+            tr = tr + p[i, j] * g[i, j]
+    x = (tr - 1.0) / 2.0
+    x = np.float64(-1.0) if x < -1.0 else (np.float64(1.0) if x > 1.0 else x)
+    ss = np.float64(0.0)
+    for i in range(3):
+        d = p[i, 3] - g[i, 3]
+        ss = ss + d * d
+    with np.errstate(invalid="ignore"):
+        return float(np.arccos(x) + np.sqrt(ss))
+
+
+def pose_select_rows_host(bank_poses, n_bank, pred, rows, cand, fk):
+    """bd_pose_select_rows on the host: bank_poses (>= n_bank, 4, 4) and pred (B, 4, 4) fp32, rows [B][N_max], cand [B][k] ->
+    (dist64 [B][k] the fp64 distances (inf: invalid candidate), fine_pos [B][fk], src flat [B * (fk + 1)]); the ranking is on the
+    distances rounded to fp32, as the kernel's."""
+    bank = torch.as_tensor(bank_poses).detach().cpu().float().numpy()
+    pr = torch.as_tensor(pred).detach().cpu().float().numpy()
+    rows, cand = torch.as_tensor(rows).tolist(), torch.as_tensor(cand).tolist()
+    dist, fine_pos, src = [], [], []
+    for b, (rb, cb) in enumerate(zip(rows, cand)):
+        rws = [_candidate_row(rb, int(s), n_bank) for s in cb]
+        d64 = [float("inf") if r == NO_VIEW else pose_distance_host(pr[b], bank[r]) for r in rws]
+        d32 = [float(np.float32(d)) for d in d64]
+        valid = [c for c, r in enumerate(rws) if r != NO_VIEW]
+        order = sorted(valid, key=lambda c: (d32[c] != d32[c], 0.0 if d32[c] != d32[c] else d32[c], c))
+        pos = sorted(order[:fk])
+        pos += [-1] * (fk - len(pos))
+        dist.append(d64)
+        fine_pos.append(pos)
+        src += [rws[c] if c >= 0 else NO_VIEW for c in pos] + [-(b + 1)]
+    return dist, fine_pos, src
+
+
+DENSE_SOLVER_HOST ="host:pnp.solve_pnp_ransac (cv2.solvePnPRansac where importable, else its scheme restated; parity vs OpenCV un-pinned)"
 DENSE_SOLVER_WAVE = "hip:bd_solve_pnp_ransac_wave (one wavefront per hypothesis, DLT + LM; parity vs OpenCV un-pinned)"
 
 
@@ -310,3 +383,89 @@ def process_multi_round(data, pose_feat, frames, camera_mask, rgb_feature, image
     data["pred_poses"] = pred_poses
     data["pred_intrinsics"] = data["intrinsics"].clone()
     return data
+
+
+def _repeat_views(fresh, times: int):
+    """The encoder's tagged (B, P, C) output with every view `times` times in a row, as the operand copy alone (features.OperandOnly of
+    (B * times, P, C)): the multi-round batch's query features over an entry-token bank.  The bytes are copied, nothing is re-cast."""
+    from . import features as _features, operand
+    f16, pid = _features.require_tag(fresh)
+    B, P, C = fresh.shape
+    out16 = operand.empty(pid, B * times * P, C, fresh.device)
+    for dst, src in zip(operand.row_planes(out16, pid, B * times * P), operand.row_planes(f16, pid, B * P)):
+        dst.reshape(B, times, P, C).copy_(src.reshape(B, 1, P, C).expand(B, times, P, C))
+    return _features.OperandOnly((B * times, P, C), out16, pid, _features.stamp_of(fresh))
+
+
+def process_multi_round_bank(data, bank, fresh, rows, cand, ar, decoder, dense_cfg, pnp_on_device=False):
+    """process_multi_round over a reference bank that keeps poses (cache.RefFeatureBank(keep_poses=True)), after the banked dense
+    selection re-packed the batch dict to (B, k + 1): `fresh` the encoder's tagged output for the B query crops, rows (B, N_max) /
+    cand (B, k) the device tables of that selection (bank rows per reference slot; the kept slots, ascending), ar = arange(B).
+    ONE bd_round_sources launch names the views of the (B * R, sub + 1) rounds -- the short last round padded with bank.zero_row --
+    and the decoder runs on them from the bank: bank.gather for a feature bank (bbox_feat re-packed by integer indexing with the
+    kernel's `view` table, zeros where it pads), BETR.forward_entry for an entry-token bank (the query's features repeated per
+    round; bbox_feat may be absent).  recover_pose_from_dense_bb8 runs as it is.  Without dense_cfg.fine_level the coarse dict is
+    written as process_multi_round writes it and (data, None) returned.  With it ONE bd_pose_select_rows launch picks the fine_topk
+    kept references nearest to the coarse pose by the BANK's poses (the dict's are not read), the dict is re-packed to
+    (B, fine_topk + 1) and (the fine round's decoder output, the new query_idx) returned; the dict gains dense_fine_slots
+    (B, fine_topk) -- original reference slots, ascending -- and dense_fine_dist (B, k).  Nothing here waits for the device unless
+    the host RANSAC runs.  The results are bit-identical to process_multi_round on the same crops."""
+    from . import hip_ops
+    B, k = cand.shape
+    sub = int(_get(dense_cfg, "sub_batch_size"))
+    R = (k + sub - 1) // sub
+    entry, friendly = bank.has_entry_tokens, bool(_get(dense_cfg, "dense_mem_friendly"))
+    dev = fresh.device
+    pose_feat, frames = data.get("bbox_feat"), data["images"]
+    size = frames.shape[-1]
+    zero_row = bank.zero_row if k % sub else -1
+    # (forward_entry takes one fresh view per pseudo-sample, in order: the round-by-round form decodes B samples at a time)
+    src, view = hip_ops.round_sources(rows, cand, len(bank), sub, zero_row, per_round_query=entry and not friendly)
+    src = src.reshape(B, R, sub + 1)
+    masks = (torch.arange(sub + 1, device=dev) == sub).expand(B * R, sub + 1).contiguous()
+    npf = nfr = None
+    if not entry:
+        v = view.reshape(B, R * (sub + 1)).long()
+        npf = pose_feat[ar[:, None], v.clamp_min(0)]
+        npf.masked_fill_((v < 0).reshape(B, -1, 1, 1, 1), 0)
+        npf = npf.reshape(B, R, sub + 1, *pose_feat.shape[2:])
+        # (BETR reads the shape of the crops and nothing else: a view of the right shape, no copy)
+        nfr = frames[:1, :1].expand(B * R, sub + 1, *frames.shape[2:])
+
+    def decode(s, n, heat):
+        if entry:
+            return decoder.forward_entry(bank.entry_tokens, len(bank), s, fresh if n == B else _repeat_views(fresh, R), masks[:n], size)
+        return decoder(heat, nfr[:n], masks[:n], bank.gather(s, fresh, (n, sub + 1)), None)
+
+    if friendly:
+        outs = [decode(src[:, i].reshape(-1).contiguous(), B, None if entry else npf[:, i].contiguous()).clone() for i in range(R)]
+        query_rets = torch.stack(outs, dim=1)
+    else:
+        flat = decode(src.reshape(-1), B * R, None if entry else npf.reshape(B * R, sub + 1, *pose_feat.shape[2:]))
+        query_rets = flat.reshape(B, R, *flat.shape[1:])
+    qi = data["query_idx"]
+    trials = _get(dense_cfg, "ransac_trials")
+    query_poses, pred_proj = recover_pose_from_dense_bb8(query_rets, data["bbox_3d"][ar, qi], data["non_ndc_intrinsics"][ar, qi],
+                                                         pnp_on_device=pnp_on_device, n_trials=1000 if trials is None else int(trials),
+                                                         record=data)
+    if _get(dense_cfg, "fine_level"):
+        fk = int(_get(dense_cfg, "fine_topk"))
+        dist, fine_pos, fsrc = hip_ops.pose_select_rows(bank.poses, len(bank), query_poses.reshape(B, 4, 4).float().contiguous(), rows, cand, fk)
+        pos = fine_pos.long().clamp_min(0)
+        data["dense_fine_dist"], data["dense_fine_slots"] = dist, cand.gather(1, pos)
+        qi = filter_by_view_index(data, torch.cat([pos, torch.full((B, 1), k, dtype=torch.long, device=dev)], dim=1), ar)
+        if entry:
+            return decoder.forward_entry(bank.entry_tokens, len(bank), fsrc, fresh, data["camera_mask"], size), qi
+        return decoder(data["bbox_feat"], data["images"], data["camera_mask"], bank.gather(fsrc, fresh, (B, fk + 1)), None), qi
+    pred_poses = data["poses"].clone()
+    if pose_feat is not None:
+        data["pred_bbox"] = pose_feat.clone()
+        data["pred_bbox"][ar, qi] = query_rets[:, 0].to(pose_feat.dtype)
+    else:       # an entry-token bank's batch may carry no heat maps: the decoder's output goes out as it does from BoxDreamer.forward
+        data["pred_query_bbox"] = query_rets[:, 0]
+    pred_poses[ar, qi] = query_poses.squeeze(1).to(pred_poses.dtype)
+    data["regression_boxes"] = data["bbox_proj_crop"].clone()
+    data["regression_boxes"][ar, qi] = pred_proj[:, 0].to(data["regression_boxes"].dtype)
+    data["pred_poses"] = pred_poses
+    data["pred_intrinsics"] = data["intrinsics"].clone()
+    return data, None

@@ -303,6 +303,42 @@ def match_select_rows(bank_sums, bank_counts, n_bank, q_sums, q_counts, rows, n_
     return scores, sel, src
 
 
+def round_sources(rows, cand, n_bank, sub, zero_row, per_round_query):
+    """bd_round_sources: one launch -> (src, view), both int32 (B * R * (sub + 1),), R = ceil(k / sub): the source table of the
+    (B * R, sub + 1) multi-round batch and each entry's view position in the filtered (B, k + 1) batch (-1: zero padding).  rows:
+    device int32 (B, N_max); cand: device int32 (B, k), bd_match_select_rows' sel; n_bank: rows of the bank that are in use (the
+    zero row among them); zero_row: the bank's all-zero view, -1 when no round is padded."""
+    lib = _lib.load()
+    (B, N_max), k, sub = rows.shape, int(cand.shape[1]), int(sub)
+    if rows.dtype != torch.int32 or cand.dtype != torch.int32 or cand.shape[0] != B or not rows.is_contiguous() or not cand.is_contiguous():
+        raise ValueError("round_sources needs contiguous int32 rows (B, N_max) and cand (B, k) of the same B")
+    n = B * (-(-k // sub) if sub > 0 else 0) * (sub + 1)
+    src = torch.empty((max(n, 0),), dtype=torch.int32, device=rows.device)
+    view = torch.empty_like(src)
+    check(lib.bd_round_sources(ptr(rows), ptr(cand), int(n_bank), int(B), int(N_max), k, sub, int(zero_row), int(bool(per_round_query)),
+                               ptr(src), ptr(view), stream()), "bd_round_sources")
+    return src, view
+
+
+def pose_select_rows(bank_poses, n_bank, pred, rows, cand, fk):
+    """bd_pose_select_rows: one launch -> (dist fp32 (B, k), fine_pos int32 (B, fk), src int32 (B * (fk + 1),)).  bank_poses: fp32
+    (capacity, 4, 4), n_bank rows in use; pred: fp32 (B, 4, 4) coarse poses; rows / cand: as round_sources."""
+    lib = _lib.load()
+    (B, N_max), k, fk = rows.shape, int(cand.shape[1]), int(fk)
+    if (bank_poses.dtype != torch.float32 or pred.dtype != torch.float32 or not bank_poses.is_contiguous() or not pred.is_contiguous()
+            or tuple(bank_poses.shape[1:]) != (4, 4) or tuple(pred.shape) != (B, 4, 4) or bank_poses.shape[0] < int(n_bank)):
+        raise ValueError("pose_select_rows needs contiguous fp32 bank_poses (>= n_bank, 4, 4) and pred (B, 4, 4)")
+    if rows.dtype != torch.int32 or cand.dtype != torch.int32 or cand.shape[0] != B or not rows.is_contiguous() or not cand.is_contiguous():
+        raise ValueError("pose_select_rows needs contiguous int32 rows (B, N_max) and cand (B, k) of the same B")
+    dev = pred.device
+    dist = torch.empty((B, k), dtype=torch.float32, device=dev)
+    fine_pos = torch.empty((B, max(fk, 0)), dtype=torch.int32, device=dev)
+    src = torch.empty((B * (max(fk, 0) + 1),), dtype=torch.int32, device=dev)
+    check(lib.bd_pose_select_rows(ptr(bank_poses), int(n_bank), ptr(pred), ptr(rows), ptr(cand), int(B), int(N_max), k, fk, ptr(dist),
+                                  ptr(fine_pos), ptr(src), stream()), "bd_pose_select_rows")
+    return dist, fine_pos, src
+
+
 def im2col_images(images, patch=14, kpad=640, *, prec="bf16"):
     lib = _lib.load()
     images = images.contiguous()

@@ -17,7 +17,7 @@ from . import _lib, calibrate, features, pnp
 from .box_utils import recover_bb8_corners_chw, solve_poses_device, solve_poses_host
 from .cache import merge_cached_features
 from .config import setup_camera_params, validate_model_config
-from .dense import filter_by_view_index, process_dense_input, process_multi_round
+from .dense import filter_by_view_index, process_dense_input, process_multi_round, process_multi_round_bank
 from .encoder import DinoV2Wrapper
 
 
@@ -284,7 +284,7 @@ class BoxDreamer(nn.Module):
                 self._sync_ranks_once()
             data["hip_precision"] = self._precision_record()
         ar = self._arange(B, dev)
-        decoded = None
+        decoded, slots_key = None, "dense_ref_slots"
         if (self.hip_graph and bank is None and counts is None and not dense and "cached_rgb_feat" not in data and not self.training
                 and images.is_cuda and isinstance(self.decoder, BETR) and not torch.cuda.is_current_stream_capturing()):
             # (a banked or a ragged batch takes the eager branch -- capture of ragged shapes is a follow-up)
@@ -303,7 +303,24 @@ class BoxDreamer(nn.Module):
             B, T = idx.shape
             qi = filter_by_view_index(data, idx, ar)
             images, pose_feat, camera_mask = data["images"], data.get("bbox_feat"), data["camera_mask"]
-            if entry:       # (rgb_feature: the queries' encoder output and the source table bd_match_select_rows wrote)
+            if _get(self.dense_cfg, "multi_round", False):
+                # (rgb_feature: the queries' encoder output and the bank-row table of the selection, on the device)
+                query_ret, fine_qi = process_multi_round_bank(data, bank, rgb_feature[0], rgb_feature[1], data["dense_ref_slots"], ar,
+                                                              self.decoder, self.dense_cfg, pnp_on_device=self.pnp_on_device)
+                if fine_qi is None:                                                   # coarse prediction only: dict is final
+                    # (a device-side query_idx that is not the table's: its verdict joins the decoder's in decoder.mask_error and
+                    # stays deferred there, as the un-banked coarse return leaves the decoder's -- this return reads nothing back)
+                    if self._dense_query_bad is not None:
+                        err = self.decoder.mask_error
+                        self.decoder.mask_error = self._dense_query_bad if err is None else (err | self._dense_query_bad)
+                    syncs = []
+                    if "original_images" in data:
+                        self._slots_host = None
+                        self._repack_original_images(data, dense_plan, data["dense_ref_slots"], syncs)
+                    self.host_syncs_per_forward = syncs
+                    return data
+                qi, (B, T), slots_key = fine_qi, data["images"].shape[:2], "dense_fine_slots"
+            elif entry:     # (rgb_feature: the queries' encoder output and the source table bd_match_select_rows wrote)
                 query_ret = self.decoder.forward_entry(bank.entry_tokens, len(bank), rgb_feature[1], rgb_feature[0], camera_mask, images.shape[-1])
             else:
                 query_ret = self.decoder(pose_feat, images, camera_mask, rgb_feature, None)
@@ -359,7 +376,8 @@ class BoxDreamer(nn.Module):
         pred_poses = data["poses"].clone()
         syncs = []
         # the selected slots travel with the corners' D2H when the host needs them (original_images is a host list)
-        slots = data["dense_ref_slots"] if dense_plan is not None and "original_images" in data else None
+        # (after a fine level: the original slots of ITS choice -- both selections composed)
+        slots = data[slots_key] if dense_plan is not None and "original_images" in data else None
         self._slots_host = None
         if not self.training:
             pred_poses = self._process_evaluation(pred_poses, data, query_ret, ar, qi, decoded, syncs, write_pred_bbox, slots)
@@ -441,7 +459,8 @@ class BoxDreamer(nn.Module):
         references in slot order, the query last).  The B query crops go through the encoder in ONE predict call; bd_match_view_sums
         summarises them, ONE bd_match_select_rows launch scores every reference against its query from the bank's summaries, picks
         the k best and writes the source table of ONE bd_gather_view_rows launch.  Images in banked slots are never read; nothing
-        here waits for the device."""
+        here waits for the device.  With dense_cfg.multi_round nothing is gathered here: the first item is (the queries' encoder
+        output, the device table of bank rows per reference slot), from which dense.process_multi_round_bank names its rounds."""
         ref_rows, n_refs, n_max, query, k = plan
         B, T = images.shape[:2]
         refreshed = bank.ensure_fresh()
@@ -449,12 +468,19 @@ class BoxDreamer(nn.Module):
         crops = images.reshape(B * T, *images.shape[2:]).index_select(0, q_flat)
         fresh = self.rgb_encoder.predict(crops)
         scores, sel, src = bank.select(fresh, crops, rows_d, n_refs_d, k)
-        # (an entry-token bank: the decoder takes the source table itself, no feature row is gathered)
-        feats = (fresh, src) if bank.has_entry_tokens else bank.gather(src, fresh, (B, k + 1))
+        multi = bool(_get(self.dense_cfg, "multi_round", False))
+        # (an entry-token bank: the decoder takes the source table itself, no feature row is gathered; multi-round: the rounds have a
+        # source table of their own, bd_round_sources', made from the selection and the bank-row table)
+        feats = (fresh, rows_d) if multi else (fresh, src) if bank.has_entry_tokens else bank.gather(src, fresh, (B, k + 1))
         data["dense_ref_slots"], data["dense_ref_scores"] = sel, scores
         self._dense_query_bad = (qi != q_d).any() if isinstance(query_idx, torch.Tensor) and query_idx.is_cuda else None
-        record = self._lanes_record(B, k + 1, None) if isinstance(self.decoder, BETR) else {}
+        sub = int(_get(self.dense_cfg, "sub_batch_size")) if multi else k
+        rounds = (k + sub - 1) // sub
+        at_once = 1 if multi and _get(self.dense_cfg, "dense_mem_friendly") else rounds      # rounds one decoder call covers
+        record = self._lanes_record(B * at_once, sub + 1, None) if isinstance(self.decoder, BETR) else {}
         record["ref_bank"] = {"banked_views": B * k, "encoded_views": B, "scored_views": sum(n_refs), "refreshed": bool(refreshed)}
+        if multi:       # (the zero views that pad the last round are bank rows too, and are not counted as banked views)
+            record["ref_bank"].update(rounds=rounds, padded_views=B * (rounds * sub - k))
         if bank.has_entry_tokens:
             record["ref_bank"]["entry_tokens"] = True
         ref = sel.long()
@@ -490,8 +516,9 @@ class BoxDreamer(nn.Module):
                                       "implemented over the reference bank only")
         if ragged and not betr:
             raise NotImplementedError("view_counts needs the BETR decoder")
-        if banked and dense and _get(self.dense_cfg, "multi_round", False):
-            raise NotImplementedError("ref_bank together with dense_cfg.multi_round (multi-round decode over the bank) is not implemented")
+        if banked and dense and _get(self.dense_cfg, "multi_round", False) and not getattr(bank, "has_poses", False):
+            raise NotImplementedError("ref_bank together with dense_cfg.multi_round (multi-round decode over the bank) needs a bank that "
+                                      "keeps its views' poses: build it with RefFeatureBank(..., keep_poses=True) and add(..., poses=...)")
         if banked and dense and not (_get(self.dense_cfg, "filter") == "dino" and _get(self.dense_cfg, "filter_enable")):
             raise NotImplementedError("ref_bank together with dense_cfg.enable is implemented for the DINO filter only "
                                       "(dense_cfg.filter = 'dino' with dense_cfg.filter_enable)")

@@ -455,6 +455,42 @@ int bd_match_select_rows(const float* bank_sums, const float* bank_counts, int R
                          const int32_t* rows, const int32_t* n_refs, int B, int N_max, int L, int D, int k,
                          float* scores, int32_t* sel, int32_t* src, void* stream);
 
+/* Dense multi-round decode over a bank that keeps its views' poses (cache.RefFeatureBank(keep_poses=True)): the two tables the
+ * facade needs between the selection above and the decoder, written on the device from what the device selected, so that nothing
+ * waits for it.  Both run one workgroup per sample without atomics; a sample's outputs do not depend on the rest of the batch.
+ * rows: device int32 [B, N_max] as above; cand: device int32 [B, k], bd_match_select_rows' `sel` (reference slots, ascending, -1:
+ * none); R: the bank's views in use.  A candidate whose slot is outside [0, N_max), or whose row is outside [0, R), is invalid: its
+ * src entry is 0x7fffffff, which bd_gather_view_rows and bd_assemble_entry_tokens skip, and `rows` is not read for it.
+ *
+ * bd_round_sources: the source table of the (B * rounds, sub + 1) batch, rounds = ceil(k / sub).  src / view: int32
+ * [B * rounds * (sub + 1)].  Pseudo-sample q = b * rounds + r, position j < sub, c = r * sub + j: src = the bank row of candidate c
+ * and view = c where c < k; src = zero_row (the bank's all-zero view, cache.RefFeatureBank.zero_row) and view = -1 where the last
+ * round runs out.  Position sub is the query: view = k, src = -(q + 1) when per_round_query != 0 (bd_decoder_forward_entry wants one
+ * fresh view per pseudo-sample, in order) and -(b + 1) otherwise (bd_gather_view_rows may name one fresh view `rounds` times).
+ * `view` is a view position of the filtered (B, k + 1) batch: the facade re-packs bbox_feat / images with it by integer indexing.
+ * Checked before any launch: NULL pointers BD_ERR_NULL; B <= 0, R < 0, N_max <= 0, k <= 0, k > 1024, sub <= 0, a table of more than
+ * 2^31 - 1 entries, and k % sub != 0 with zero_row outside [0, R) BD_ERR_SHAPE (zero_row is not read when no round is padded). */
+int bd_round_sources(const int32_t* rows, const int32_t* cand, int R, int B, int N_max, int k, int sub, int zero_row,
+                     int per_round_query, int32_t* src, int32_t* view, void* stream);
+
+/* bd_pose_select_rows: the fine level's choice (data_utils.py:97-135, fetch_neighbors_by_pose_similarity) among the k candidates, from
+ * the bank's poses.  bank_poses: fp32 [>= R, 4, 4]; pred: fp32 [B, 4, 4], the coarse pose (bd_solve_pnp_ransac_wave's output, or the
+ * host RANSAC's, uploaded); 1 <= fk <= k <= 1024.  Distance of candidate c, with P = pred[b], G = bank_poses[row of c]:
+ *     d = acos(clamp((tr - 1) / 2, -1, 1)) + sqrt(ss)
+ *     tr = trace(P_R G_R^T) = sum over i = 0..2, j = 0..2 (i outer) of P[i][j] * G[i][j]
+ *     ss = sum over i = 0..2 of (P[i][3] - G[i][3])^2
+ * evaluated in fp64 from the fp32 inputs, each sum sequential from 0.0 in the order written, every operation rounded on its own (no
+ * contraction), the clamp by comparison (a NaN stays a NaN), and d rounded ONCE to fp32.  A failed coarse pose (all zeros) and
+ * non-finite poses are ordinary inputs.
+ * dist: fp32 [B, k], +inf for an invalid candidate.  fine_pos: int32 [B, fk], the positions in `cand` of the fk valid candidates
+ * that rank first, in ascending position order (the order filter_by_neighbor_mask keeps).  Ranking is on the stored fp32 value:
+ * smaller first, ties to the lower position, +inf an ordinary value, NaN after every number and among NaNs by position.  src: int32
+ * [B * (fk + 1)]: per sample those candidates' bank rows, then -(b + 1), fresh view b (the query).  With fewer than fk valid
+ * candidates the remaining entries of fine_pos[b] are -1 and their src entries 0x7fffffff.
+ * Checked before any launch: NULL pointers BD_ERR_NULL; B <= 0, R < 0, N_max <= 0, k <= 0, k > 1024, fk <= 0, fk > k BD_ERR_SHAPE. */
+int bd_pose_select_rows(const float* bank_poses, int R, const float* pred, const int32_t* rows, const int32_t* cand, int B,
+                        int N_max, int k, int fk, float* dist, int32_t* fine_pos, int32_t* src, void* stream);
+
 /* Eval-step pose metrics: the per-sample values of Metrics.compute_metrics, src/lightning/utils/metrics/metric_utils.py:97-128
  * (query_pose_error :162-211, process_single_bs_2d :255-306 with project_optimized :224-239, process_single_bs_add :331-424).
  * Per pose b (the query view, gathered by the caller): pred_poses / original_poses fp32 [n_poses, 4, 4], scale fp32 [n_poses, 3],

@@ -1,0 +1,226 @@
+"""CPU: the host side of the dense multi-round decode over a reference bank that keeps poses -- the pose-keeping bank's argument rules,
+BoxDreamer._check_mode's one rule for ref_bank + dense_cfg.multi_round (nothing is encoded on a box without a GPU), the CPU
+restatements of bd_round_sources / bd_pose_select_rows (dense.round_sources_host, dense.pose_select_rows_host) and the argument
+validation of the two entry points."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from boxdreamer_amd import _lib, dense
+from boxdreamer_amd.cache import RefFeatureBank
+from boxdreamer_amd.model import BoxDreamer
+
+NO_VIEW = 0x7FFFFFFF
+DENSE = {"enable": True, "filter": "dino", "filter_enable": True, "filter_topk": 3, "multi_round": True, "sub_batch_size": 2,
+         "fine_level": False, "fine_topk": 2}
+
+
+def _model(dense_cfg):
+    cfg = {"modules": {
+        "use_keypoints": False, "use_matching": False, "use_tracking": False, "use_rgb": True, "use_pp": True,
+        "regression_intri": True, "rotation_type": None, "coordinate": "object", "pose_representation": "bb8",
+        "bbox_representation": "heatmap", "patchify_rays": True, "dense_cfg": dense_cfg,
+        "decoder": {"d_model": 768, "nhead": 8, "num_decoder_layers": 1, "decoder_only": True, "patch_size": 14,
+                    "img_size": 224, "diff_emb": False, "nvs_supervision": False, "ray_supervision": True, "use_mask": False},
+        "encoder": {"name": "dino", "dino": {"ckpt_path": None, "cfg": {"model_type": "dinov2_vitb14_reg",
+                                                                        "synthetic_seed": 1, "depth": 1}}}}}
+    return BoxDreamer(cfg).eval()
+
+
+def _batch(B=2, T=6, query=(5, 1)):
+    data = {"images": torch.zeros(B, T, 3, 8, 8), "bbox_feat": torch.zeros(B, T, 8, 8, 8), "query_idx": torch.tensor(query)}
+    table = [[b * T + t for t in range(T)] for b in range(B)]
+    for b, q in enumerate(query):
+        table[b][q] = -1
+    return data, table
+
+
+def test_pose_keeping_bank_argument_rules():
+    """Every refusal below comes before the encoder is touched."""
+    model = _model(DENSE)
+    plain = RefFeatureBank(model.rgb_encoder)
+    assert plain.has_poses is False and plain.poses is None
+    with pytest.raises(ValueError, match="keep_poses=True"):                       # poses= without keep_poses
+        plain.add(torch.zeros(3, 3, 8, 8), poses=torch.eye(4).expand(3, 4, 4))
+    bank = RefFeatureBank(model.rgb_encoder, keep_poses=True)
+    assert bank.has_poses is True and bank.poses is None and len(bank) == 0
+    with pytest.raises(ValueError, match="needs the references' poses"):          # a missing poses= with it
+        bank.add(torch.zeros(3, 3, 8, 8))
+    for bad in (torch.zeros(2, 4, 4), torch.zeros(3, 3, 4), torch.zeros(1, 3, 4, 4), torch.zeros(3, 4, 4, dtype=torch.int64)):
+        with pytest.raises(ValueError, match="poses must be a float tensor"):
+            bank.add(torch.zeros(3, 3, 8, 8), poses=bad)
+    with pytest.raises(ValueError, match="poses must be a float tensor"):         # (B, R, ...) images want (B, R, 4, 4)
+        bank.add(torch.zeros(2, 3, 3, 8, 8), poses=torch.zeros(6, 4, 4))
+    with pytest.raises(KeyError, match="no pose kept"):
+        bank.poses_of(0)
+    with pytest.raises(ValueError, match="empty reference bank"):
+        bank.zero_row
+    with pytest.raises(KeyError, match="no pose kept"):
+        plain.poses_of(0)
+
+
+def test_check_mode_lets_a_bank_with_poses_through_and_no_other():
+    model = _model(DENSE)
+    data, table = _batch()
+    for fine in (False, True):
+        model.dense_cfg = dict(DENSE, fine_level=fine)                             # ONE rule, whether or not fine_level is set
+        without = RefFeatureBank(model.rgb_encoder, match_threshold=0.05)
+        without._n = 40
+        with pytest.raises(NotImplementedError, match="multi_round") as e:
+            model._check_mode(dict(data, ref_bank=without, ref_rows=table), 2, 6, None, True)
+        assert "keep_poses=True" in str(e.value)
+        with_poses = RefFeatureBank(model.rgb_encoder, match_threshold=0.05, keep_poses=True)
+        with_poses._n = 40
+        bank, rows = model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), 2, 6, None, True)
+        assert bank is with_poses and rows == table
+    # ... and it still wants the DINO filter and the match summaries, as the banked dense mode does
+    model.dense_cfg = dict(DENSE, filter_enable=False)
+    with pytest.raises(NotImplementedError, match="DINO filter"):
+        model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), 2, 6, None, True)
+    model.dense_cfg = dict(DENSE)
+    no_sums = RefFeatureBank(model.rgb_encoder, keep_poses=True)
+    no_sums._n = 40
+    with pytest.raises(ValueError, match="match summaries"):
+        model._dense_bank_plan(no_sums, table, None, data["query_idx"], 2, 6)
+
+
+def _rot(axis, angle):
+    axis = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * (K @ K)
+
+
+def spread_poses(n, seed, base=None):
+    """n poses whose distances to `base` (default: identity rotation, t = (0, 0, 1)) are 0.05, 0.10, ... in a shuffled order: a
+    rotation about a random axis by 0.03 (i + 1) rad plus a translation offset of length 0.02 (i + 1)."""
+    rng = np.random.default_rng(seed)
+    base = np.eye(4) if base is None else np.asarray(base, dtype=np.float64)
+    if base[:3, 3].tolist() == [0, 0, 0]:
+        base = base.copy()
+        base[2, 3] = 1.0
+    out = np.zeros((n, 4, 4))
+    for i, m in enumerate(rng.permutation(n)):
+        d = rng.normal(size=3)
+        out[i] = np.eye(4)
+        out[i, :3, :3] = _rot(rng.normal(size=3), 0.03 * (m + 1)) @ base[:3, :3]
+        out[i, :3, 3] = base[:3, 3] + 0.02 * (m + 1) * d / np.linalg.norm(d)
+    return torch.from_numpy(out).float(), torch.from_numpy(base).float()
+
+
+def test_pose_select_host_picks_what_fetch_neighbors_picks():
+    B, N, fk = 3, 9, 4
+    poses, pred = zip(*(spread_poses(N, 40 + b) for b in range(B)))
+    bank = torch.cat(poses)                                                        # bank row b * N + n is sample b's reference n
+    pred = torch.stack(pred)
+    rows = [[b * N + n for n in range(N)] for b in range(B)]
+    cand = [list(range(N))] * B
+    dist, fine_pos, src = dense.pose_select_rows_host(bank, B * N, pred, rows, cand, fk)
+    for b in range(B):
+        gaps = np.diff(np.sort(np.asarray(dist[b])))
+        assert gaps.min() >= 1e-3, gaps                                           # the two forms may differ by rounding, not by this
+    want = dense.fetch_neighbors_by_pose_similarity(bank.reshape(B, N, 4, 4), pred.reshape(B, 1, 4, 4), topk=fk)
+    assert fine_pos == [sorted(w) for w in want.tolist()]
+    assert src == [x for b in range(B) for x in [rows[b][p] for p in fine_pos[b]] + [-(b + 1)]]
+    # the distance itself, against torch in fp64
+    g, p = bank.double().reshape(B, N, 4, 4), pred.double()[:, None]
+    tr = torch.diagonal(p[..., :3, :3] @ g[..., :3, :3].transpose(-1, -2), dim1=-2, dim2=-1).sum(-1)
+    ref = torch.acos(((tr - 1) / 2).clamp(-1, 1)) + (p[..., :3, 3] - g[..., :3, 3]).norm(dim=-1)
+    assert torch.allclose(torch.tensor(dist, dtype=torch.float64), ref, rtol=0, atol=1e-12)
+
+
+def test_pose_select_host_ranking_rules():
+    """Ties to the lower position, NaN after every number (and among NaNs by position), +inf ordinary, invalid candidates never
+    picked, fewer valid candidates than fk."""
+    bank, pred = spread_poses(6, 7)
+    bank[4] = bank[1]                                                              # an exact tie
+    bank[2, 0, 0] = float("nan")
+    bank[5, 0, 3] = float("inf")
+    rows = [[0, 1, 2, 3, 4, 5, 99, -1]]
+    cand = [[0, 1, 2, 4, 5, 6, 7, -1, 8]]                                          # slot 6: a row outside the bank, slot 7: -1, then none, then past N_max
+    dist, fine_pos, src = dense.pose_select_rows_host(bank, 6, pred[None], rows, cand, 9)
+    d = dist[0]
+    assert d[1] == d[3] and math.isnan(d[2]) and d[4] == math.inf and d[5:] == [math.inf] * 4
+    order = sorted([0, 1, 3], key=lambda c: (d[c], c))
+    assert fine_pos == [[0, 1, 2, 3, 4, -1, -1, -1, -1]] and src == [0, 1, 2, 4, 5] + [NO_VIEW] * 4 + [-1]
+    for fk, keep in ((1, order[:1]), (2, order[:2]), (3, order[:3]), (4, order[:3] + [4]), (5, order[:3] + [4, 2])):
+        got = dense.pose_select_rows_host(bank, 6, pred[None], rows, cand, fk)[1]
+        assert got == [sorted(keep)], fk
+    assert order.index(1) + 1 == order.index(3)                                    # the tied pair: the lower position first
+    # a failed coarse pose (all zeros) is an ordinary input: acos(-1/2) + |t|
+    d0 = dense.pose_select_rows_host(bank, 6, torch.zeros(1, 4, 4), rows, [[0]], 1)[0][0][0]
+    assert abs(d0 - (math.acos(-0.5) + float(bank[0, :3, 3].double().norm()))) < 1e-12
+
+
+@pytest.mark.parametrize("k,sub", [(5, 2), (4, 2), (3, 5)])
+def test_round_sources_host(k, sub):
+    B, N_max, zero = 2, 9, 77
+    rows = [[10 + n for n in range(N_max)], [30 + n for n in range(N_max)]]
+    cand = [list(range(1, 1 + k)), list(range(8, 8 - k, -1))[::-1]]
+    R = -(-k // sub)
+    for per_round in (0, 1):
+        src, view = dense.round_sources_host(rows, cand, 100, sub, zero, per_round)
+        assert len(src) == len(view) == B * R * (sub + 1)
+        for b in range(B):
+            for r in range(R):
+                for j in range(sub + 1):
+                    e = (b * R + r) * (sub + 1) + j
+                    c = r * sub + j
+                    if j == sub:
+                        assert (src[e], view[e]) == (-((b * R + r if per_round else b) + 1), k)
+                    elif c < k:
+                        assert (src[e], view[e]) == (rows[b][cand[b][c]], c)
+                    else:
+                        assert (src[e], view[e]) == (zero, -1)
+    # the view table re-packs a (B, k + 1) batch the way dense.sub_batchify does
+    x = torch.arange(B * (k + 1) * 2, dtype=torch.float32).reshape(B, k + 1, 2) + 1
+    cm = torch.zeros(B, k + 1, dtype=torch.bool)
+    cm[:, k] = True
+    want = dense._sub(x, cm, sub)
+    v = torch.tensor(dense.round_sources_host(rows, cand, 100, sub, zero, 0)[1]).reshape(B, -1)
+    got = x[torch.arange(B)[:, None], v.clamp_min(0)].masked_fill((v < 0)[..., None], 0).reshape(B, R, sub + 1, 2)
+    assert torch.equal(got, want)
+    # a -1 candidate, one past N_max and a row outside the bank are 0x7fffffff, and keep their view position
+    bad = [list(c) for c in cand]
+    bad[0][0], bad[1][k - 1] = -1, N_max
+    rows2 = [list(r) for r in rows]
+    rows2[0][cand[0][1]] = 100
+    src, view = dense.round_sources_host(rows2, bad, 100, sub, zero, 0)
+    assert src[0] == NO_VIEW and view[0] == 0
+    assert src[(1 // sub) * (sub + 1) + 1 % sub] == NO_VIEW
+    e = (R + (k - 1) // sub) * (sub + 1) + (k - 1) % sub
+    assert src[e] == NO_VIEW and view[e] == k - 1
+
+
+def test_abi_declares_both_entries_and_they_validate_before_any_launch():
+    lib = _lib.load()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "boxdreamer_hip.h")).read()
+    for name in ("bd_round_sources", "bd_pose_select_rows"):
+        assert name in _lib.EXPORTS and hasattr(lib, name)
+        assert re.search(r"^int " + name + r"\(", header, re.M), name
+    assert lib.bd_abi_version() == 9
+    p = [0x10000000 * (i + 1) for i in range(7)]        # made-up addresses: every call below returns before anything is dereferenced
+
+    def rounds(ptrs=p, R=20, B=3, N_max=9, k=5, sub=2, zero_row=19, per_round=0):
+        return lib.bd_round_sources(ptrs[0], ptrs[1], R, B, N_max, k, sub, zero_row, per_round, ptrs[2], ptrs[3], None)
+
+    assert rounds(B=0) == -1 and rounds(R=-1) == -1 and rounds(N_max=0) == -1 and rounds(k=0) == -1 and rounds(k=1025) == -1
+    assert rounds(sub=0) == -1 and rounds(sub=-3) == -1
+    assert rounds(zero_row=-1) == -1 and rounds(zero_row=20) == -1                # k = 5, sub = 2: the last round is padded
+    assert rounds(B=1 << 21, k=1024, sub=1) == -1                                 # a table past 2^31 - 1 entries
+    for i in range(4):
+        assert rounds(ptrs=[None if j == i else x for j, x in enumerate(p)]) == -5, i
+    assert rounds(ptrs=[None] * 7, k=0) == -5                                     # NULL is reported first
+
+    def select(ptrs=p, R=20, B=3, N_max=9, k=6, fk=2):
+        return lib.bd_pose_select_rows(ptrs[0], R, ptrs[1], ptrs[2], ptrs[3], B, N_max, k, fk, ptrs[4], ptrs[5], ptrs[6], None)
+
+    assert select(B=0) == -1 and select(R=-1) == -1 and select(N_max=0) == -1 and select(k=0) == -1 and select(k=1025, fk=5) == -1
+    assert select(fk=0) == -1 and select(fk=7) == -1 and select(fk=-1) == -1
+    for i in range(7):
+        assert select(ptrs=[None if j == i else x for j, x in enumerate(p)]) == -5, i
+    assert select(ptrs=[None] * 7, fk=7) == -5
