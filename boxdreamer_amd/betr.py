@@ -69,6 +69,33 @@ class _Views:
         return x.contiguous() if self.index is None else x.flatten(0, 1).index_select(0, self.index)
 
 
+class _Call:
+    """What forward() and forward_entry() share of one call on (B, T) view slots: the view counts (None: IS the uniform batch), all
+    checked before a GPU is needed; then the device of `tensors` (`masks` among them), the precision, the packed weights with the latency forms as
+    `hip_latency` says, the call's _Views, the query view per sample (BETR._one_hot_query) and the class the features are read in."""
+
+    def __init__(self, decoder, B: int, T: int, view_counts, masks, *tensors):
+        self.B, self.T, self.counts = B, T, None
+        if view_counts is not None:
+            self.counts = _lib.view_counts_list(view_counts, B)
+            _lib.check_view_counts(self.counts, T)
+            if all(c == T for c in self.counts):      # IS the uniform batch
+                self.counts = None
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.dev = _lib.same_device(*tensors)
+        self.prec = decoder.hip_precision
+        self.pid = _lib.prec_id(self.prec)
+        self.w = w = decoder._weights(self.dev, self.prec).struct
+        if self.counts is None and w.latency_mode != int(decoder.hip_latency):      # (the ragged entry points have no latency forms)
+            decoder._check_not_frozen("switching hip_latency (the workspace layout changes)")
+            w.latency_mode = int(decoder.hip_latency)
+        self.P, self.D = w.grid * w.grid, w.dim
+        self.views = _Views(decoder, B, T, self.counts, self.dev)
+        self.query_idx = decoder._one_hot_query(masks, B, T, self.counts, self.views, self.dev)
+        self.fcls = decoder.feats_class(self.prec)
+
+
 class BETR(nn.Module):
     """Box Estimation TRansformer on MI355X (HIP kernels behind the reference interface)."""
 
@@ -262,27 +289,10 @@ class BETR(nn.Module):
         (RefFeatureBank.tables / select); query_feat (B, P, C): the encoder's output for the B query crops, in sample order; masks
         (B, T) bool: the query position per sample (T: the batch's view slots); view_counts: as in forward(), a ragged batch (one
         lane).  Returns (B, 8, H, W) fp32 in [-1, 1], bit-identical to forward() on the same views; `last_logits` as there."""
-        _lib.require_gpu()
-        lib = _lib.load()
         B, T = masks.shape
-        counts = None
-        if view_counts is not None:
-            counts = _lib.view_counts_list(view_counts, B)
-            _lib.check_view_counts(counts, T)
-            if all(c == T for c in counts):
-                counts = None
         only = isinstance(query_feat, features.OperandOnly)
-        dev = _lib.same_device(entry_rows, src, masks, query_feat.operand if only else query_feat)
-        prec = self.hip_precision
-        pid = _lib.prec_id(prec)
-        w = self._weights(dev, prec).struct
-        if counts is None and w.latency_mode != int(self.hip_latency):
-            self._check_not_frozen("switching hip_latency (the workspace layout changes)")
-            w.latency_mode = int(self.hip_latency)
-        P, D = w.grid * w.grid, w.dim
-        H = self.img_size if img_size is None else int(img_size)
-        views = _Views(self, B, T, counts, dev)
-        n_views = views.n_views
+        c = _Call(self, B, T, view_counts, masks, entry_rows, src, masks, query_feat.operand if only else query_feat)
+        P, D, n_views = c.P, c.D, c.views.n_views
         if entry_rows.dtype != torch.float32 or entry_rows.dim() != 3 or tuple(entry_rows.shape[1:]) != (P, D) or not entry_rows.is_contiguous() \
                 or not 0 <= int(n_rows) <= entry_rows.shape[0]:
             raise ValueError(f"entry_rows must be a contiguous fp32 (rows >= {int(n_rows)}, {P}, {D}) tensor, got {tuple(entry_rows.shape)} {entry_rows.dtype}")
@@ -290,27 +300,36 @@ class BETR(nn.Module):
             raise ValueError(f"src must be a contiguous int32 tensor of the batch's {n_views} views, got {tuple(src.shape)} {src.dtype}")
         if tuple(query_feat.shape) != (B, P, D):
             raise ValueError(f"query_feat must be ({B}, {P}, {D}), got {tuple(query_feat.shape)}")
-        query_idx = self._one_hot_query(masks, B, T, counts, views, dev)
-        fcls = self.feats_class(prec)
-        feats16 = features.resolve(query_feat, fcls, _lib.planes(fcls) * B * P * D, dev)
+        feats16 = features.resolve(query_feat, c.fcls, _lib.planes(c.fcls) * B * P * D, c.dev)
         if feats16 is None:
-            raise ValueError(f"forward_entry needs the HIP encoder's operand copy of the query features in this decoder's feature class ({fcls})")
-        plane = operand.plane_offset(feats16, fcls)
-        logits = torch.empty((B, 8, H, H), dtype=torch.float32, device=dev)
+            raise ValueError(f"forward_entry needs the HIP encoder's operand copy of the query features in this decoder's feature class ({c.fcls})")
+        return self._launch(c, True, (_lib.ptr(entry_rows), int(n_rows), _lib.ptr(src)), feats16, self.img_size if img_size is None else int(img_size))
+
+    def _launch(self, c: _Call, banked: bool, source, feats16, H: int):
+        """The one decoder launch of a call, uniform (sub-batch lanes) or ragged, on the workspace it asks for.  `source`: the C entry
+        point's arguments that name the entry tokens' source -- (heat maps, their dtype), or banked: (entry rows, rows in use, src)."""
+        lib, w, B, T, pid, views = c.lib, c.w, c.B, c.T, c.pid, c.views
+        logits = torch.empty((B, 8, H, H), dtype=torch.float32, device=c.dev)
         heat = torch.empty_like(logits)
-        if counts is None:
-            lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, prec)
-            ws = self._workspace(max(lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, 1),
-                                     lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, lanes)), dev)
-            _lib.check(lib.bd_decoder_forward_entry(w, _lib.ptr(entry_rows), int(n_rows), _lib.ptr(src), _lib.ptr(feats16), plane,
-                                                    _lib.ptr(query_idx), B, T, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(),
-                                                    pid, lanes, _lib.stream()), "bd_decoder_forward_entry")
+        feats = (_lib.ptr(feats16), operand.plane_offset(feats16, c.fcls))
+        if c.counts is None:
+            lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, c.prec)
+            if banked:
+                name = "bd_decoder_forward_entry"
+                need = max(lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, 1), lib.bd_decoder_entry_workspace_bytes(w, B, T, pid, lanes))
+            else:
+                name = "bd_decoder_forward_lanes"
+                need = max(lib.bd_decoder_workspace_bytes(w, B, T, pid), lib.bd_decoder_workspace_bytes_lanes(w, B, T, pid, lanes))
+            ws = self._workspace(need, c.dev)
+            rc = getattr(lib, name)(w, *source, *feats, _lib.ptr(c.query_idx), B, T, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws),
+                                    ws.numel(), pid, lanes, _lib.stream())
         else:
-            ws = self._workspace(lib.bd_decoder_entry_workspace_bytes_ragged(w, n_views, B, pid), dev)
-            _lib.check(lib.bd_decoder_forward_entry_ragged(w, _lib.ptr(entry_rows), int(n_rows), _lib.ptr(src), _lib.ptr(feats16), plane,
-                                                           _lib.ptr(views.view_start), _lib.ptr(query_idx), B, n_views, views.max_views, H,
-                                                           _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, _lib.stream()),
-                       "bd_decoder_forward_entry_ragged")
+            name = "bd_decoder_forward_entry_ragged" if banked else "bd_decoder_forward_ragged"
+            need = (lib.bd_decoder_entry_workspace_bytes_ragged if banked else lib.bd_decoder_workspace_bytes_ragged)(w, views.n_views, B, pid)
+            ws = self._workspace(need, c.dev)
+            rc = getattr(lib, name)(w, *source, *feats, _lib.ptr(views.view_start), _lib.ptr(c.query_idx), B, views.n_views, views.max_views, H,
+                                    _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, _lib.stream())
+        _lib.check(rc, name)
         self.last_logits = logits
         return heat
 
@@ -333,29 +352,14 @@ class BETR(nn.Module):
         assert H == W == self.img_size, f"H and W should be equal to img_size {self.img_size}, got {H}x{W}"
         if pretrain_rgb_feat is None:
             raise NotImplementedError("the MI355X path requires pretrained RGB features (use_pretrained=True)")
-        counts = None
-        if view_counts is not None:
-            counts = _lib.view_counts_list(view_counts, B)
-            _lib.check_view_counts(counts, T)
-            if all(c == T for c in counts):      # IS the uniform batch
-                counts = None
-        _lib.require_gpu()
-        lib = _lib.load()
         only = isinstance(pretrain_rgb_feat, features.OperandOnly)       # an operand copy with no fp32 tensor behind it (a reference bank)
-        dev = _lib.same_device(pose_feat, rgbs, masks, pretrain_rgb_feat.operand if only else pretrain_rgb_feat)
-        prec = self.hip_precision
-        pid = _lib.prec_id(prec)
-        w = self._weights(dev, prec).struct
-        if counts is None and w.latency_mode != int(self.hip_latency):      # (the ragged entry point has no latency forms)
-            self._check_not_frozen("switching hip_latency (the workspace layout changes)")
-            w.latency_mode = int(self.hip_latency)
-        P, D = w.grid * w.grid, w.dim
-        if masks.dtype != torch.bool or masks.shape != (B, T):
-            raise ValueError("masks must be a (B, T) bool tensor")
+        # (the reference writes the query token through `pose_feat[masks] = ...` (betr.py:286-290), which fails unless every sample marks
+        # exactly one view; argmax would silently pick view 0 for an empty row: _one_hot_query)
+        c = _Call(self, B, T, view_counts, masks, pose_feat, rgbs, masks, pretrain_rgb_feat.operand if only else pretrain_rgb_feat)
+        counts, views, fcls, P, D = c.counts, c.views, c.fcls, c.P, c.D
         if tuple(pose_feat.shape) != (B, T, self.box_dim, H, W):
             raise ValueError(f"pose_feat must be (B, T, {self.box_dim}, H, W) = {(B, T, self.box_dim, H, W)}, got "
                              f"{tuple(pose_feat.shape)}")
-        views = _Views(self, B, T, counts, dev)
         n_views, shape = views.n_views, tuple(pretrain_rgb_feat.shape)
         # `packed`: the features are the n_views views in order (a uniform batch's always are); else padded (B, T_max, P, D) of a ragged one
         packed = counts is None or shape == (n_views, P, D)
@@ -363,14 +367,10 @@ class BETR(nn.Module):
             raise ValueError(f"pretrain_rgb_feat must be (B, T, {P}, {D}), got {shape}")
         if not packed and shape != (B, T, P, D):
             raise ValueError(f"pretrain_rgb_feat must be packed ({n_views}, {P}, {D}) or padded ({B}, {T}, {P}, {D}), got {shape}")
-        # the reference writes the query token through `pose_feat[masks] = ...` (betr.py:286-290), which fails unless
-        # every sample marks exactly one view; argmax would silently pick view 0 for an empty row
-        query_idx = self._one_hot_query(masks, B, T, counts, views, dev)
-        fcls = self.feats_class(prec)
         if only and not packed:
             raise ValueError(f"operand-only features of a ragged batch must be packed ({n_views}, {P}, {D}), got {shape}")
         # (padded features of a ragged batch are never taken as they are: their copy holds the padded slots too)
-        feats16 = features.resolve(pretrain_rgb_feat, fcls, _lib.planes(fcls) * n_views * P * D, dev) if packed else None
+        feats16 = features.resolve(pretrain_rgb_feat, fcls, _lib.planes(fcls) * n_views * P * D, c.dev) if packed else None
         if feats16 is None:   # features without an operand copy (computed elsewhere, copied, sliced): explicit re-cast
             self.recast_count += 1
             if self.recast_count == 1:
@@ -379,21 +379,4 @@ class BETR(nn.Module):
             f32 = pretrain_rgb_feat if packed else views.pack(pretrain_rgb_feat)
             feats16 = hip_ops.to_operand(f32.reshape(n_views * P, D).float(), fcls)
         pose = views.pack(pose_feat)                       # the valid views only: [n_views, 8, H, W]
-        plane = operand.plane_offset(feats16, fcls)
-        logits = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
-        heat = torch.empty_like(logits)
-        if counts is None:
-            lanes = _lib.resolve_lanes(self.hip_lanes, B * T, B, prec)
-            ws = self._workspace(max(lib.bd_decoder_workspace_bytes(w, B, T, pid),
-                                     lib.bd_decoder_workspace_bytes_lanes(w, B, T, pid, lanes)), dev)
-            _lib.check(lib.bd_decoder_forward_lanes(w, _lib.ptr(pose), _lib.dtype_id(pose), _lib.ptr(feats16), plane, _lib.ptr(query_idx),
-                                                    B, T, H, _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, lanes,
-                                                    _lib.stream()), "bd_decoder_forward_lanes")
-        else:
-            ws = self._workspace(lib.bd_decoder_workspace_bytes_ragged(w, n_views, B, pid), dev)
-            _lib.check(lib.bd_decoder_forward_ragged(w, _lib.ptr(pose), _lib.dtype_id(pose), _lib.ptr(feats16), plane,
-                                                     _lib.ptr(views.view_start), _lib.ptr(query_idx), B, n_views, views.max_views, H,
-                                                     _lib.ptr(logits), _lib.ptr(heat), _lib.ptr(ws), ws.numel(), pid, _lib.stream()),
-                       "bd_decoder_forward_ragged")
-        self.last_logits = logits
-        return heat
+        return self._launch(c, False, (_lib.ptr(pose), _lib.dtype_id(pose)), feats16, H)

@@ -352,25 +352,31 @@ EncBufs carve_encoder(const bd_dino_weights* w, int n, int prec, void* ws) {
     return e;
 }
 
-struct DecBufs { void *a_heat, *t1, *qtok; float *t2, *rgb, *proj; BlockBufs blk; size_t bytes; };
+// The decoder's one workspace layout, in take() order: a_heat, t1, t2, rgb, qtok, proj, blk.  What a call lacks takes no bytes and does
+// not move the offset:
+//   heat   the heat-map patch operand, and the adapter's buffers (t1, t2, rgb) on all n_views * P rows (the heat-map entry of
+//          decoder_chain, bd_decoder_entry_tokens); without it the adapter runs on the B * P query rows (the banked entry)
+//   stack  the head's buffers (qtok, proj) and the block buffers on all n_views * P rows (every forward; not bd_decoder_entry_tokens)
 // n_views: views of the whole batch (B * T, or the sum of a ragged batch's view counts): every buffer is sized by token rows, none by T
-DecBufs carve_decoder_views(const bd_betr_weights* w, int64_t n_views, int B, int prec, void* ws) {
+struct DecBufs { void *a_heat, *t1, *qtok; float *t2, *rgb, *proj; BlockBufs blk; size_t bytes; };
+DecBufs carve_decoder(const bd_betr_weights* w, int64_t n_views, int B, int prec, void* ws, bool heat, bool stack) {
     Carver c{(unsigned char*)ws, 0};
     const int np = planes_of(prec), P = w->grid * w->grid, D = w->dim;
-    const int64_t Mb = n_views * P, Mq = (int64_t)B * P;
+    const int64_t Mb = n_views * P, Mq = (int64_t)B * P, Ma = heat ? Mb : Mq;
     const int F = w->patch * w->patch * w->box_dim;
-    DecBufs d;
-    d.a_heat = c.take((size_t)Mb * w->kpad * 2 * np);
-    d.t1 = c.take((size_t)Mb * D * 2 * np);
-    d.t2 = (float*)c.take((size_t)Mb * D * 4);
-    d.rgb = (float*)c.take((size_t)Mb * D * 4);
-    d.qtok = c.take((size_t)Mq * D * 2 * np);
-    d.proj = (float*)c.take((size_t)Mq * F * 4);
-    d.blk = carve_block(c, Mb, D, np, w->latency_mode != 0);
+    DecBufs d{};
+    if (heat) d.a_heat = c.take((size_t)Mb * w->kpad * 2 * np);
+    d.t1 = c.take((size_t)Ma * D * 2 * np);
+    d.t2 = (float*)c.take((size_t)Ma * D * 4);
+    d.rgb = (float*)c.take((size_t)Ma * D * 4);
+    if (stack) {
+        d.qtok = c.take((size_t)Mq * D * 2 * np);
+        d.proj = (float*)c.take((size_t)Mq * F * 4);
+        d.blk = carve_block(c, Mb, D, np, w->latency_mode != 0);
+    }
     d.bytes = c.off + 256;
     return d;
 }
-DecBufs carve_decoder(const bd_betr_weights* w, int B, int T, int prec, void* ws) { return carve_decoder_views(w, (int64_t)B * T, B, prec, ws); }
 
 inline bool bad_prec(int prec) {
     return prec != BD_PREC_BF16 && prec != BD_PREC_F16 && prec != BD_PREC_BF16X3 && prec != BD_PREC_FP8 &&
@@ -433,69 +439,132 @@ extern "C" int bd_encoder_forward(const bd_dino_weights* w, const void* images, 
 
 extern "C" size_t bd_decoder_workspace_bytes(const bd_betr_weights* w, int B, int T, int prec) {
     if (!w || B <= 0 || T <= 0 || bad_prec(prec)) return 0;
-    return carve_decoder(w, B, T, prec, nullptr).bytes;
+    return carve_decoder(w, (int64_t)B * T, B, prec, nullptr, true, true).bytes;
 }
 
 namespace {
-// The decoder chain on n_views * P packed token rows.  view_start == NULL: the uniform batch of bd_decoder_forward (n_views = B * T, every
-// sample T views).  view_start != NULL: the ragged batch of bd_decoder_forward_ragged -- the same launches; attention, the query-token
-// substitution and the query-row gather take the sample boundaries from the offsets, everything else is row-wise and sees M = n_views * P.
-int decoder_chain(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16, int64_t feats16_plane,
-                  const int32_t* view_start, const int32_t* query_idx, int B, int n_views, int T, int size, float* logits, float* heat,
-                  void* workspace, size_t workspace_bytes, int wprec, void* stream) {
-    const int prec = gemm_prec(wprec);
-    const DecBufs d = carve_decoder_views(w, n_views, B, prec, workspace);
+
+// operand classes of the Linears outside the blocks (F16C8 family: per-Linear promotion, include/boxdreamer_hip.h)
+struct MiscClasses { int a1, a2, be, bp; };
+inline MiscClasses misc_classes(const bd_betr_weights* w, int prec) {
+    const int pm0 = (prec == BD_PREC_F16C8 || prec == BD_PREC_FP8) ? w->promote_misc : 0;
+    const int pmisc = (pm0 & BD_PROMOTE_ADAPTER_FC1) ? (pm0 | BD_PROMOTE_ADAPTER_FC2) : pm0;
+    return {lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC1), lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC2),
+            lin_class(prec, pmisc, BD_PROMOTE_BBOX_EMB), lin_class(prec, pmisc, BD_PROMOTE_BBOX_PROJ)};
+}
+
+// K6 adapter on M rows: rgb = LN_noaffine(fc2(gelu(fc1(feat))))  (betr.py:313-317); feats16 arrives in the class of adapter fc1
+int adapter_rows(const bd_betr_weights* w, const MiscClasses& c, const void* feats16, int64_t feats16_plane, int M, void* t1, float* t2,
+                 float* rgb, int prec, void* stream) {
+    const int D = w->dim;
+    const int64_t pD = (int64_t)M * D;
+    {
+        bd_gemm_args g = gemm_args(feats16, D, feats16_plane, w->adapter_fc1, D, D, t1, D, pD, handoff_kind(c.a1, c.a2), M, D, BD_ACT_GELU);
+        BD_TRY(bd_gemm(&g, c.a1, stream));
+    }
+    {
+        bd_gemm_args g = gemm_args(t1, D, pD, w->adapter_fc2, D, D, t2, D, 0, 1, M, D, BD_ACT_NONE);
+        BD_TRY(bd_gemm(&g, c.a2, stream));
+    }
+    return bd_layernorm(t2, D, nullptr, nullptr, w->adapter_ln_eps, nullptr, 0, rgb, D, M, D, 0, 0, 0, prec, stream);
+}
+
+// K7+K8 on n_views views: x = bbox_emb(patchify(bbox_feat)) + rgb + pos, the heat-map patch embedding fused with its two additions
+// (betr.py:324-329, 367-399)
+int entry_rows(const bd_betr_weights* w, const MiscClasses& c, const void* bbox_feat, int in_dtype, int n_views, int size, void* a_heat,
+               const float* rgb, float* x, void* stream) {
+    const int P = w->grid * w->grid, D = w->dim, M = n_views * P;
+    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, a_heat, (int64_t)M * w->kpad, n_views, w->box_dim, size, w->patch, w->kpad, c.be, stream));
+    bd_gemm_args g = gemm_args(a_heat, w->kpad, (int64_t)M * w->kpad, w->bbox_emb, w->kpad, D, x, D, 0, 1, M, w->kpad, BD_ACT_NONE);
+    g.addtab = w->pos_table; g.tab_rows = P;
+    g.resid = rgb; g.ldr = D;
+    return bd_gemm(&g, c.be, stream);
+}
+
+// Where a call's decoder-entry tokens come from; exactly one of the two sources is set.
+//   heat maps (bank == false): bbox_feat in in_dtype, one map per view; feats16 then covers all n_views views
+//   a bank    (bank == true):  banked entry rows bank_x [bank_views, P, D] and the views' source table src (include/boxdreamer_hip.h,
+//                              bd_assemble_entry_tokens_from); feats16 then covers the B query views.  `first`: a sub-batch lane's samples
+//                              are [first, first + B) of the batch, and src names their queries by the batch's numbering
+struct EntrySource {
+    bool bank;
+    const void* bbox_feat; int in_dtype;
+    const float* bank_x; int bank_views; const int32_t* src; int first;
+};
+inline EntrySource heat_source(const void* bbox_feat, int in_dtype) { return {false, bbox_feat, in_dtype, nullptr, 0, nullptr, 0}; }
+inline EntrySource bank_source(const float* bank_x, int bank_views, const int32_t* src, int first) {
+    return {true, nullptr, 0, bank_x, bank_views, src, first};
+}
+
+inline bool bad_betr_shape(const bd_betr_weights* w, int size) {
+    return size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 || w->kpad < w->patch * w->patch * w->box_dim;
+}
+
+// The argument checks of every decoder entry point, in one order; nothing is dereferenced but w, nothing enqueued.  `stack`: the call runs
+// the block stack and the head (a forward; bd_decoder_entry_tokens only builds rows: B = n_views free-standing views, T = 1).  `ragged`:
+// the samples' views are given by view_start, T is the largest per-sample count.  `out`: any one of the call's outputs.
+int check_decoder_call(const bd_betr_weights* w, const EntrySource& e, const void* feats16, const int32_t* view_start, const int32_t* query_idx,
+                       bool ragged, bool stack, int B, int64_t n_views, int T, int size, const void* out, const void* workspace, int wprec) {
+    if (!w || !feats16 || !out || !workspace) return BD_ERR_NULL;
+    if (e.bank ? (!e.src || (e.bank_views > 0 && !e.bank_x)) : !e.bbox_feat) return BD_ERR_NULL;
+    if (stack && (!query_idx || !w->blocks || (ragged && !view_start))) return BD_ERR_NULL;
+    if (bad_prec(wprec)) return BD_ERR_DTYPE;
+    if (!e.bank && (e.in_dtype < 0 || e.in_dtype > 2)) return BD_ERR_DTYPE;
+    if (B <= 0 || T <= 0 || n_views < B || (e.bank && e.bank_views < 0) || bad_betr_shape(w, size)) return BD_ERR_SHAPE;
+    if (ragged) {
+        if (T > n_views - (B - 1) || (int64_t)T * B < n_views) return BD_ERR_SHAPE;       // no set of B view counts has this sum and maximum
+        if ((w->grid * w->grid) % 128 || w->dim / w->heads != 96) return BD_ERR_SHAPE;      // what bd_attention_varlen takes
+    }
+    if (n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;             // token rows are counted in int
+    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    return BD_OK;
+}
+
+// The decoder chain on n_views * P packed token rows, for every forward.  Entry tokens by their source: from heat maps, the adapter runs on
+// all rows, the heat-map embedding adds rgb + pos and the query rows are substituted; from a bank, the adapter runs on the B * P query rows
+// and one launch assembles the stream from the banked rows and the query rows -- then the same Stack, the same plan, the same head.
+// !ragged: a uniform batch (n_views = B * T, every sample T views).  ragged: the same launches; attention, the query-token substitution and
+// the query-row gather take the sample boundaries from view_start, everything else is row-wise and sees M = n_views * P.
+int decoder_chain(const bd_betr_weights* w, const EntrySource& e, const void* feats16, int64_t feats16_plane, const int32_t* view_start,
+                  const int32_t* query_idx, bool ragged, int B, int64_t views, int T, int size, float* logits, float* heat, void* workspace,
+                  size_t workspace_bytes, int wprec, void* stream) {
+    BD_TRY(check_decoder_call(w, e, feats16, view_start, query_idx, ragged, true, B, views, T, size, logits ? logits : heat, workspace, wprec));
+    const int prec = gemm_prec(wprec), n_views = (int)views;
+    const DecBufs d = carve_decoder(w, n_views, B, prec, workspace, !e.bank, true);
     if (workspace_bytes < d.bytes) return BD_ERR_WORKSPACE;
     const int P = w->grid * w->grid, D = w->dim, F = w->patch * w->patch * w->box_dim;
     const int Mb = n_views * P, Mq = B * P;
-    const int64_t pD = (int64_t)Mb * D;
     // K9: joint self-attention over all T*P tokens of a sample; the last block runs the query view's rows only past K / V, on d.t2 (dead
     // since the adapter) as its compact stream
     Stack s{};
     s.blocks = w->blocks; s.depth = w->depth; s.b = d.blk;
     s.M = Mb; s.batch = B; s.seq = T * P; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.rms_eps = w->rms_eps;
-    s.lat = !view_start && w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
-    s.view_start = view_start; s.n_views = n_views; s.max_views = T;      // (ragged: T is the largest per-sample view count)
+    s.lat = !ragged && w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
+    s.view_start = ragged ? view_start : nullptr; s.n_views = n_views; s.max_views = T;      // (ragged: T is the largest per-sample view count)
     std::vector<BlockPlan> sched;
     BD_TRY(plan_stack(s, wprec, sched));
     if (d.blk.sk && hipMemsetAsync(d.blk.sk, 0, d.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
 
-    // operand classes of the Linears outside the blocks (F16C8 family: per-Linear promotion, include/boxdreamer_hip.h)
-    const int pm0 = (prec == BD_PREC_F16C8 || prec == BD_PREC_FP8) ? w->promote_misc : 0;
-    const int pmisc = (pm0 & BD_PROMOTE_ADAPTER_FC1) ? (pm0 | BD_PROMOTE_ADAPTER_FC2) : pm0;
-    const int c_a1 = lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC1), c_a2 = lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC2);
-    const int c_be = lin_class(prec, pmisc, BD_PROMOTE_BBOX_EMB), c_bp = lin_class(prec, pmisc, BD_PROMOTE_BBOX_PROJ);
-    // K6 adapter: LN_noaffine(fc2(gelu(fc1(feat))))  (betr.py:313-317); feats16 arrives in the class of adapter fc1
-    {
-        bd_gemm_args g = gemm_args(feats16, D, feats16_plane, w->adapter_fc1, D, D, d.t1, D, pD, handoff_kind(c_a1, c_a2), Mb, D, BD_ACT_GELU);
-        BD_TRY(bd_gemm(&g, c_a1, stream));
+    const MiscClasses c = misc_classes(w, prec);
+    if (e.bank) {
+        // K6 on the query views only, then the stream: banked rows as they are, the query rows (query_token + rgb) + pos  (betr.py:286-290)
+        BD_TRY(adapter_rows(w, c, feats16, feats16_plane, Mq, d.t1, d.t2, d.rgb, prec, stream));
+        BD_TRY(bd_assemble_entry_tokens_from(e.bank_x, e.bank_views, d.rgb, e.first, B, w->pos_table, w->query_token, e.src, d.blk.x, n_views, P,
+                                             D, stream));
+    } else {
+        BD_TRY(adapter_rows(w, c, feats16, feats16_plane, Mb, d.t1, d.t2, d.rgb, prec, stream));
+        BD_TRY(entry_rows(w, c, e.bbox_feat, e.in_dtype, n_views, size, d.a_heat, d.rgb, d.blk.x, stream));
+        if (ragged) BD_TRY(bd_query_substitute_varlen(d.blk.x, d.rgb, w->pos_table, w->query_token, view_start, query_idx, B, P, D, stream));
+        else BD_TRY(bd_query_substitute(d.blk.x, d.rgb, w->pos_table, w->query_token, query_idx, B, T, P, D, stream));
     }
-    {
-        bd_gemm_args g = gemm_args(d.t1, D, pD, w->adapter_fc2, D, D, d.t2, D, 0, 1, Mb, D, BD_ACT_NONE);
-        BD_TRY(bd_gemm(&g, c_a2, stream));
-    }
-    BD_TRY(bd_layernorm(d.t2, D, nullptr, nullptr, w->adapter_ln_eps, nullptr, 0, d.rgb, D, Mb, D, 0, 0, 0, prec, stream));
-    // K7+K8: heatmap patch embedding fused with  + rgb + pos  (betr.py:324-329, 367-399)
-    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, d.a_heat, (int64_t)Mb * w->kpad, n_views, w->box_dim, size, w->patch,
-                                w->kpad, c_be, stream));
-    {
-        bd_gemm_args g = gemm_args(d.a_heat, w->kpad, (int64_t)Mb * w->kpad, w->bbox_emb, w->kpad, D, d.blk.x, D, 0, 1,
-                                   Mb, w->kpad, BD_ACT_NONE);
-        g.addtab = w->pos_table; g.tab_rows = P;
-        g.resid = d.rgb; g.ldr = D;
-        BD_TRY(bd_gemm(&g, c_be, stream));
-    }
-    if (view_start) BD_TRY(bd_query_substitute_varlen(d.blk.x, d.rgb, w->pos_table, w->query_token, view_start, query_idx, B, P, D, stream));
-    else BD_TRY(bd_query_substitute(d.blk.x, d.rgb, w->pos_table, w->query_token, query_idx, B, T, P, D, stream));
     for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
     // K10: head on the query view's tokens (no final norm, betr.py:298-306)
-    BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c_bp, stream));
+    BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c.bp, stream));
     {
         bd_gemm_args g = gemm_args(d.qtok, D, (int64_t)Mq * D, w->bbox_proj, D, F, d.proj, F, 0, 1, Mq, D, BD_ACT_NONE);
-        BD_TRY(bd_gemm(&g, c_bp, stream));
+        BD_TRY(bd_gemm(&g, c.bp, stream));
     }
-    BD_TRY(bd_unpatchify_sigmoid(d.proj, logits, heat, B, w->box_dim, size, w->patch, stream));
-    return BD_OK;
+    return bd_unpatchify_sigmoid(d.proj, logits, heat, B, w->box_dim, size, w->patch, stream);
 }
 }  // namespace
 
@@ -503,36 +572,21 @@ extern "C" int bd_decoder_forward(const bd_betr_weights* w, const void* bbox_fea
                                   int64_t feats16_plane, const int32_t* query_idx, int B, int T, int size,
                                   float* logits, float* heat, void* workspace, size_t workspace_bytes, int wprec,
                                   void* stream) {
-    if (!w || !bbox_feat || !feats16 || !query_idx || !workspace || !w->blocks || (!logits && !heat)) return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (B <= 0 || T <= 0 || size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 ||
-        w->kpad < w->patch * w->patch * w->box_dim)
-        return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    return decoder_chain(w, bbox_feat, in_dtype, feats16, feats16_plane, nullptr, query_idx, B, B * T, T, size, logits, heat, workspace,
-                         workspace_bytes, wprec, stream);
+    return decoder_chain(w, heat_source(bbox_feat, in_dtype), feats16, feats16_plane, nullptr, query_idx, false, B, (int64_t)B * T, T, size,
+                         logits, heat, workspace, workspace_bytes, wprec, stream);
 }
 
 extern "C" size_t bd_decoder_workspace_bytes_ragged(const bd_betr_weights* w, int n_views, int B, int prec) {
     if (!w || B <= 0 || n_views < B || bad_prec(prec)) return 0;
-    return carve_decoder_views(w, n_views, B, prec, nullptr).bytes;
+    return carve_decoder(w, n_views, B, prec, nullptr, true, true).bytes;
 }
 
 extern "C" int bd_decoder_forward_ragged(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
                                          int64_t feats16_plane, const int32_t* view_start, const int32_t* query_view, int B, int n_views,
                                          int max_views, int size, float* logits, float* heat, void* workspace, size_t workspace_bytes,
                                          int wprec, void* stream) {
-    if (!w || !bbox_feat || !feats16 || !view_start || !query_view || !workspace || !w->blocks || (!logits && !heat)) return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (in_dtype < 0 || in_dtype > 2) return BD_ERR_DTYPE;
-    if (B <= 0 || n_views < B || max_views <= 0 || max_views > n_views - (B - 1) || (int64_t)max_views * B < n_views ||
-        size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 || w->kpad < w->patch * w->patch * w->box_dim)
-        return BD_ERR_SHAPE;
-    if ((w->grid * w->grid) % 128 || w->dim / w->heads != 96) return BD_ERR_SHAPE;      // what bd_attention_varlen takes
-    if ((int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    return decoder_chain(w, bbox_feat, in_dtype, feats16, feats16_plane, view_start, query_view, B, n_views, max_views, size, logits, heat,
-                         workspace, workspace_bytes, wprec, stream);
+    return decoder_chain(w, heat_source(bbox_feat, in_dtype), feats16, feats16_plane, view_start, query_view, true, B, n_views, max_views,
+                         size, logits, heat, workspace, workspace_bytes, wprec, stream);
 }
 
 // ----------------------------------------------------------------------------------------------------------------------------
@@ -579,6 +633,30 @@ inline int lane_count(int lanes, int units) { return lanes < 1 ? 1 : (lanes > kM
 inline int lane_units(int units, int lanes, int l) { return units / lanes + (l < units % lanes ? 1 : 0); }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+// Lane l of nl: its units [first, first + count) of the batch and its slice [woff, woff + bytes) of the workspace.  bytes_of(count) is
+// the aligned carve size of a lane of `count` units: the laned forwards and the *_workspace_bytes*_lanes totals split with the same one.
+struct LaneSlice { int first, count; size_t woff, bytes; };
+template <class F> LaneSlice lane_slice(int units, int nl, int l, const F& bytes_of) {
+    LaneSlice s{0, lane_units(units, nl, l), 0, 0};
+    for (int j = 0; j < l; ++j) {
+        s.first += lane_units(units, nl, j);
+        s.woff += bytes_of(lane_units(units, nl, j));
+    }
+    s.bytes = bytes_of(s.count);
+    return s;
+}
+template <class F> size_t lanes_total(int units, int nl, const F& bytes_of) {
+    const LaneSlice last = lane_slice(units, nl, nl - 1, bytes_of);
+    return last.woff + last.bytes;
+}
+inline auto encoder_lane_bytes(const bd_dino_weights* w, int prec) {
+    return [=](int n) { return align256(carve_encoder(w, n, gemm_prec(prec), nullptr).bytes); };
+}
+// (a lane of b samples at T views each; heat: the heat-map entry's layout, else the banked entry's -- carve_decoder)
+inline auto decoder_lane_bytes(const bd_betr_weights* w, int T, int prec, bool heat) {
+    return [=](int b) { return align256(carve_decoder(w, (int64_t)b * T, b, gemm_prec(prec), nullptr, heat, true).bytes); };
+}
+
 // element offset e0 into a 16-bit operand buffer of class `cls`: plane 0 moves by e0 elements; F16C8's one-byte lo8 plane (which
 // starts `plane` 2-byte units behind plane 0) moves by e0 BYTES, i.e. the plane distance seen from the moved base shrinks by e0 / 2
 inline void operand_slice(const void* base, int64_t plane, int cls, int64_t e0, const void** b, int64_t* p) {
@@ -620,10 +698,7 @@ extern "C" int bd_lanes_prepare(void) {
 
 extern "C" size_t bd_encoder_workspace_bytes_lanes(const bd_dino_weights* w, int n_images, int prec, int lanes) {
     if (!w || n_images <= 0 || bad_prec(prec)) return 0;
-    const int nl = lane_count(lanes, n_images);
-    size_t total = 0;
-    for (int l = 0; l < nl; ++l) total += align256(carve_encoder(w, lane_units(n_images, nl, l), gemm_prec(prec), nullptr).bytes);
-    return total;
+    return lanes_total(n_images, lane_count(lanes, n_images), encoder_lane_bytes(w, prec));
 }
 
 extern "C" int bd_encoder_forward_lanes(const bd_dino_weights* w, const void* images, int img_dtype, int n_images, int size,
@@ -636,32 +711,24 @@ extern "C" int bd_encoder_forward_lanes(const bd_dino_weights* w, const void* im
     if (!images || !workspace) return BD_ERR_NULL;
     if (img_dtype < 0 || img_dtype > 2) return BD_ERR_DTYPE;
     if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    if (workspace_bytes < bd_encoder_workspace_bytes_lanes(w, n_images, wprec, nl)) return BD_ERR_WORKSPACE;
-    const int prec = gemm_prec(wprec), fcls = w->feats_prec ? w->feats_prec : prec;
+    const auto lane_bytes = encoder_lane_bytes(w, wprec);
+    if (workspace_bytes < lanes_total(n_images, nl, lane_bytes)) return BD_ERR_WORKSPACE;
+    const int fcls = w->feats_prec ? w->feats_prec : gemm_prec(wprec);
     const int64_t PD = (int64_t)w->grid * w->grid * w->dim, img_elems = (int64_t)3 * size * size;
     return run_lanes(nl, (hipStream_t)stream, [&](int l, hipStream_t s) {
-        int first = 0;
-        size_t woff = 0;
-        for (int j = 0; j < l; ++j) {
-            first += lane_units(n_images, nl, j);
-            woff += align256(carve_encoder(w, lane_units(n_images, nl, j), prec, nullptr).bytes);
-        }
-        const int n = lane_units(n_images, nl, l);
+        const LaneSlice ln = lane_slice(n_images, nl, l, lane_bytes);
         const void* f16 = nullptr;
         int64_t plane = feats16_plane;
-        operand_slice(feats16, feats16_plane, fcls, first * PD, &f16, &plane);
-        return bd_encoder_forward(w, (const unsigned char*)images + first * img_elems * dtype_bytes(img_dtype), img_dtype, n, size,
-                                  feats32 ? feats32 + first * PD : nullptr, const_cast<void*>(f16), plane,
-                                  (unsigned char*)workspace + woff, align256(carve_encoder(w, n, prec, nullptr).bytes), wprec, s);
+        operand_slice(feats16, feats16_plane, fcls, ln.first * PD, &f16, &plane);
+        return bd_encoder_forward(w, (const unsigned char*)images + ln.first * img_elems * dtype_bytes(img_dtype), img_dtype, ln.count, size,
+                                  feats32 ? feats32 + ln.first * PD : nullptr, const_cast<void*>(f16), plane,
+                                  (unsigned char*)workspace + ln.woff, ln.bytes, wprec, s);
     });
 }
 
 extern "C" size_t bd_decoder_workspace_bytes_lanes(const bd_betr_weights* w, int B, int T, int prec, int lanes) {
     if (!w || B <= 0 || T <= 0 || bad_prec(prec)) return 0;
-    const int nl = lane_count(lanes, B);
-    size_t total = 0;
-    for (int l = 0; l < nl; ++l) total += align256(carve_decoder(w, lane_units(B, nl, l), T, gemm_prec(prec), nullptr).bytes);
-    return total;
+    return lanes_total(B, lane_count(lanes, B), decoder_lane_bytes(w, T, prec, true));
 }
 
 extern "C" int bd_decoder_forward_lanes(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
@@ -670,189 +737,59 @@ extern "C" int bd_decoder_forward_lanes(const bd_betr_weights* w, const void* bb
     const int nl = lane_count(lanes, B);
     if (nl <= 1 || !w) return bd_decoder_forward(w, bbox_feat, in_dtype, feats16, feats16_plane, query_idx, B, T, size, logits, heat,
                                                  workspace, workspace_bytes, wprec, stream);
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (!bbox_feat || !feats16 || !query_idx || !workspace) return BD_ERR_NULL;
-    if (in_dtype < 0 || in_dtype > 2) return BD_ERR_DTYPE;
-    if (T <= 0) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    if (workspace_bytes < bd_decoder_workspace_bytes_lanes(w, B, T, wprec, nl)) return BD_ERR_WORKSPACE;
-    const int prec = gemm_prec(wprec);
-    const int pm0 = (prec == BD_PREC_F16C8 || prec == BD_PREC_FP8) ? w->promote_misc : 0;
-    const int fcls = lin_class(prec, pm0, BD_PROMOTE_ADAPTER_FC1);       // the class bd_decoder_forward reads feats16 in
+    // (the whole batch's arguments and the laned workspace total are checked before the fork: a bad call records no event)
+    BD_TRY(check_decoder_call(w, heat_source(bbox_feat, in_dtype), feats16, nullptr, query_idx, false, true, B, (int64_t)B * T, T, size,
+                              logits ? logits : heat, workspace, wprec));
+    const auto lane_bytes = decoder_lane_bytes(w, T, wprec, true);
+    if (workspace_bytes < lanes_total(B, nl, lane_bytes)) return BD_ERR_WORKSPACE;
+    const int fcls = misc_classes(w, gemm_prec(wprec)).a1;       // the class bd_decoder_forward reads feats16 in
     const int64_t PD = (int64_t)w->grid * w->grid * w->dim, view_elems = (int64_t)w->box_dim * size * size;
     return run_lanes(nl, (hipStream_t)stream, [&](int l, hipStream_t s) {
-        int first = 0;
-        size_t woff = 0;
-        for (int j = 0; j < l; ++j) {
-            first += lane_units(B, nl, j);
-            woff += align256(carve_decoder(w, lane_units(B, nl, j), T, prec, nullptr).bytes);
-        }
-        const int b = lane_units(B, nl, l);
+        const LaneSlice ln = lane_slice(B, nl, l, lane_bytes);
+        const int64_t v0 = (int64_t)ln.first * T;                  // the lane's first view
         const void* f16 = nullptr;
         int64_t plane = feats16_plane;
-        operand_slice(feats16, feats16_plane, fcls, (int64_t)first * T * PD, &f16, &plane);
-        return bd_decoder_forward(w, (const unsigned char*)bbox_feat + (int64_t)first * T * view_elems * dtype_bytes(in_dtype), in_dtype,
-                                  f16, plane, query_idx + first, b, T, size, logits ? logits + first * view_elems : nullptr,
-                                  heat ? heat + first * view_elems : nullptr, (unsigned char*)workspace + woff,
-                                  align256(carve_decoder(w, b, T, prec, nullptr).bytes), wprec, s);
+        operand_slice(feats16, feats16_plane, fcls, v0 * PD, &f16, &plane);
+        return bd_decoder_forward(w, (const unsigned char*)bbox_feat + v0 * view_elems * dtype_bytes(in_dtype), in_dtype, f16, plane,
+                                  query_idx + ln.first, ln.count, T, size, logits ? logits + ln.first * view_elems : nullptr,
+                                  heat ? heat + ln.first * view_elems : nullptr, (unsigned char*)workspace + ln.woff, ln.bytes, wprec, s);
     });
 }
 
 // ----------------------------------------------------------------------------------------------------------------------------
 // Decoder-entry tokens kept in a bank (include/boxdreamer_hip.h).  A reference's entry row -- bbox_emb(patchify(bbox_feat)) + pos +
 // adapter(feat), betr.py:313-329 and :367-399 -- is row-wise and independent of the query: bd_decoder_entry_tokens computes it once,
-// with decoder_chain's own five launches, and bd_decoder_forward_entry runs the adapter on the query rows alone, assembles the token
-// stream from the banked rows in one launch and goes on with decoder_chain's block stack and head.
-namespace {
-
-// operand classes of the Linears outside the blocks, as decoder_chain derives them (per-Linear promotion, include/boxdreamer_hip.h)
-struct MiscClasses { int a1, a2, be, bp; };
-inline MiscClasses misc_classes(const bd_betr_weights* w, int prec) {
-    const int pm0 = (prec == BD_PREC_F16C8 || prec == BD_PREC_FP8) ? w->promote_misc : 0;
-    const int pmisc = (pm0 & BD_PROMOTE_ADAPTER_FC1) ? (pm0 | BD_PROMOTE_ADAPTER_FC2) : pm0;
-    return {lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC1), lin_class(prec, pmisc, BD_PROMOTE_ADAPTER_FC2),
-            lin_class(prec, pmisc, BD_PROMOTE_BBOX_EMB), lin_class(prec, pmisc, BD_PROMOTE_BBOX_PROJ)};
-}
-
-// K6 adapter on M rows: rgb = LN_noaffine(fc2(gelu(fc1(feat))))  (betr.py:313-317); feats16 arrives in the class of adapter fc1
-int adapter_rows(const bd_betr_weights* w, const MiscClasses& c, const void* feats16, int64_t feats16_plane, int M, void* t1, float* t2,
-                 float* rgb, int prec, void* stream) {
-    const int D = w->dim;
-    const int64_t pD = (int64_t)M * D;
-    {
-        bd_gemm_args g = gemm_args(feats16, D, feats16_plane, w->adapter_fc1, D, D, t1, D, pD, handoff_kind(c.a1, c.a2), M, D, BD_ACT_GELU);
-        BD_TRY(bd_gemm(&g, c.a1, stream));
-    }
-    {
-        bd_gemm_args g = gemm_args(t1, D, pD, w->adapter_fc2, D, D, t2, D, 0, 1, M, D, BD_ACT_NONE);
-        BD_TRY(bd_gemm(&g, c.a2, stream));
-    }
-    return bd_layernorm(t2, D, nullptr, nullptr, w->adapter_ln_eps, nullptr, 0, rgb, D, M, D, 0, 0, 0, prec, stream);
-}
-
-struct TokBufs { void *a_heat, *t1; float *t2, *rgb; size_t bytes; };
-TokBufs carve_entry_tokens(const bd_betr_weights* w, int64_t n_views, int prec, void* ws) {
-    Carver c{(unsigned char*)ws, 0};
-    const int np = planes_of(prec), D = w->dim;
-    const int64_t M = n_views * w->grid * w->grid;
-    TokBufs t;
-    t.a_heat = c.take((size_t)M * w->kpad * 2 * np);
-    t.t1 = c.take((size_t)M * D * 2 * np);
-    t.t2 = (float*)c.take((size_t)M * D * 4);
-    t.rgb = (float*)c.take((size_t)M * D * 4);
-    t.bytes = c.off + 256;
-    return t;
-}
-
-// the entry decoder's buffers: the adapter's on the B * P query rows (t2 doubles as the last block's compact stream, as in
-// decoder_chain), the head's, and the block buffers on all n_views * P rows -- no heat-map patch operand
-struct EntryBufs { void *t1, *qtok; float *t2, *rgb, *proj; BlockBufs blk; size_t bytes; };
-EntryBufs carve_entry_views(const bd_betr_weights* w, int64_t n_views, int B, int prec, void* ws) {
-    Carver c{(unsigned char*)ws, 0};
-    const int np = planes_of(prec), P = w->grid * w->grid, D = w->dim;
-    const int64_t Mb = n_views * P, Mq = (int64_t)B * P;
-    const int F = w->patch * w->patch * w->box_dim;
-    EntryBufs d;
-    d.t1 = c.take((size_t)Mq * D * 2 * np);
-    d.t2 = (float*)c.take((size_t)Mq * D * 4);
-    d.rgb = (float*)c.take((size_t)Mq * D * 4);
-    d.qtok = c.take((size_t)Mq * D * 2 * np);
-    d.proj = (float*)c.take((size_t)Mq * F * 4);
-    d.blk = carve_block(c, Mb, D, np, w->latency_mode != 0);
-    d.bytes = c.off + 256;
-    return d;
-}
-
-inline bool bad_betr_shape(const bd_betr_weights* w, int size) {
-    return size != w->grid * w->patch || w->dim % w->heads || w->kpad % 64 || w->box_dim != 8 || w->kpad < w->patch * w->patch * w->box_dim;
-}
-
-// decoder_chain with its token stream assembled from banked entry rows: the same Stack, the same plan, the same head.
-int entry_chain(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src, const void* feats16, int64_t feats16_plane,
-                const int32_t* view_start, const int32_t* query_idx, int first, int B, int n_views, int T, int size, float* logits,
-                float* heat, void* workspace, size_t workspace_bytes, int wprec, void* stream) {
-    const int prec = gemm_prec(wprec);
-    const EntryBufs d = carve_entry_views(w, n_views, B, prec, workspace);
-    if (workspace_bytes < d.bytes) return BD_ERR_WORKSPACE;
-    const int P = w->grid * w->grid, D = w->dim, F = w->patch * w->patch * w->box_dim;
-    const int Mb = n_views * P, Mq = B * P;
-    Stack s{};
-    s.blocks = w->blocks; s.depth = w->depth; s.b = d.blk;
-    s.M = Mb; s.batch = B; s.seq = T * P; s.D = D; s.heads = w->heads; s.ln_eps = w->ln_eps; s.rms_eps = w->rms_eps;
-    s.lat = !view_start && w->latency_mode && Mb <= BD_SPLITK_MAX_ROWS; s.query_idx = query_idx; s.P = P; s.xc = d.t2;
-    s.view_start = view_start; s.n_views = n_views; s.max_views = T;
-    std::vector<BlockPlan> sched;
-    BD_TRY(plan_stack(s, wprec, sched));
-    if (d.blk.sk && hipMemsetAsync(d.blk.sk, 0, d.blk.sk_flag_bytes, (hipStream_t)stream) != hipSuccess) return BD_ERR_WORKSPACE;
-    const MiscClasses c = misc_classes(w, prec);
-    // K6 on the query views only, then the stream: banked rows as they are, the query rows (query_token + rgb) + pos  (betr.py:286-290)
-    BD_TRY(adapter_rows(w, c, feats16, feats16_plane, Mq, d.t1, d.t2, d.rgb, prec, stream));
-    // (`first`: a sub-batch lane's samples are [first, first + B) of the batch, and src names their queries by the batch's numbering)
-    BD_TRY(bd_assemble_entry_tokens_from(bank_x, bank_views, d.rgb, first, B, w->pos_table, w->query_token, src, d.blk.x, n_views, P, D, stream));
-    for (const BlockPlan& b : sched) BD_TRY(run_block(b, s, stream));
-    // K10: head on the query view's tokens (no final norm, betr.py:298-306)
-    BD_TRY(bd_gather_query_tokens(d.t2, nullptr, d.qtok, (int64_t)Mq * D, B, 1, P, D, c.bp, stream));
-    {
-        bd_gemm_args g = gemm_args(d.qtok, D, (int64_t)Mq * D, w->bbox_proj, D, F, d.proj, F, 0, 1, Mq, D, BD_ACT_NONE);
-        BD_TRY(bd_gemm(&g, c.bp, stream));
-    }
-    return bd_unpatchify_sigmoid(d.proj, logits, heat, B, w->box_dim, size, w->patch, stream);
-}
-
-int entry_forward_one(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src, const void* feats16,
-                      int64_t feats16_plane, const int32_t* query_idx, int first, int B, int T, int size, float* logits, float* heat,
-                      void* workspace, size_t workspace_bytes, int wprec, void* stream) {
-    if (!w || !src || !feats16 || !query_idx || !workspace || !w->blocks || (!logits && !heat) || (bank_views > 0 && !bank_x)) return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (B <= 0 || T <= 0 || bank_views < 0 || bad_betr_shape(w, size)) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    return entry_chain(w, bank_x, bank_views, src, feats16, feats16_plane, nullptr, query_idx, first, B, B * T, T, size, logits, heat, workspace,
-                       workspace_bytes, wprec, stream);
-}
-
-}  // namespace
+// with the heat-map entry's own five launches (adapter_rows, entry_rows), and bd_decoder_forward_entry[_ragged] is decoder_chain with the
+// bank as its entry source: the adapter on the query rows alone, one launch that assembles the token stream from the banked rows, then
+// the one block stack and head.
 
 extern "C" size_t bd_decoder_entry_tokens_workspace_bytes(const bd_betr_weights* w, int n_views, int prec) {
     if (!w || n_views <= 0 || bad_prec(prec)) return 0;
-    return carve_entry_tokens(w, n_views, gemm_prec(prec), nullptr).bytes;
+    return carve_decoder(w, n_views, 0, gemm_prec(prec), nullptr, true, false).bytes;
 }
 
 extern "C" int bd_decoder_entry_tokens(const bd_betr_weights* w, const void* bbox_feat, int in_dtype, const void* feats16,
                                        int64_t feats16_plane, int n_views, int size, float* x_out, void* workspace,
                                        size_t workspace_bytes, int wprec, void* stream) {
-    if (!w || !bbox_feat || !feats16 || !x_out || !workspace) return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (in_dtype < 0 || in_dtype > 2) return BD_ERR_DTYPE;
-    if (n_views <= 0 || bad_betr_shape(w, size) || (int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
+    // (n_views free-standing views: each its own sample of one view)
+    BD_TRY(check_decoder_call(w, heat_source(bbox_feat, in_dtype), feats16, nullptr, nullptr, false, false, n_views, n_views, 1, size, x_out,
+                              workspace, wprec));
     const int prec = gemm_prec(wprec);
-    const TokBufs t = carve_entry_tokens(w, n_views, prec, workspace);
+    const DecBufs t = carve_decoder(w, n_views, 0, prec, workspace, true, false);
     if (workspace_bytes < t.bytes) return BD_ERR_WORKSPACE;
-    const int P = w->grid * w->grid, D = w->dim, M = n_views * P;
     const MiscClasses c = misc_classes(w, prec);
-    BD_TRY(adapter_rows(w, c, feats16, feats16_plane, M, t.t1, t.t2, t.rgb, prec, stream));
-    // K7+K8: heatmap patch embedding fused with  + rgb + pos  (betr.py:324-329, 367-399)
-    BD_TRY(bd_patchify_heatmaps(bbox_feat, in_dtype, t.a_heat, (int64_t)M * w->kpad, n_views, w->box_dim, size, w->patch, w->kpad, c.be, stream));
-    bd_gemm_args g = gemm_args(t.a_heat, w->kpad, (int64_t)M * w->kpad, w->bbox_emb, w->kpad, D, x_out, D, 0, 1, M, w->kpad, BD_ACT_NONE);
-    g.addtab = w->pos_table; g.tab_rows = P;
-    g.resid = t.rgb; g.ldr = D;
-    return bd_gemm(&g, c.be, stream);
+    BD_TRY(adapter_rows(w, c, feats16, feats16_plane, n_views * w->grid * w->grid, t.t1, t.t2, t.rgb, prec, stream));
+    return entry_rows(w, c, bbox_feat, in_dtype, n_views, size, t.a_heat, t.rgb, x_out, stream);
 }
 
 extern "C" size_t bd_decoder_entry_workspace_bytes_ragged(const bd_betr_weights* w, int n_views, int B, int prec) {
     if (!w || B <= 0 || n_views < B || bad_prec(prec)) return 0;
-    return carve_entry_views(w, n_views, B, gemm_prec(prec), nullptr).bytes;
+    return carve_decoder(w, n_views, B, gemm_prec(prec), nullptr, false, true).bytes;
 }
 
 extern "C" size_t bd_decoder_entry_workspace_bytes(const bd_betr_weights* w, int B, int T, int prec, int lanes) {
     if (!w || B <= 0 || T <= 0 || bad_prec(prec)) return 0;
-    const int nl = lane_count(lanes, B);
-    size_t total = 0;
-    for (int l = 0; l < nl; ++l) {
-        const int b = lane_units(B, nl, l);
-        total += align256(carve_entry_views(w, (int64_t)b * T, b, gemm_prec(prec), nullptr).bytes);
-    }
-    return total;
+    return lanes_total(B, lane_count(lanes, B), decoder_lane_bytes(w, T, prec, false));
 }
 
 extern "C" int bd_decoder_forward_entry(const bd_betr_weights* w, const float* bank_x, int bank_views, const int32_t* src,
@@ -860,31 +797,25 @@ extern "C" int bd_decoder_forward_entry(const bd_betr_weights* w, const float* b
                                         float* logits, float* heat, void* workspace, size_t workspace_bytes, int wprec, int lanes,
                                         void* stream) {
     const int nl = lane_count(lanes, B);
-    if (nl <= 1 || !w) return entry_forward_one(w, bank_x, bank_views, src, feats16, feats16_plane, query_idx, 0, B, T, size, logits, heat,
-                                                workspace, workspace_bytes, wprec, stream);
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (!src || !feats16 || !query_idx || !workspace) return BD_ERR_NULL;
-    if (T <= 0) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    if (workspace_bytes < bd_decoder_entry_workspace_bytes(w, B, T, wprec, nl)) return BD_ERR_WORKSPACE;
-    const int prec = gemm_prec(wprec);
-    const int fcls = misc_classes(w, prec).a1;       // the class the adapter's first Linear reads feats16 in
+    const int64_t n_views = (int64_t)B * T;
+    if (nl <= 1 || !w) return decoder_chain(w, bank_source(bank_x, bank_views, src, 0), feats16, feats16_plane, nullptr, query_idx, false, B,
+                                            n_views, T, size, logits, heat, workspace, workspace_bytes, wprec, stream);
+    // (the whole batch's arguments and the laned workspace total are checked before the fork: a bad call records no event)
+    BD_TRY(check_decoder_call(w, bank_source(bank_x, bank_views, src, 0), feats16, nullptr, query_idx, false, true, B, n_views, T, size,
+                              logits ? logits : heat, workspace, wprec));
+    const auto lane_bytes = decoder_lane_bytes(w, T, wprec, false);
+    if (workspace_bytes < lanes_total(B, nl, lane_bytes)) return BD_ERR_WORKSPACE;
+    const int fcls = misc_classes(w, gemm_prec(wprec)).a1;       // the class the adapter's first Linear reads feats16 in
     const int64_t PD = (int64_t)w->grid * w->grid * w->dim, map_elems = (int64_t)w->box_dim * size * size;
-    const auto lane_bytes = [&](int b) { return align256(carve_entry_views(w, (int64_t)b * T, b, prec, nullptr).bytes); };
     return run_lanes(nl, (hipStream_t)stream, [&](int l, hipStream_t s) {
-        int first = 0;
-        size_t woff = 0;
-        for (int j = 0; j < l; ++j) {
-            first += lane_units(B, nl, j);
-            woff += lane_bytes(lane_units(B, nl, j));
-        }
-        const int b = lane_units(B, nl, l);
+        const LaneSlice ln = lane_slice(B, nl, l, lane_bytes);
         const void* f16 = nullptr;
         int64_t plane = feats16_plane;
-        operand_slice(feats16, feats16_plane, fcls, (int64_t)first * PD, &f16, &plane);     // (one query view per sample)
-        return entry_forward_one(w, bank_x, bank_views, src + (int64_t)first * T, f16, plane, query_idx + first, first, b, T, size,
-                                 logits ? logits + first * map_elems : nullptr, heat ? heat + first * map_elems : nullptr,
-                                 (unsigned char*)workspace + woff, lane_bytes(b), wprec, s);
+        operand_slice(feats16, feats16_plane, fcls, ln.first * PD, &f16, &plane);     // (one query view per sample)
+        return decoder_chain(w, bank_source(bank_x, bank_views, src + (int64_t)ln.first * T, ln.first), f16, plane, nullptr,
+                             query_idx + ln.first, false, ln.count, (int64_t)ln.count * T, T, size,
+                             logits ? logits + ln.first * map_elems : nullptr, heat ? heat + ln.first * map_elems : nullptr,
+                             (unsigned char*)workspace + ln.woff, ln.bytes, wprec, s);
     });
 }
 
@@ -892,15 +823,6 @@ extern "C" int bd_decoder_forward_entry_ragged(const bd_betr_weights* w, const f
                                                const void* feats16, int64_t feats16_plane, const int32_t* view_start,
                                                const int32_t* query_view, int B, int n_views, int max_views, int size, float* logits,
                                                float* heat, void* workspace, size_t workspace_bytes, int wprec, void* stream) {
-    if (!w || !src || !feats16 || !view_start || !query_view || !workspace || !w->blocks || (!logits && !heat) || (bank_views > 0 && !bank_x))
-        return BD_ERR_NULL;
-    if (bad_prec(wprec)) return BD_ERR_DTYPE;
-    if (B <= 0 || bank_views < 0 || n_views < B || max_views <= 0 || max_views > n_views - (B - 1) || (int64_t)max_views * B < n_views ||
-        bad_betr_shape(w, size))
-        return BD_ERR_SHAPE;
-    if ((w->grid * w->grid) % 128 || w->dim / w->heads != 96) return BD_ERR_SHAPE;      // what bd_attention_varlen takes
-    if ((int64_t)n_views * w->grid * w->grid >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
-    if ((uintptr_t)workspace & 255) return BD_ERR_ALIGN;
-    return entry_chain(w, bank_x, bank_views, src, feats16, feats16_plane, view_start, query_view, 0, B, n_views, max_views, size, logits, heat,
-                       workspace, workspace_bytes, wprec, stream);
+    return decoder_chain(w, bank_source(bank_x, bank_views, src, 0), feats16, feats16_plane, view_start, query_view, true, B, n_views,
+                         max_views, size, logits, heat, workspace, workspace_bytes, wprec, stream);
 }

@@ -4,6 +4,7 @@ rules of a forward over such a bank (all checked before any launch, so on a box 
 bd_assemble_entry_tokens / bd_decoder_entry_tokens / bd_decoder_forward_entry."""
 import os
 import re
+import types
 import warnings
 
 import pytest
@@ -273,3 +274,70 @@ def test_abi_declares_the_entries_and_they_validate_before_any_launch():
     assert lib.bd_decoder_forward_entry(None, p[0], 4, p[1], p[2], 0, p[3], 2, 3, 224, p[4], p[4], p[5], 0, 0, 1, None) == -5
     assert lib.bd_decoder_forward_entry(w, p[0], 4, None, p[2], 0, p[3], 2, 3, 224, p[4], p[4], p[5], 0, 0, 2, None) == -5
     assert lib.bd_decoder_forward_entry_ragged(w, p[0], 4, p[1], p[2], 0, None, p[3], 2, 5, 3, 224, p[4], p[4], p[5], 0, 0, None) == -5
+
+
+# ---- one table of bad arguments through every validating decoder entry point.  Made-up addresses: every call returns before anything
+# is dereferenced or launched (a call that went on would fault here).
+_ADDR = {k: 0x10000000 * (i + 1) for i, k in enumerate(("bbox", "f16", "qidx", "vs", "src", "bank", "out", "ws"))}
+_GOOD = dict(_ADDR, in_dtype=2, prec=0, B=2, T=3, n_views=5, max_views=3, bank_views=4, size=224, ws_bytes=1 << 40)
+# entry point -> (the call, the pointers it takes, reads a heat map, kind of batch)
+_ENTRY_POINTS = {
+    "forward": (lambda lib, w, a: lib.bd_decoder_forward(w, a.bbox, a.in_dtype, a.f16, 0, a.qidx, a.B, a.T, a.size, a.out, a.out, a.ws,
+                                                         a.ws_bytes, a.prec, None),
+                ("bbox", "f16", "qidx", "out", "ws"), True, "uniform"),
+    "forward_lanes(2)": (lambda lib, w, a: lib.bd_decoder_forward_lanes(w, a.bbox, a.in_dtype, a.f16, 0, a.qidx, a.B, a.T, a.size, a.out, a.out,
+                                                                        a.ws, a.ws_bytes, a.prec, 2, None),
+                         ("bbox", "f16", "qidx", "out", "ws"), True, "uniform"),
+    "forward_ragged": (lambda lib, w, a: lib.bd_decoder_forward_ragged(w, a.bbox, a.in_dtype, a.f16, 0, a.vs, a.qidx, a.B, a.n_views, a.max_views,
+                                                                       a.size, a.out, a.out, a.ws, a.ws_bytes, a.prec, None),
+                       ("bbox", "f16", "vs", "qidx", "out", "ws"), True, "ragged"),
+    "forward_entry(1)": (lambda lib, w, a: lib.bd_decoder_forward_entry(w, a.bank, a.bank_views, a.src, a.f16, 0, a.qidx, a.B, a.T, a.size, a.out,
+                                                                        a.out, a.ws, a.ws_bytes, a.prec, 1, None),
+                         ("bank", "src", "f16", "qidx", "out", "ws"), False, "uniform"),
+    "forward_entry(2)": (lambda lib, w, a: lib.bd_decoder_forward_entry(w, a.bank, a.bank_views, a.src, a.f16, 0, a.qidx, a.B, a.T, a.size, a.out,
+                                                                        a.out, a.ws, a.ws_bytes, a.prec, 2, None),
+                         ("bank", "src", "f16", "qidx", "out", "ws"), False, "uniform"),
+    "forward_entry_ragged": (lambda lib, w, a: lib.bd_decoder_forward_entry_ragged(w, a.bank, a.bank_views, a.src, a.f16, 0, a.vs, a.qidx, a.B,
+                                                                                   a.n_views, a.max_views, a.size, a.out, a.out, a.ws,
+                                                                                   a.ws_bytes, a.prec, None),
+                             ("bank", "src", "f16", "vs", "qidx", "out", "ws"), False, "ragged"),
+    "entry_tokens": (lambda lib, w, a: lib.bd_decoder_entry_tokens(w, a.bbox, a.in_dtype, a.f16, 0, a.n_views, a.size, a.out, a.ws, a.ws_bytes,
+                                                                   a.prec, None),
+                     ("bbox", "f16", "out", "ws"), True, "tokens"),
+}
+# case -> (expected code, what it changes: for every kind of batch, or per kind)
+_BAD = {
+    **{f"NULL {p}": (-5, {p: None}) for p in ("w", *_ADDR)},
+    "bad prec": (-2, {"prec": 99}),
+    "in_dtype 3": (-2, {"in_dtype": 3}),                 # bd_decoder_forward too, before anything is enqueued
+    "B 0": (-1, {"uniform": {"B": 0}, "ragged": {"B": 0}, "tokens": {"n_views": 0}}),
+    "size 200": (-1, {"size": 200}),
+    "misaligned workspace": (-3, {"ws": _ADDR["ws"] + 16}),
+    "ws_bytes 1024": (-4, {"ws_bytes": 1024}),
+    # P = 256 token rows per view: 2^23 views are 2^31 rows -- the uniform entry points too
+    "2^31 token rows": (-1, {"uniform": {"B": 1 << 12, "T": 1 << 11}, "ragged": {"n_views": 1 << 23, "max_views": 1 << 22},
+                             "tokens": {"n_views": 1 << 23}}),
+}
+
+
+@pytest.fixture(scope="module")
+def betr_struct():
+    from boxdreamer_amd import pack, synth
+    pk = pack.pack_betr(synth.betr_state_dict(1234, 1), "bf16", "cpu", 8)
+    yield pk.struct
+    del pk
+
+
+def _applies(entry, case):
+    _, pointers, reads_heat_map, _ = _ENTRY_POINTS[entry]
+    return (case[5:] in ("w", *pointers)) if case.startswith("NULL ") else (reads_heat_map or case != "in_dtype 3")
+
+
+@pytest.mark.parametrize("entry,case", [(e, c) for e in _ENTRY_POINTS for c in _BAD if _applies(e, c)])
+def test_every_decoder_entry_point_rejects_the_same_bad_arguments_with_the_same_codes(betr_struct, entry, case):
+    lib = _lib.load()
+    call, _, _, kind = _ENTRY_POINTS[entry]
+    code, change = _BAD[case]
+    change = change[kind] if set(change) <= {"uniform", "ragged", "tokens"} else change
+    args = types.SimpleNamespace(**dict(_GOOD, **change))
+    assert call(lib, None if case == "NULL w" else betr_struct, args) == code, (entry, case)

@@ -2,6 +2,7 @@
 reject bad arguments before any launch, the ragged workspace equals the uniform one at equal views, and the host-side bookkeeping
 (packing index, offsets, the attention work list the kernels derive from the offsets, the facade's validation)."""
 import ctypes
+import json
 import os
 
 import pytest
@@ -83,6 +84,60 @@ def test_decoder_ragged_rejects_bad_arguments_and_sizes_its_workspace(betr_weigh
             assert lib.bd_decoder_workspace_bytes_ragged(w, B * T, B, pid) == lib.bd_decoder_workspace_bytes(w, B, T, pid) > 0
     # sized by views, not by B x the longest sample
     assert lib.bd_decoder_workspace_bytes_ragged(w, 30, 5, 13) < lib.bd_decoder_workspace_bytes(w, 5, 17, 13)
+
+
+PRECS = ("bf16", "fp16", "bf16x3", "fp8", "f16c8", "f16c8_qk16", "f16x3", "f16x3_attn_x3")
+
+
+def _workspace_row(lib, wd, we, B, T, pid):
+    """Every *_workspace_bytes* entry point of the whole-path calls at one batch, in the fixture's column order."""
+    n = B * T
+    return ([lib.bd_decoder_workspace_bytes(wd, B, T, pid), lib.bd_decoder_workspace_bytes_ragged(wd, n, B, pid)] +
+            [lib.bd_decoder_workspace_bytes_lanes(wd, B, T, pid, l) for l in (1, 2, 4)] +
+            [lib.bd_decoder_entry_tokens_workspace_bytes(wd, n, pid), lib.bd_decoder_entry_workspace_bytes_ragged(wd, n, B, pid)] +
+            [lib.bd_decoder_entry_workspace_bytes(wd, B, T, pid, l) for l in (1, 2, 4)] +
+            [lib.bd_encoder_workspace_bytes(we, n, pid)] + [lib.bd_encoder_workspace_bytes_lanes(we, n, pid, l) for l in (1, 2, 4)])
+
+
+def test_workspace_bytes_are_pinned_and_share_one_layout(betr_weights):
+    """The workspace sizes are part of the contract with callers that size their blobs once (graph capture, the facade's cache): every
+    entry point returns the bytes recorded in tests/golden/workspace_bytes.json (computed once, before the decoder's carvers became
+    one), and the sizes relate as the one take() order -- a_heat, t1, t2, rgb, qtok, proj, blk -- implies."""
+    lib = _lib.load()
+    wd = betr_weights.struct
+    enc = pack.pack_dino(synth.dino_state_dict(4321, 1), "bf16", "cpu", 12)
+    we = enc.struct
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")))
+    try:
+        for prec in PRECS:
+            for B, T, lat in ((1, 2, 0), (1, 2, 1), (3, 6, 0), (32, 6, 0), (2, 17, 0)):
+                wd.latency_mode = we.latency_mode = lat
+                row = _workspace_row(lib, wd, we, B, T, _lib.prec_id(prec))
+                assert row == want[f"{prec} B={B} T={T} latency={lat}"], (prec, B, T, lat)
+    finally:
+        wd.latency_mode = we.latency_mode = 0
+
+    def takes(off, sizes):                                   # csrc/forward.hip Carver.take, then the 256 spare bytes of every total
+        for s in sizes:
+            off = (off + 255) // 256 * 256 + s
+        return off + 256
+
+    P, D, F = wd.grid * wd.grid, wd.dim, wd.patch * wd.patch * wd.box_dim
+    for prec in PRECS:
+        pid = _lib.prec_id(prec)
+        e = 2 * (2 if prec not in ("bf16", "fp16", "fp8") else 1)          # bytes per element of a 16-bit operand buffer (both planes)
+        for B, T in ((1, 2), (3, 6), (32, 6), (2, 17)):
+            n = B * T
+            Mb, Mq = n * P, B * P
+            stack = [Mq * D * e, Mq * F * 4,                               # the head: qtok, proj
+                     Mb * D * 4, Mb * D * e, Mb * 3 * D * e, Mb * D * e, Mb * 4 * D * e, Mb * ((D + 95) // 96) * 8]      # the blocks' buffers
+            tokens = lib.bd_decoder_entry_tokens_workspace_bytes(wd, n, pid)
+            assert tokens == takes(0, [Mb * wd.kpad * e, Mb * D * e, Mb * D * 4, Mb * D * 4])
+            assert lib.bd_decoder_workspace_bytes_ragged(wd, n, B, pid) == takes(tokens - 256, stack)
+            ragged = lib.bd_decoder_entry_workspace_bytes_ragged(wd, n, B, pid)
+            assert ragged == takes(0, [Mq * D * e, Mq * D * 4, Mq * D * 4] + stack)                # no a_heat, the adapter on the query rows
+            assert 0 <= lib.bd_decoder_entry_workspace_bytes(wd, B, T, pid, 1) - ragged < 256
+            assert 0 <= lib.bd_decoder_workspace_bytes_lanes(wd, B, T, pid, 1) - lib.bd_decoder_workspace_bytes(wd, B, T, pid) < 256
 
 
 def test_packing_index_and_offsets():
