@@ -117,10 +117,18 @@ template <> __device__ __forceinline__ void store_cvt<fp8e4, 4>(fp8e4* dst, cons
 //   q8 of A (derived in the GEMM's registers) = e4m3(clamp(hi, +-448)): an element beyond 448 loses accuracy only in its
 //       q_A . lo_W term, i.e. degrades to what a single f16 pass gives for that one element;
 //   lo8 = e4m3(clamp((x - hi) 2^D, +-448)): exact for |x| < 512, partially saturated beyond (f16's ulp there exceeds 448 / 2^D).
-// Saturation costs nothing: with MODE.FP16_OVFL set, gfx950's fp8 conversions (v_cvt_scalef32_pk_fp8_f16, v_cvt_pk_fp8_f32) clamp
+// Saturation costs nothing: with MODE.FP16_OVFL set, gfx950's fp8 conversions (v_cvt_scalef32_pk_fp8_f16, v_cvt_pk_fp8_f32, and lo8's
+// v_cvt_scalef32_pk_fp8_f32: tools/lo8_scaled_cvt_probe.hip) clamp
 // to +-448 and f32 -> f16 conversions to +-65504 instead of producing NaN / inf (measured: tools/fp8_sat_probe.hip; an explicit
 // v_pk_max / v_pk_min pair per f16 pair in the GEMM's K loop cost 3.2 % of the strict step).  Every kernel that produces or consumes
 // the class calls bd_saturating_conversions() first; the mode is per-wave state and dies with the wave.
+// Beyond +-65504 the residual is still taken against the fp32 value: hi is the saturated f16 and lo (lo8) the saturated image of what it
+// left over (hip_ops.to_operand packs the same way).  FP16_OVFL clamps FINITE values only; a true Inf stays Inf in f16 and becomes NaN in
+// e4m3, so nothing on the way to a conversion may overflow fp32 (f16c8_lo8_pk below).
+// Tested (tests/test_gpu_range.py): every store of every kernel that calls this, on values known exactly in front of the store -- ties
+// with an even and an odd lower neighbour in eight binades, +- one fp32 ulp, subnormals of the class, MAX, MAX + half an ulp, 7e4 .. fp32's
+// largest value, lo8 ties / subnormals / saturation -- bit for bit against hip_ops.to_operand, which tests/test_operand_host.py pins
+// against an integer restatement of the rounding.
 __device__ __forceinline__ void bd_saturating_conversions() {
     __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1);      // hwreg(HW_REG_MODE, 23, 1) = MODE.FP16_OVFL
 }
@@ -157,6 +165,9 @@ __device__ __forceinline__ float wave_sum(float v) {
 //   1 + erf(z) = erfc(-z);  erfc(|z|) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2),  t = 1 / (1 + p |z|)
 // (Abramowitz & Stegun 7.1.26, |abs err| <= 1.5e-7 -- fp32-rounding class).  ~12 VALU ops + v_exp + v_rcp per
 // element instead of ocml erff's branchy ~40: the fc1 epilogue was costing 40 % of that GEMM.
+// Tested element by element on [-12, 12] and out to +-1e4 (tests/test_gpu_range.py): |err| <= 1e-7 |x| + 2^-20 |gelu(x)| in fp32, plus half
+// a unit of the class through the two-plane / F16C8 stores, whose planes are the packing of the fp32 result bit for bit; measured
+// 4e-7 at most (profiles/gelu_epilogue_error.md), exactly x from x = 10 on.
 // (All GELU forms: every fused multiply-add is written out and contraction is off inside, so that the arithmetic does not
 // depend on the inlining context -- two kernels computing the same row must agree bit for bit.)
 __device__ __forceinline__ float gelu_erf(float x) {
@@ -208,6 +219,9 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
 // form: the fc1 epilogue is VALU-bound (64 GELUs per lane per 256x128 tile against 192 MFMAs), so this is what lets it
 // hide under the next tile's MFMAs.  Only the single-pass modes use it; the strict split-bf16 mode and every fp32
 // output keep gelu_erf.  The argument is clamped to +-8 where the fitted polynomial is still monotone (Phi saturates).
+// Beyond the fit interval the result is x times the clamped Phi: measured to |x| = 1e4 (profiles/gelu_epilogue_error.md) it is x to within
+// half an f16 ulp above the clamp and at most one f16 subnormal below it.  tests/test_gpu_range.py holds the 5.4e-5 on [-9, 9] element by
+// element through the f16 store, and |gelu(x)| <= 2e-6 |x| / |gelu(x) - x| <= 2e-6 |x| outside; both zeros give a zero.
 __device__ __forceinline__ float gelu_fast(float x) {
 #pragma clang fp contract(off)
     const float xc = __builtin_amdgcn_fmed3f(x, -8.0f, 8.0f);
@@ -220,6 +234,10 @@ __device__ __forceinline__ float gelu_fast(float x) {
 // |abs err| <= 1.6e-4 in fp32 arithmetic = half a bf16 ulp at |gelu| = 0.08.  v_exp_f32 / v_rcp_f32 issue at quarter
 // rate, so gelu_fast spends most of its time in them; this form is ~2x cheaper.  fp16 results keep gelu_fast (an f16 ulp
 // is 8x finer), fp32 / split-bf16 results keep gelu_erf.
+// The 1.6e-4 holds on [-4, 4] only.  Past the clamp the factor 0.5 + xc P(xc^2) is a constant that is not exactly 0 or 1: measured
+// (profiles/gelu_epilogue_error.md) gelu(x) = -5.95e-7 x for x <= -4 -- 5.9e-4 at x = -1000, 5.9e-3 at -1e4 -- and x to within half a bf16
+// ulp for x >= 4.  That is below half a bf16 ulp of anything it is added to; tests/test_gpu_range.py asserts |gelu(x)| <= 2e-6 |x| there,
+// the 1.6e-4 inside, element by element through the bf16 and e4m3 stores.
 __device__ __forceinline__ f32x2 gelu_poly2(f32x2 x) {
 #pragma clang fp contract(off)
     f32x2 xc;
@@ -294,18 +312,28 @@ __device__ __forceinline__ int64_t f16c8_lo_index(int64_t e) {            // byt
     return (e & ~(int64_t)31) + (((g & 1) << 4) | ((g >> 1) << 3));          // a = g >> 1, h = g & 1  ->  16 h + 8 a
 }
 template <int N>
-__device__ __forceinline__ void f16c8_split(const float (&v)[N], _Float16 (&hi)[N], float (&lo_scaled)[N]) {
+__device__ __forceinline__ void f16c8_split(const float (&v)[N], _Float16 (&hi)[N], float (&lo)[N]) {
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         // (MODE.FP16_OVFL is set by the calling kernel: hi saturates at +-65504, the e4m3 image of lo at +-448.)  The value is made
         // opaque first, as in store_cvt: hi must be the rounding of the SAME fp32 number lo is taken against -- left alone, hipcc folds
         // the producer's last multiply into the conversion in some contexts and not into the subtraction (op test: lo planes off by
-        // an f16 ulp in the attention epilogue).
+        // an f16 ulp in the attention epilogue).  Pinned by tests/test_gpu_range.py::test_attention_normalisation_rounds_once_before_the_split:
+        // without this line the attention kernels get v_fma_mixlo_f16 here and store another lo8 at every f16 tie.
         float c = v[j];
         asm("" : "+v"(c));
         hi[j] = (_Float16)c;
-        lo_scaled[j] = (c - (float)hi[j]) * (float)(1 << BD_F16C8_D);
+        lo[j] = c - (float)hi[j];
     }
+}
+// Two lo8 bytes e4m3((x - hi) 2^D) into the low (HIGH = false) or high half of `old`.  The scale rides in the conversion
+// (v_cvt_scalef32_pk_fp8_f32 divides by its scale operand, 2^-D): as a separate fp32 multiply it overflows to Inf for |x - hi| >= 2^117, and
+// FP16_OVFL clamps finite values only -- fp32's largest value came out as the NaN byte 0x7f, which poisons every product of its row
+// (tests/test_gpu_range.py).  Same bytes as multiply + v_cvt_pk_fp8_f32 for every residual that does not overflow (tools/lo8_scaled_cvt_probe.hip:
+// 1M random values over 30 binades, ties and e4m3 subnormals included), and one VALU instruction per pair fewer.
+template <bool HIGH> __device__ __forceinline__ int f16c8_lo8_pk(float a, float b, int old) {
+    typedef short s16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(__builtin_bit_cast(s16x2, old), a, b, 1.0f / (float)(1 << BD_F16C8_D), HIGH));
 }
 template <> __device__ __forceinline__ void store_operand8<f16c8, 2>(f16c8* base, int64_t plane, int64_t e, const float (&v)[8]) {
     _Float16 h[8];
@@ -315,8 +343,8 @@ template <> __device__ __forceinline__ void store_operand8<f16c8, 2>(f16c8* base
 #pragma unroll
     for (int j = 0; j < 8; ++j) hv[j] = h[j];
     int l0 = 0, l1 = 0;
-    l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], l0, false); l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], l0, true);
-    l1 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4], lo[5], l1, false); l1 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[6], lo[7], l1, true);
+    l0 = f16c8_lo8_pk<false>(lo[0], lo[1], l0); l0 = f16c8_lo8_pk<true>(lo[2], lo[3], l0);
+    l1 = f16c8_lo8_pk<false>(lo[4], lo[5], l1); l1 = f16c8_lo8_pk<true>(lo[6], lo[7], l1);
     unsigned char* lo_plane = (unsigned char*)(base + plane);
 #if defined(BD_STORE_NT) && BD_STORE_NT
     __builtin_nontemporal_store(__builtin_bit_cast(u128, hv), (u128*)(base + e));
@@ -333,7 +361,7 @@ __device__ __forceinline__ void f16c8_store4(f16c8* base, int64_t plane, int64_t
     typedef __attribute__((__vector_size__(4 * sizeof(_Float16)))) _Float16 f16x4;
     f16x4 hv = {h[0], h[1], h[2], h[3]};
     int l0 = 0;
-    l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], l0, false); l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], l0, true);
+    l0 = f16c8_lo8_pk<false>(lo[0], lo[1], l0); l0 = f16c8_lo8_pk<true>(lo[2], lo[3], l0);
     *(f16x4*)(base + e) = hv;
     *(int*)((unsigned char*)(base + plane) + f16c8_lo_index(e & ~(int64_t)7) + (e & 4)) = l0;
 }

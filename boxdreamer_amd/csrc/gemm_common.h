@@ -540,8 +540,8 @@ __device__ __forceinline__ void pc_epilogue(const bd_gemm_args& p, f32x16 (&acc)
                         hh[cb][0] = __builtin_bit_cast(unsigned, (h2_){h[0], h[1]});
                         hh[cb][1] = __builtin_bit_cast(unsigned, (h2_){h[2], h[3]});
                         int l0 = 0;
-                        l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], l0, false);
-                        l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], l0, true);
+                        l0 = f16c8_lo8_pk<false>(lo[0], lo[1], l0);
+                        l0 = f16c8_lo8_pk<true>(lo[2], lo[3], l0);
                         ll[cb] = (unsigned)l0;
                     }
                     const bool odd = c4 & 1;
@@ -657,8 +657,8 @@ __device__ __forceinline__ void pc_epilogue(const bd_gemm_args& p, f32x16 (&acc)
 #pragma unroll
                     for (int q = 0; q < 8; ++q) hv[q] = hh[q];
                     int l0 = 0, l1 = 0;
-                    l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0], lo[1], l0, false); l0 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[2], lo[3], l0, true);
-                    l1 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[4], lo[5], l1, false); l1 = __builtin_amdgcn_cvt_pk_fp8_f32(lo[6], lo[7], l1, true);
+                    l0 = f16c8_lo8_pk<false>(lo[0], lo[1], l0); l0 = f16c8_lo8_pk<true>(lo[2], lo[3], l0);
+                    l1 = f16c8_lo8_pk<false>(lo[4], lo[5], l1); l1 = f16c8_lo8_pk<true>(lo[6], lo[7], l1);
                     *(u128*)(b0p + (size_t)(2u * e)) = __builtin_bit_cast(u128, hv);
                     *(uint2*)(b1p + (size_t)lo_index32(e)) = make_uint2((unsigned)l0, (unsigned)l1);
                 }

@@ -36,11 +36,13 @@ def f16c8_encode(x: torch.Tensor, qexp: int = 0, weight: bool = False) -> torch.
       activations: the first rows*K bytes are the lo8 plane e4m3((x - hi) 2^D), k-permuted per 32-block (rest unused);
       weights:     per 32-block 64 bytes = for each lane half h: [q8 x 16 | lo8 x 16] of its sixteen k (same k order),
                    q8 = e4m3(hi 2^E), lo8 = e4m3((w - hi) 2^(E + D)).
+    The residual is taken against the fp32 value itself (csrc/bd_common.h: f16c8_split), so beyond +-65504 hi is the saturated f16 and
+    lo8 the saturated image of what hi left over.
     Torch ops: weight packing at load time and test helpers (not on the hot path)."""
-    x = x.float().clamp(-65504.0, 65504.0)
+    x = x.float()
     rows, K = x.shape
     assert K % 32 == 0, "F16C8 operands are laid out in 32-element blocks"
-    hi = x.half()
+    hi = x.clamp(-65504.0, 65504.0).half()
     lo = (x - hi.float()) * 2.0 ** (qexp + _lib.F16C8_D)
     perm = _f16c8_perm(K, x.device)
     l8 = lo.clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)[:, perm]
@@ -79,12 +81,13 @@ def to_operand(x: torch.Tensor, prec) -> torch.Tensor:
         return f16c8_encode(x, 0, False)
     if prec_id(prec) == _lib.PREC_FP8:
         return x.float().clamp(-448.0, 448.0).to(dt).contiguous()
-    if dt == torch.float16:
-        x = x.float().clamp(-65504.0, 65504.0)             # the kernels' f16 conversions saturate (bd_common.h: RANGE)
-    hi = x.to(dt)
+    # the kernels' f16 conversions saturate (bd_common.h: RANGE), each on its own: lo is what the saturated hi left of the fp32 value
+    sat = (lambda v: v.clamp(-65504.0, 65504.0)) if dt == torch.float16 else (lambda v: v)
+    x = x.float()
+    hi = sat(x).to(dt)
     if planes(prec) == 1:
         return hi.contiguous()
-    return torch.stack([hi, (x.float() - hi.float()).to(dt)]).contiguous()
+    return torch.stack([hi, sat(x - hi.float()).to(dt)]).contiguous()
 
 
 def from_operand(t: torch.Tensor, prec) -> torch.Tensor:
