@@ -132,7 +132,9 @@ EXPORTS = [
     "bd_decoder_forward_entry_ragged", "bd_solve_pnp_wave",
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
     "bd_round_sources", "bd_pose_select_rows",
+    "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host",
 ]
+STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
 
 _lib = None
 
@@ -225,6 +227,10 @@ def load() -> C.CDLL:
     lib.bd_decoder_entry_workspace_bytes_ragged.argtypes = [C.POINTER(BetrWeights), i, i, i]
     lib.bd_decoder_entry_workspace_bytes_ragged.restype = sz
     lib.bd_decoder_forward_entry_ragged.argtypes = [C.POINTER(BetrWeights), vp, i, vp, vp, i64, vp, vp, i, i, i, i, vp, vp, vp, sz, i, vp]
+    lib.bd_stream_windows.argtypes = [vp, vp, C.c_double, i, vp, vp, i, vp]
+    lib.bd_stream_windows_host.argtypes = [vp, vp, C.c_double, i, vp, vp, i]
+    lib.bd_stream_results.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, vp]
+    lib.bd_stream_results_host.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:

@@ -1,0 +1,186 @@
+// The two ends of a streaming pose step (boxdreamer_amd/stream.py: PoseStream), as one launch each, so that the step's captured graph
+// holds two nodes where the façade enqueues a few dozen tiny torch kernels per frame:
+//   * bd_stream_windows: detector boxes -> the integer crop windows and the intrinsics of the resized crops.  The torch form of
+//     preprocess.square_bbox followed by preprocess.crop_intrinsics (the reference's square_bbox / _crop_image / adjust_intrinsic_matrix,
+//     src/datasets/utils/preprocess.py:22-45, :253-259, :277-300), bit for bit: fp64 from the fp32 inputs, in those functions' order.
+//   * bd_stream_results: what the demo loop reads per frame (src/demo/demo.py:1500-1564) in one row of BD_STREAM_ROW_FLOATS floats
+//     per sample: the pose through nan_to_num, its reprojection RMS, a validity flag, the decoded corners in crop and in full-frame
+//     pixels, and the 3-D box projected into the full frame with the solved pose.
+// One sample per lane, one wavefront per 64 samples, plain vector loads and stores; both are bound by launch latency.  The
+// arithmetic is written once (__host__ __device__) and runs on the host as bd_stream_*_host, the twin the tests compare the
+// kernels against.  Floating-point contraction is OFF in it: hipcc -O3 would turn a * b - c * d into an FMA, which rounds once
+// where torch's separate fp64 kernels round twice.
+#include "bd_common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int SW_LANES = 64;
+constexpr int SW_MAX_N = 65535;
+
+__host__ __device__ inline bool sw_finite(double v) { return v - v == 0.0; }
+
+// one sample: box [4] x0 y0 x1 y1, K [9] -> win [4], Kc [9]
+__host__ __device__ inline void stream_window(const float* box, const float* K, double padding, int out_size, int32_t* win, float* Kc) {
+#pragma clang fp contract(off)
+    const double b0 = box[0], b1 = box[1], b2 = box[2], b3 = box[3];
+    // square_bbox: centre +- the larger half-extent x (1 + padding)
+    const double cx = (b0 + b2) / 2.0, cy = (b1 + b3) / 2.0;
+    const double ex = (b2 - b0) / 2.0, ey = (b3 - b1) / 2.0;
+    const double size = (ex > ey ? ex : ey) * (1.0 + padding);
+    const double lx = cx - size, ly = cy - size, hx = cx + size, hy = cy + size;
+    // integer_box: left = int(x0), width = int(x1 - x0), every int() towards zero
+    const double ltx = trunc(lx), lty = trunc(ly);
+    const double whx = trunc(hx - lx), why = trunc(hy - ly);
+    const double w0 = ltx, w1 = lty, w2 = ltx + whx, w3 = lty + why;
+    const double lim = 2147483648.0;
+    const bool ok = sw_finite(b0) && sw_finite(b1) && sw_finite(b2) && sw_finite(b3) && sw_finite(w0) && sw_finite(w1) && sw_finite(w2) &&
+                    sw_finite(w3) && w0 >= -lim && w0 < lim && w1 >= -lim && w1 < lim && w2 >= -lim && w2 < lim && w3 >= -lim && w3 < lim;
+    const int32_t x0 = ok ? (int32_t)w0 : 0, y0 = ok ? (int32_t)w1 : 0, x1 = ok ? (int32_t)w2 : 0, y1 = ok ? (int32_t)w3 : 0;
+    win[0] = x0; win[1] = y0; win[2] = x1; win[3] = y1;
+    // crop_intrinsics: scale = out_size / side, offset = (x0, y0).  torch evaluates `float / tensor` as reciprocal(tensor) * float
+    // (Tensor.__rtruediv__): two roundings, and those are the bits to reproduce
+    const double dx0 = (double)x0, dy0 = (double)y0;
+    const double rx = 1.0 / ((double)x1 - dx0), ry = 1.0 / ((double)y1 - dy0);
+    const double sx = rx * (double)out_size, sy = ry * (double)out_size;
+    const double k00 = (double)K[0] * sx, k11 = (double)K[4] * sy;
+    const double px = (double)K[2] * sx, ox = dx0 * sx, py = (double)K[5] * sy, oy = dy0 * sy;
+    const double k02 = px - ox, k12 = py - oy;
+    Kc[0] = (float)k00; Kc[1] = K[1]; Kc[2] = (float)k02;
+    Kc[3] = K[3]; Kc[4] = (float)k11; Kc[5] = (float)k12;
+    Kc[6] = K[6]; Kc[7] = K[7]; Kc[8] = K[8];
+}
+
+// one sample: pose [16], rms, kp [16], win [4], K [9] full frame, box [24] -> row [BD_STREAM_ROW_FLOATS]
+__host__ __device__ inline void stream_result(const float* pose, float rms, const float* kp, const int32_t* win, const float* K,
+                                              const float* box, int out_size, float* row) {
+#pragma clang fp contract(off)
+    float p[16];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        p[i] = pose[i];
+        const bool f = p[i] - p[i] == 0.0f;
+        finite = finite && f;
+        row[i] = f ? p[i] : 0.0f;                           // nan_to_num(nan = 0, posinf = 0, neginf = 0)
+    }
+    const bool ok = finite && p[15] == 1.0f;                // (a failed solve leaves an all-zero matrix)
+    row[16] = rms;
+    row[17] = ok ? 1.0f : 0.0f;
+    // corners: crop pixels, then full-frame pixels (the inverse of crop_intrinsics: no half-pixel term)
+    const double x0 = (double)win[0], y0 = (double)win[1];
+    const double sx = (double)win[2] - x0, sy = (double)win[3] - y0;
+    const double S = (double)out_size;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float kx = kp[2 * j], ky = kp[2 * j + 1];
+        row[18 + 2 * j] = kx;
+        row[19 + 2 * j] = ky;
+        const double mx = (double)kx * sx, my = (double)ky * sy;
+        const double qx = mx / S, qy = my / S;
+        row[34 + 2 * j] = (float)(x0 + qx);
+        row[35 + 2 * j] = (float)(y0 + qy);
+    }
+    // the 3-D box through the solved pose into the full frame
+    const double k00 = K[0], k01 = K[1], k02 = K[2], k11 = K[4], k12 = K[5];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float u = 0.0f, v = 0.0f;
+        if (ok) {
+            const double x = box[3 * j], y = box[3 * j + 1], z = box[3 * j + 2];
+            double c[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const double a = (double)p[4 * r] * x, b = (double)p[4 * r + 1] * y, d = (double)p[4 * r + 2] * z;
+                const double ab = a + b;
+                const double abd = ab + d;
+                c[r] = abd + (double)p[4 * r + 3];
+            }
+            const double xc = c[0], yc = c[1], zc = c[2];
+            if (zc <= 0.0) {
+                u = v = __builtin_nanf("");
+            } else {
+                const double a = k00 * xc, b = k01 * yc, d = k02 * zc;
+                const double ab = a + b;
+                const double nu = ab + d;
+                const double e = k11 * yc, g = k12 * zc;
+                const double nv = e + g;
+                u = (float)(nu / zc);
+                v = (float)(nv / zc);
+            }
+        }
+        row[50 + 2 * j] = u;
+        row[51 + 2 * j] = v;
+    }
+}
+
+__global__ __launch_bounds__(SW_LANES) void stream_windows_kernel(const float* __restrict__ det_boxes, const float* __restrict__ K,
+                                                                  double padding, int out_size, int32_t* __restrict__ windows,
+                                                                  float* __restrict__ K_crop, int n) {
+    const int i = blockIdx.x * SW_LANES + threadIdx.x;
+    if (i >= n) return;
+    stream_window(det_boxes + (int64_t)i * 4, K + (int64_t)i * 9, padding, out_size, windows + (int64_t)i * 4, K_crop + (int64_t)i * 9);
+}
+
+__global__ __launch_bounds__(SW_LANES) void stream_results_kernel(const float* __restrict__ poses, const float* __restrict__ rms_px,
+                                                                  const float* __restrict__ kp_px, const int32_t* __restrict__ windows,
+                                                                  const float* __restrict__ K, const float* __restrict__ bbox_3d,
+                                                                  int out_size, float* __restrict__ rows, int n) {
+    const int i = blockIdx.x * SW_LANES + threadIdx.x;
+    if (i >= n) return;
+    stream_result(poses + (int64_t)i * 16, rms_px[i], kp_px + (int64_t)i * 16, windows + (int64_t)i * 4, K + (int64_t)i * 9,
+                  bbox_3d + (int64_t)i * 24, out_size, rows + (int64_t)i * BD_STREAM_ROW_FLOATS);
+}
+
+int windows_args(const void* a, const void* b, const void* c, const void* d, int out_size, int n) {
+    if (!a || !b || !c || !d) return BD_ERR_NULL;
+    if (n < 0 || n > SW_MAX_N || out_size < 1) return BD_ERR_SHAPE;
+    return BD_OK;
+}
+
+int results_args(const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, const void* g, int out_size, int n) {
+    if (!a || !b || !c || !d || !e || !f || !g) return BD_ERR_NULL;
+    if (n < 0 || n > SW_MAX_N || out_size < 1) return BD_ERR_SHAPE;
+    return BD_OK;
+}
+
+}  // namespace
+
+extern "C" int bd_stream_windows(const float* det_boxes, const float* K, double padding, int out_size, int32_t* windows, float* K_crop,
+                                 int n, void* stream) {
+    const int rc = windows_args(det_boxes, K, windows, K_crop, out_size, n);
+    if (rc != BD_OK || n == 0) return rc;
+    hipLaunchKernelGGL(stream_windows_kernel, dim3((n + SW_LANES - 1) / SW_LANES), dim3(SW_LANES), 0, (hipStream_t)stream, det_boxes, K,
+                       padding, out_size, windows, K_crop, n);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_stream_windows_host(const float* det_boxes, const float* K, double padding, int out_size, int32_t* windows,
+                                      float* K_crop, int n) {
+    const int rc = windows_args(det_boxes, K, windows, K_crop, out_size, n);
+    if (rc != BD_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        stream_window(det_boxes + (int64_t)i * 4, K + (int64_t)i * 9, padding, out_size, windows + (int64_t)i * 4, K_crop + (int64_t)i * 9);
+    return BD_OK;
+}
+
+extern "C" int bd_stream_results(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
+                                 const float* bbox_3d, int out_size, float* rows, int n, void* stream) {
+    const int rc = results_args(poses, rms_px, kp_px, windows, K, bbox_3d, rows, out_size, n);
+    if (rc != BD_OK || n == 0) return rc;
+    hipLaunchKernelGGL(stream_results_kernel, dim3((n + SW_LANES - 1) / SW_LANES), dim3(SW_LANES), 0, (hipStream_t)stream, poses, rms_px,
+                       kp_px, windows, K, bbox_3d, out_size, rows, n);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_stream_results_host(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
+                                      const float* bbox_3d, int out_size, float* rows, int n) {
+    const int rc = results_args(poses, rms_px, kp_px, windows, K, bbox_3d, rows, out_size, n);
+    if (rc != BD_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        stream_result(poses + (int64_t)i * 16, rms_px[i], kp_px + (int64_t)i * 16, windows + (int64_t)i * 4, K + (int64_t)i * 9,
+                      bbox_3d + (int64_t)i * 24, out_size, rows + (int64_t)i * BD_STREAM_ROW_FLOATS);
+    return BD_OK;
+}

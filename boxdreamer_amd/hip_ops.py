@@ -387,3 +387,79 @@ def decode_topk(heat, k=20, want_idx=True):
     idx = torch.empty((n, k), dtype=torch.int32, device=heat.device) if want_idx else None
     check(lib.bd_decode_topk(ptr(heat), n, H, W, k, ptr(kp), ptr(kn), ptr(idx), stream()), "bd_decode_topk")
     return kp.reshape(*lead, 2), kn.reshape(*lead, 2), (idx.reshape(*lead, k) if want_idx else None)
+
+
+def _stream_dev(t, shape, dtype, name):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                         f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    return t
+
+
+def stream_windows(det_boxes, K, padding=0.1, out_size=224, windows=None, K_crop=None):
+    """bd_stream_windows: det_boxes fp32 (n, 4) x0 y0 x1 y1, K fp32 (n, 3, 3) of the full frame -> (windows int32 (n, 4), K_crop fp32
+    (n, 3, 3)): preprocess.square_bbox(det_boxes, padding) and preprocess.crop_intrinsics(K, windows, out_size) in ONE launch, bit for
+    bit.  `windows` / `K_crop`: where to write them (allocated when None)."""
+    lib = _lib.load()
+    n = int(det_boxes.shape[0]) if isinstance(det_boxes, torch.Tensor) and det_boxes.dim() == 2 else -1
+    _stream_dev(det_boxes, (n, 4), torch.float32, "det_boxes")
+    _stream_dev(K, (n, 3, 3), torch.float32, "K")
+    windows = torch.empty((n, 4), dtype=torch.int32, device=det_boxes.device) if windows is None else _stream_dev(windows, (n, 4), torch.int32, "windows")
+    K_crop = torch.empty((n, 3, 3), dtype=torch.float32, device=det_boxes.device) if K_crop is None else _stream_dev(K_crop, (n, 3, 3), torch.float32, "K_crop")
+    _lib.same_device(det_boxes, K, windows, K_crop)
+    check(lib.bd_stream_windows(ptr(det_boxes), ptr(K), float(padding), int(out_size), ptr(windows), ptr(K_crop), n, stream()), "bd_stream_windows")
+    return windows, K_crop
+
+
+def stream_results(poses, rms_px, kp_px, windows, K, bbox_3d, out_size=224, rows=None):
+    """bd_stream_results: poses fp32 (n, 4, 4), rms_px fp32 (n,), kp_px fp32 (n, 8, 2), windows int32 (n, 4), K fp32 (n, 3, 3) of the
+    full frame, bbox_3d fp32 (n, 8, 3) -> rows fp32 (n, 66) in ONE launch (the layout: include/boxdreamer_hip.h), written into `rows`
+    when given."""
+    lib = _lib.load()
+    n = int(poses.shape[0]) if isinstance(poses, torch.Tensor) and poses.dim() == 3 else -1
+    _stream_dev(poses, (n, 4, 4), torch.float32, "poses")
+    _stream_dev(rms_px, (n,), torch.float32, "rms_px")
+    _stream_dev(kp_px, (n, 8, 2), torch.float32, "kp_px")
+    _stream_dev(windows, (n, 4), torch.int32, "windows")
+    _stream_dev(K, (n, 3, 3), torch.float32, "K")
+    _stream_dev(bbox_3d, (n, 8, 3), torch.float32, "bbox_3d")
+    shape = (n, _lib.STREAM_ROW_FLOATS)
+    rows = torch.empty(shape, dtype=torch.float32, device=poses.device) if rows is None else _stream_dev(rows, shape, torch.float32, "rows")
+    _lib.same_device(poses, rms_px, kp_px, windows, K, bbox_3d, rows)
+    check(lib.bd_stream_results(ptr(poses), ptr(rms_px), ptr(kp_px), ptr(windows), ptr(K), ptr(bbox_3d), int(out_size), ptr(rows), n, stream()),
+          "bd_stream_results")
+    return rows
+
+
+def _host32(a, shape, dtype):
+    import numpy as np
+    a = np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+    if a.shape != tuple(shape):
+        raise ValueError(f"expected a host array of shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+def stream_windows_host(det_boxes, K, padding=0.1, out_size=224):
+    """bd_stream_windows_host: the same arithmetic on host arrays (numpy or CPU tensors) -> (windows int32 (n, 4), K_crop fp32 (n, 3, 3)),
+    numpy.  Needs no GPU."""
+    import numpy as np
+    lib = _lib.load()
+    n = len(det_boxes)
+    b, k = _host32(det_boxes, (n, 4), np.float32), _host32(K, (n, 3, 3), np.float32)
+    windows, K_crop = np.empty((n, 4), np.int32), np.empty((n, 3, 3), np.float32)
+    rc = lib.bd_stream_windows_host(b.ctypes.data, k.ctypes.data, float(padding), int(out_size), windows.ctypes.data, K_crop.ctypes.data, n)
+    check(rc, "bd_stream_windows_host")
+    return windows, K_crop
+
+
+def stream_results_host(poses, rms_px, kp_px, windows, K, bbox_3d, out_size=224):
+    """bd_stream_results_host: the same arithmetic on host arrays (numpy or CPU tensors) -> rows fp32 (n, 66), numpy.  Needs no GPU."""
+    import numpy as np
+    lib = _lib.load()
+    n = len(poses)
+    args = (_host32(poses, (n, 4, 4), np.float32), _host32(rms_px, (n,), np.float32), _host32(kp_px, (n, 8, 2), np.float32),
+            _host32(windows, (n, 4), np.int32), _host32(K, (n, 3, 3), np.float32), _host32(bbox_3d, (n, 8, 3), np.float32))
+    rows = np.empty((n, _lib.STREAM_ROW_FLOATS), np.float32)
+    rc = lib.bd_stream_results_host(*(a.ctypes.data for a in args), int(out_size), rows.ctypes.data, n)
+    check(rc, "bd_stream_results_host")
+    return rows

@@ -529,6 +529,46 @@ int bd_crop_resize_frames(const uint8_t* frames, int n_frames, int H, int W, int
                           const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int out_size,
                           void* out, int out_dtype, void* stream);
 
+/* The two ends of a streaming pose step (boxdreamer_amd/stream.py), one launch each, so that a captured step holds two graph nodes
+ * where the facade enqueues a few dozen small torch kernels per frame.  Each is ceil(n / 64) wavefronts, one sample per lane: no
+ * workspace, no atomics, no synchronisation.  The *_host forms run the SAME arithmetic (written once, __host__ __device__) on host
+ * pointers, in the calling thread: the twin the device forms are tested against, bit for bit.  Floating-point contraction is off
+ * in it.  Before any launch, for all four: a NULL pointer BD_ERR_NULL; n < 0, n > 65535 or out_size < 1 BD_ERR_SHAPE; n == 0
+ * returns BD_OK without a launch.
+ *
+ * Windows: replaces the torch forms of preprocess.square_bbox(box, padding) + preprocess.crop_intrinsics(K, window, out_size) (the
+ * reference's square_bbox / _crop_image / adjust_intrinsic_matrix, src/datasets/utils/preprocess.py:22-45, :253-259, :277-300;
+ * about 20 fp64 torch kernels), bit for bit.  det_boxes fp32 [n, 4] = x0 y0 x1 y1 detector boxes, K fp32 [n, 3, 3] intrinsics of
+ * the full frame.  Everything is fp64 from the fp32 inputs, in those functions' operation order: center = (b0 + b2) / 2, extent =
+ * (b2 - b0) / 2, size = max(ex, ey) * (1 + padding), lt = trunc(center - size), wh = trunc((center + size) - (center - size)),
+ * windows int32 [n, 4] = lt, lt + wh; then sx = out_size / (x1 - x0) as torch evaluates `float / tensor`, (1 / (x1 - x0)) *
+ * out_size, k00 *= sx, k02 = k02 * sx - x0 * sx (likewise y), the other entries copied: K_crop fp32 [n, 3, 3], rounded once.  A window whose sides differ after truncation is written as computed (the
+ * crop kernel writes zeros for it); a non-finite box or a coordinate outside int32 gives the window 0 0 0 0. */
+int bd_stream_windows(const float* det_boxes, const float* K, double padding, int out_size, int32_t* windows, float* K_crop, int n,
+                      void* stream);
+int bd_stream_windows_host(const float* det_boxes, const float* K, double padding, int out_size, int32_t* windows, float* K_crop,
+                           int n);
+
+/* Results: replaces the indexing, cat, nan_to_num and clone the facade enqueues after the pose solve (boxdreamer_amd/model.py:
+ * _process_evaluation) and the demo loop's per-frame projections (src/demo/demo.py:1500-1564).  poses fp32 [n, 4, 4] and rms_px
+ * fp32 [n] as the wave solver leaves them (an all-zero matrix on failure), kp_px fp32 [n, 8, 2] decoded corners in crop pixels,
+ * windows / out_size the crop they were decoded in, K fp32 [n, 3, 3] of the FULL frame, bbox_3d fp32 [n, 8, 3].
+ * rows fp32 [n, BD_STREAM_ROW_FLOATS]:
+ *   [0, 16)  the pose, row-major, NaN and +-inf replaced by 0 (torch.nan_to_num(nan=0, posinf=0, neginf=0));
+ *   [16]     rms_px;
+ *   [17]     ok: 1 when pose[3][3] == 1 and all 16 entries are finite, else 0;
+ *   [18, 34) kp_px, copied;
+ *   [34, 50) the corners in full-frame pixels, x = x0 + kp_x * (x1 - x0) / out_size (likewise y; the inverse of the crop's
+ *            intrinsics, no half-pixel term), fp64, rounded once;
+ *   [50, 66) the 3-D box projected into the full frame with the pose: Xc = ((r0 x + r1 y) + r2 z) + t, u = ((k00 xc + k01 yc) +
+ *            k02 zc) / zc, v = (k11 yc + k12 zc) / zc in fp64, in that order, rounded once; a point with zc <= 0 gives NaN for
+ *            both; all 16 values are 0 when ok == 0. */
+#define BD_STREAM_ROW_FLOATS 66
+int bd_stream_results(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
+                      const float* bbox_3d, int out_size, float* rows, int n, void* stream);
+int bd_stream_results_host(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
+                           const float* bbox_3d, int out_size, float* rows, int n);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-path entry points
  * ---------------------------------------------------------------------------------------- */
