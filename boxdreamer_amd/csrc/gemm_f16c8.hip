@@ -14,7 +14,7 @@ namespace {
 // BD_PREC_F16C8 GEMM (bd_common.h: f16 hi pass + one e4m3 correction pass; 3 bytes per element through LDS-DMA).
 // Same producer / consumer persistent structure and 256 x 192 tile as gemm_kernel_pc, with
 //   * a stage of four sub-planes per 32-deep slab: A hi (256 x 64 B), W hi (192 x 64 B), A lo8 (256 x 32 B), W lo8 (192 x 32 B)
-//     = 42 KiB, so THREE stages fit next to nothing else (the LDS-staged epilogue's 48 KiB scratch overlays stage 2, which is
+//     = 48 KiB, so THREE stages fit next to nothing else (the LDS-staged epilogue's 48 KiB scratch overlays stage 2, which is
 //     where every tile's last slab lives when K / 32 is a multiple of 3 -- K = 768 and 3072 -- and is free while the next
 //     tile's first two slabs land in stages 0 and 1).  With three stages the producers run TWO slabs ahead and wait with a
 //     counted vmcnt: the ~1100-cycle issue-to-landing latency of a slab, which bounds the 2-stage kernels at ~2800 cycles per
@@ -38,14 +38,27 @@ namespace {
 //     per-(tile, ks, wave) flag and exit; the LAST one (highest blockIdx of the tile: dispatched after its secondaries, so its wait cannot
 //     starve them) starts from the residual as usual, waits for each flag in turn, adds the partials in the fixed order ks = 0 .. S - 2
 //     and runs the epilogue.  Deterministic (fixed association), NOT bit-identical to the unsplit forms: include/boxdreamer_hip.h, sk_ws.
+//   * the consumers' K loop unrolled over the ring period, as attention.hip's attn_kernel_pp is: the stage is a compile-time constant of
+//     each slab body, the ring is laid out plane-major so that one per-lane register per fragment kind reaches every stage with the DS
+//     instruction's 16-bit immediate, the e4m3 conversions overwrite the previous slab's image and the weight scale stays in a VGPR.  Per slab
+//     and wave: 18 MFMA, 18 ds_read_b128, 16 conversions, the waits, the barrier and NO other vector instruction (26 before).  Same MFMA
+//     order, operands and interleave: every row's bits are unchanged.  profiles/f16c8_slab_loop.md.
 template <int NSTAGE, int EP, int OUTK, bool GELU, int WM = 4, int WN = 2, int NPW = 4, bool LNF = false, bool SK = false>
 __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1) void gemm_kernel_pc_f16c8(const bd_gemm_args p) {
     constexpr int MI = 2, NI = 3, NCW = WM * WN;
     constexpr int TBM = WM * MI * 32, TBN = WN * NI * 32, BK = 32;
     constexpr int A0 = TBM * 64, W0 = TBN * 64, A1 = TBM * 32, W1 = TBN * 64;     // W's e4m3 plane carries q8 AND lo8 (weights: packed once)
-    constexpr int OFF_W0 = A0, OFF_A1 = A0 + W0, OFF_W1 = A0 + W0 + A1, STAGE = A0 + W0 + A1 + W1;
-    constexpr int SR = 16, SCRATCH = NCW * SR * NI * 32 * 4, S2 = SCRATCH > STAGE ? SCRATCH : STAGE;
-    static_assert(SCRATCH <= STAGE, "the epilogue scratch overlays stage 2");
+    constexpr int STAGE = A0 + W0 + A1 + W1;
+    // The ring is laid out PLANE-major: the NSTAGE copies of a plane lie side by side, so that a consumer's fragment address is one
+    // loop-invariant per-lane register (plane start + row + swizzled chunk) plus a 16-bit immediate (stage and fragment), whatever the
+    // stage -- the K loop is unrolled over the ring period and carries no address arithmetic (profiles/f16c8_slab_loop.md).  A0 and W0
+    // ascend with the stage, A1 and W1 descend: the last stage's A planes (A0 | A1) and W planes (W0 | W1) are then two contiguous
+    // regions, which the epilogue scratch of the three-stage forms overlays.
+    constexpr int PL_A0 = 0, PL_A1 = NSTAGE * A0, PL_W0 = NSTAGE * (A0 + A1), PL_W1 = PL_W0 + NSTAGE * W0;
+    static_assert((NSTAGE - 1) * A0 + (MI - 1) * 2048 + 16 <= 65536 && (NSTAGE - 1) * W0 + (NI - 1) * 2048 + 16 <= 65536, "stage + fragment fit a DS immediate");
+    constexpr int SR = 16, WSCR = SR * NI * 32 * 4, SCRATCH = NCW * WSCR, S2 = SCRATCH > STAGE ? SCRATCH : STAGE;
+    constexpr int NSA = (A0 + A1) / WSCR < NCW ? (A0 + A1) / WSCR : NCW;     // consumer waves whose scratch lies in stage 2's A planes
+    static_assert(SCRATCH <= STAGE && (NCW - NSA) * WSCR <= W0 + W1, "the epilogue scratch overlays stage 2");
     // producers: every plane of a stage is fetched in 1-KiB pieces (one wave instruction: 16 rows of 64 B, or 32 rows of 32 B), dealt round-robin
     constexpr int GA0 = TBM / 16, GW0 = TBN / 16, GA1 = TBM / 32, GW1 = TBN / 16;
     constexpr int IA0 = (GA0 + NPW - 1) / NPW, IW0 = (GW0 + NPW - 1) / NPW, IA1 = (GA1 + NPW - 1) / NPW, IW1 = (GW1 + NPW - 1) / NPW;
@@ -57,7 +70,7 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
     constexpr int AUX_COLP = 2 * STAGE + S2, AUX_RMS = AUX_COLP + 4096, AUX_ROWS = AUX_RMS + 2048, AUX_BYTES = EP == 0 ? 0 : (LNF ? 10240 : 6144);
     static_assert(!LNF || (EP != 0 && NPW * 64 >= TBM && NSTAGE == 3), "LayerNorm fold: one producer lane per tile row");
     static_assert(!SK || ((EP == 3 || EP == 4 || EP == 5) && !LNF && NSTAGE == 3), "split-K: the fp32-residual epilogues, one tile per workgroup");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE + S2 + AUX_BYTES];   // stages at 0, STAGE, 2*STAGE; scratch at 2*STAGE
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * STAGE + S2 + AUX_BYTES];   // ring (plane-major) in [0, NSTAGE * STAGE); scratch: over stage 2 (NSTAGE 3), at 2 * STAGE (NSTAGE 2)
 
     bd_saturating_conversions();      // q8 images (K loop) and F16C8 / f16 results (epilogue) saturate instead of turning NaN / inf
     const int tid = threadIdx.x, lane = tid & 63;
@@ -108,19 +121,21 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
             const int rows_a = (M - m0) < TBM ? (M - m0) : TBM, rows_w = (N - n0) < TBN ? (N - n0) : TBN;
             const unsigned la0 = (unsigned)(rows_a - 1) * lda0 + 48, lw0 = (unsigned)(rows_w - 1) * ldw0 + 48;
             const unsigned la1 = (unsigned)(rows_a - 1) * lda1 + 16, lw1 = (unsigned)(rows_w - 1) * ldw1 + 48;
-            const unsigned st = lds_off + stage * STAGE + pw * 1024;
+            const unsigned st = lds_off + pw * 1024;
+            const unsigned sa0 = st + PL_A0 + stage * A0, sw0 = st + PL_W0 + stage * W0;
+            const unsigned sa1 = st + PL_A1 + (NSTAGE - 1 - stage) * A1, sw1 = st + PL_W1 + (NSTAGE - 1 - stage) * W1;
             const unsigned char* ba0 = pA0 + (int64_t)m0 * lda0 + (int64_t)(k_lo + kt) * 64;
             const unsigned char* bw0 = pW0 + (int64_t)n0 * ldw0 + (int64_t)(k_lo + kt) * 64;
             const unsigned char* ba1 = pA1 + (int64_t)m0 * lda1 + (int64_t)(k_lo + kt) * 32;
             const unsigned char* bw1 = pW1 + (int64_t)n0 * ldw1 + (int64_t)(k_lo + kt) * 64;
 #pragma unroll
-            for (int i = 0; i < IA0; ++i) glds16_s(oA0[i] < la0 ? oA0[i] : la0, ba0, st + i * (NPW * 1024));
+            for (int i = 0; i < IA0; ++i) glds16_s(oA0[i] < la0 ? oA0[i] : la0, ba0, sa0 + i * (NPW * 1024));
 #pragma unroll
-            for (int i = 0; i < IW0; ++i) glds16_s(oW0[i] < lw0 ? oW0[i] : lw0, bw0, st + OFF_W0 + i * (NPW * 1024));
+            for (int i = 0; i < IW0; ++i) glds16_s(oW0[i] < lw0 ? oW0[i] : lw0, bw0, sw0 + i * (NPW * 1024));
 #pragma unroll
-            for (int i = 0; i < IA1; ++i) glds16_s(oA1[i] < la1 ? oA1[i] : la1, ba1, st + OFF_A1 + i * (NPW * 1024));
+            for (int i = 0; i < IA1; ++i) glds16_s(oA1[i] < la1 ? oA1[i] : la1, ba1, sa1 + i * (NPW * 1024));
 #pragma unroll
-            for (int i = 0; i < IW1; ++i) glds16_s(oW1[i] < lw1 ? oW1[i] : lw1, bw1, st + OFF_W1 + i * (NPW * 1024));
+            for (int i = 0; i < IW1; ++i) glds16_s(oW1[i] < lw1 ? oW1[i] : lw1, bw1, sw1 + i * (NPW * 1024));
         };
         // issue cursor over this workgroup's slab sequence (all tiles, slab by slab); slab number ig goes to stage ig % NSTAGE
         int ig = 0, ist = 0, it = t_begin + (bid >> 3), ikt = 0, im0 = 0, in0 = 0, itn = 0;
@@ -209,7 +224,22 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
     const int wm = wid / WN, wn = wid % WN;
     const int lrow = lane & 31, lhalf = lane >> 5;
     const int scale_a = 127, scale_w = 127 - (p.w_qexp + BD_F16C8_D);           // E8M0: the cross terms carry 2^(E + D)
-    int g_st = 0;
+    int g_st = 0;                                    // stage of this workgroup's next slab: carried from tile to tile
+    // The seven per-lane fragment addresses of the K loop (byte offsets into lds; the 32-row fragment i / j and the stage are immediates):
+    // A hi / W hi per k-step, A lo8, W's e4m3 plane per 16-byte half.  The swizzle term depends on lrow alone (fragments start at
+    // multiples of 32 rows).  Opaque to the compiler, which otherwise derives one from another inside the loop.
+    unsigned fa0[2], fw0[2], fa1, fw1[2];
+    {
+        const int ra = wm * (MI * 32) + lrow, rw = wn * (NI * 32) + lrow;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            fa0[k] = PL_A0 + ra * 64 + (swz_chunk<4>(ra, k * 2 + lhalf) << 4);
+            fw0[k] = PL_W0 + rw * 64 + (swz_chunk<4>(rw, k * 2 + lhalf) << 4);
+            fw1[k] = PL_W1 + rw * 64 + (swz_chunk<4>(rw, 2 * lhalf + k) << 4);
+        }
+        fa1 = PL_A1 + ra * 32 + (swz_chunk<2>(ra, lhalf) << 4);
+        asm volatile("" : "+v"(fa0[0]), "+v"(fa0[1]), "+v"(fw0[0]), "+v"(fw0[1]), "+v"(fa1), "+v"(fw1[0]), "+v"(fw1[1]));
+    }
 #ifdef BD_GEMM_PROBE
     unsigned probe_ts = 0;
     int g = 0;
@@ -236,25 +266,34 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
         int m0, n0;
         tile_origin(t, m0, n0);
         if constexpr (EP == 0) acc_init<MI, NI>(p, acc, m0 + wm * (MI * 32), n0 + wn * (NI * 32), lane);
-        for (int kt = 0; kt < nk; ++kt) {
+        // The scales in VGPRs (the scaled MFMA takes them from there) and A's e4m3 image of the slab, both set once per tile.  A conversion
+        // writes HALF a register and keeps the other half (its "old" operand): fed with the previous slab's image -- both halves are
+        // overwritten -- it needs no zeroing move (8 per slab and wave before).
+        int sc_a = scale_a, sc_w = scale_w;
+        unsigned qd[MI][4] = {};
+        asm volatile("" : "+v"(sc_a), "+v"(sc_w));
+        // One slab out of stage ST, a compile-time constant: the loop below is unrolled over the ring period.
+        auto slab = [&](auto st_) {
+            constexpr int ST = decltype(st_)::value;
+            constexpr int SA0 = ST * A0, SW0 = ST * W0, SA1 = (NSTAGE - 1 - ST) * A1, SW1 = (NSTAGE - 1 - ST) * W1;
             BD_PROBE_IF(g < 20, g * 3)
             pc_barrier();                                 // B
             BD_PROBE_IF(g < 20, g * 3 + 1)
 #ifdef BD_GEMM_PROBE
             ++g;
 #endif
-            const unsigned char* base = lds + g_st * STAGE;
-            g_st = g_st + 1 == NSTAGE ? 0 : g_st + 1;
             f16x8 ah[2][MI], wh[2][NI];
             u128 al[MI];
             i32x8 w8[NI];
-#define LD16(dst, ptr, row, ks) dst = __builtin_bit_cast(f16x8, *(const u128*)((ptr) + (row) * 64 + (swz_chunk<4>((row), (ks) * 2 + lhalf) << 4)));
-#define LDLO(dst, ptr, row) dst = *(const u128*)((ptr) + (row) * 32 + (swz_chunk<2>((row), lhalf) << 4));
+            // (lane address, immediate): fragment f of A hi / W hi at k-step ks, of A lo8, of W's e4m3 plane
+#define LD16A(dst, f, ks) dst = __builtin_bit_cast(f16x8, *(const u128*)(lds + fa0[ks] + (SA0 + (f) * 2048)));
+#define LD16W(dst, f, ks) dst = __builtin_bit_cast(f16x8, *(const u128*)(lds + fw0[ks] + (SW0 + (f) * 2048)));
+#define LDLO(dst, f) dst = *(const u128*)(lds + fa1 + (SA1 + (f) * 1024));
             // W's e4m3 operand straight from LDS: 32 bytes = [q8 x 16 | lo8 x 16] of this lane half
-#define LDW8(dst, ptr, row)                                                                                    \
+#define LDW8(dst, f)                                                                                           \
             {                                                                                                     \
-                const u128 lo_ = *(const u128*)((ptr) + (row) * 64 + (swz_chunk<4>((row), 2 * lhalf) << 4));        \
-                const u128 hi_ = *(const u128*)((ptr) + (row) * 64 + (swz_chunk<4>((row), 2 * lhalf + 1) << 4));    \
+                const u128 lo_ = *(const u128*)(lds + fw1[0] + (SW1 + (f) * 2048));                               \
+                const u128 hi_ = *(const u128*)(lds + fw1[1] + (SW1 + (f) * 2048));                               \
                 dst = (i32x8){(int)lo_[0], (int)lo_[1], (int)lo_[2], (int)lo_[3], (int)hi_[0], (int)hi_[1], (int)hi_[2], (int)hi_[3]}; \
             }
             // e4m3 image of one f16 A fragment (8 values of a k-step), 2 dwords; scale 1.0.  The wave runs with MODE.FP16_OVFL set
@@ -267,7 +306,7 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
             {                                                                                                     \
                 typedef _Float16 h2_ __attribute__((ext_vector_type(2)));                                         \
                 typedef short s2_ __attribute__((ext_vector_type(2)));                                            \
-                s2_ a_ = {0, 0}, b_ = {0, 0};                                                                     \
+                s2_ a_ = __builtin_bit_cast(s2_, d0), b_ = __builtin_bit_cast(s2_, d1);       /* the previous slab's image */ \
                 a_ = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(a_, Q8P(f, 0, 1), 1.0f, false);                     \
                 a_ = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(a_, Q8P(f, 2, 3), 1.0f, true);                      \
                 b_ = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(b_, Q8P(f, 4, 5), 1.0f, false);                     \
@@ -276,19 +315,18 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
                 d1 = __builtin_bit_cast(unsigned, b_);                                                            \
             }
 #pragma unroll
-            for (int j = 0; j < NI; ++j) LD16(wh[0][j], base + OFF_W0, wn * (NI * 32) + j * 32 + lrow, 0)
+            for (int j = 0; j < NI; ++j) LD16W(wh[0][j], j, 0)
 #pragma unroll
-            for (int i = 0; i < MI; ++i) LD16(ah[0][i], base, wm * (MI * 32) + i * 32 + lrow, 0)
+            for (int i = 0; i < MI; ++i) LD16A(ah[0][i], i, 0)
             __builtin_amdgcn_sched_barrier(0);
             constexpr int NMM = MI * NI;
             static_assert(MI == 2 && NI == 3, "the interleave below is written for 2 x 3 MFMA tiles per wave");
-            unsigned qd[MI][4];
 #pragma unroll
             for (int q = 0; q < NMM; ++q) {                       // f16, k-step 0
                 const int i = q % MI, j = q / MI;
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0][i], wh[0][j], acc[i][j], 0, 0, 0);
-                if (q < MI) LD16(ah[1][q], base, wm * (MI * 32) + q * 32 + lrow, 1)
-                else if (q < MI + NI) LD16(wh[1][q - MI], base + OFF_W0, wn * (NI * 32) + (q - MI) * 32 + lrow, 1)
+                if (q < MI) LD16A(ah[1][q], q, 1)
+                else if (q < MI + NI) LD16W(wh[1][q - MI], q - MI, 1)
                 if (q == 3) Q8H(qd[0][0], qd[0][1], ah[0][0])
                 if (q == 4) Q8H(qd[1][0], qd[1][1], ah[0][1])
                 __builtin_amdgcn_sched_barrier(0);
@@ -297,9 +335,9 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
             for (int q = 0; q < NMM; ++q) {                       // f16, k-step 1
                 const int i = q % MI, j = q / MI;
                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1][i], wh[1][j], acc[i][j], 0, 0, 0);
-                if (q < MI) LDLO(al[q], base + OFF_A1, wm * (MI * 32) + q * 32 + lrow)
-                if (q == 2) LDW8(w8[0], base + OFF_W1, wn * (NI * 32) + lrow)
-                if (q == 4) LDW8(w8[1], base + OFF_W1, wn * (NI * 32) + 32 + lrow)
+                if (q < MI) LDLO(al[q], q)
+                if (q == 2) LDW8(w8[0], 0)
+                if (q == 4) LDW8(w8[1], 1)
                 if (q == 2) Q8H(qd[0][2], qd[0][3], ah[1][0])
                 if (q == 3) Q8H(qd[1][2], qd[1][3], ah[1][1])
                 __builtin_amdgcn_sched_barrier(0);
@@ -308,15 +346,35 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
             for (int q = 0; q < NMM; ++q) {                       // e4m3 correction pass: [lo_A | q_A] . [q_W | lo_W]
                 const int i = q % MI, j = q / MI;
                 const i32x8 a8 = {(int)al[i][0], (int)al[i][1], (int)al[i][2], (int)al[i][3], (int)qd[i][0], (int)qd[i][1], (int)qd[i][2], (int)qd[i][3]};
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, w8[j], acc[i][j], 0, 0, 0, scale_a, 0, scale_w);
-                if (q == 0) LDW8(w8[2], base + OFF_W1, wn * (NI * 32) + 64 + lrow)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, w8[j], acc[i][j], 0, 0, 0, sc_a, 0, sc_w);
+                if (q == 0) LDW8(w8[2], 2)
                 __builtin_amdgcn_sched_barrier(0);
             }
 #undef LDW8
-#undef LD16
+#undef LD16A
+#undef LD16W
 #undef LDLO
 #undef Q8H
 #undef Q8P
+        };
+        // nk slabs starting at stage g_st: up to NSTAGE - 1 slabs bring the ring to stage 0 (a tile after one whose slab count is no
+        // multiple of the period; split-K), whole periods, then the remainder
+        {
+            using std::integral_constant;
+            int left = nk;
+            if constexpr (NSTAGE == 3) {
+                if (g_st == 1 && left > 0) { slab(integral_constant<int, 1>{}); g_st = 2; --left; }
+            }
+            if (g_st == NSTAGE - 1 && left > 0) { slab(integral_constant<int, NSTAGE - 1>{}); g_st = 0; --left; }
+            for (; left >= NSTAGE; left -= NSTAGE) {
+                slab(integral_constant<int, 0>{});
+                slab(integral_constant<int, 1>{});
+                if constexpr (NSTAGE == 3) slab(integral_constant<int, 2>{});
+            }
+            if (left > 0) { slab(integral_constant<int, 0>{}); g_st = 1; --left; }
+            if constexpr (NSTAGE == 3) {
+                if (left > 0) { slab(integral_constant<int, 1>{}); g_st = 2; }
+            }
         }
         BD_PROBE_IF(g == nk, 60)
         pc_barrier();                                     // X
@@ -376,7 +434,9 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, (WM * WN + NPW) <= 4 ? 2 : 1)
                             for (int e = 0; e < 4; ++e) acc[i][j][4 * q + e] += v[(i * NI + j) * 4 + q][e];
             }
         }
-        unsigned char* scratch = lds + 2 * STAGE + wid * (SR * NI * 32 * 4);
+        // three stages: the last stage's planes, A0 | A1 (the first NSA waves) and W0 | W1; two stages: behind the ring
+        unsigned char* scratch = NSTAGE != 3 ? lds + 2 * STAGE + wid * WSCR
+                                 : wid < NSA ? lds + PL_A0 + 2 * A0 + wid * WSCR : lds + PL_W0 + 2 * W0 + (wid - NSA) * WSCR;
         if constexpr (EP == 0) {
             gemm_epilogue_lds<f16c8, 2, MI, NI, SR, true>(p, acc, scratch, m0 + wm * (MI * 32), n0 + wn * (NI * 32), lane);
         } else {
