@@ -79,6 +79,19 @@ class GemmArgs(C.Structure):
                 ("sk_ws", C.c_void_p), ("sk_split", C.c_int)]
 
 
+GEMM_FAMILY_PC, GEMM_FAMILY_GLDS, GEMM_FAMILY_PC_F16C8 = 1, 2, 3      # BD_GEMM_FAMILY_*
+GEMM_KEY_LEN, GEMM_PLAN_MAX_LAUNCHES = 13, 3
+
+
+class GemmLaunch(C.Structure):
+    _fields_ = [("family", C.c_int), ("row", C.c_int), ("key", C.c_int * GEMM_KEY_LEN), ("grid", C.c_int), ("block", C.c_int),
+                ("row0", C.c_int), ("rows", C.c_int), ("split_k", C.c_int)]
+
+
+class GemmPlan(C.Structure):
+    _fields_ = [("n_launches", C.c_int), ("launch", GemmLaunch * GEMM_PLAN_MAX_LAUNCHES)]
+
+
 class Linear(C.Structure):
     _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("wscale", C.c_void_p), ("w_qexp", C.c_int)]
 
@@ -133,6 +146,7 @@ EXPORTS = [
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
     "bd_round_sources", "bd_pose_select_rows",
     "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host",
+    "bd_gemm_plan", "bd_gemm_instance",
 ]
 STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
 
@@ -161,6 +175,8 @@ def load() -> C.CDLL:
     lib.bd_gemm.argtypes = [C.POINTER(GemmArgs), i, vp]
     lib.bd_gemm_fuses_qk_rmsnorm.argtypes = [C.POINTER(GemmArgs), i]
     lib.bd_gemm_takes_ln_fold.argtypes = [C.POINTER(GemmArgs), i]
+    lib.bd_gemm_plan.argtypes = [C.POINTER(GemmArgs), i, i, i, C.POINTER(GemmPlan)]
+    lib.bd_gemm_instance.argtypes = [i, i, C.POINTER(C.c_int)]
     lib.bd_gemm_splitk_flag_bytes.argtypes = [i, i]
     lib.bd_gemm_splitk_flag_bytes.restype = sz
     lib.bd_gemm_splitk_workspace_bytes.argtypes = [i, i]

@@ -626,73 +626,102 @@ __global__ __launch_bounds__((WM * WN + NPW) * 64, 1) void gemm_kernel_pc(const 
 #endif
 }
 
+// The operand classes of this file.  tc is the element type's code in a table key: 0 __bf16, 1 _Float16, 2 fp8e4.
+struct op_class { int tc, ns, bk, esz; };
+template <int TC> struct elem_of;
+template <> struct elem_of<0> { typedef __bf16 type; };
+template <> struct elem_of<1> { typedef _Float16 type; };
+template <> struct elem_of<2> { typedef fp8e4 type; };
+
+// Every instantiated kernel of the two families: one argument list gives a row's key and its kernel, so a key cannot name another instance.
+// gemm_kernel_pc exists on 256 x 192 tiles (8 consumer waves of 64 x 96) with one producer wave per SIMD only: a single wave issues one
+// LDS-DMA piece per ~70 cycles, the CU ~23.
+#define BD_PC_ROW(TC, NS, BK, EP, OUTK, GELU, RING, LNF) \
+    {{TC, NS, BK, 4, 2, 2, 3, 4, EP, OUTK, GELU, RING, LNF}, gemm_kernel_pc<elem_of<TC>::type, NS, BK, 4, 2, 2, 3, 4, EP, OUTK, GELU, RING, LNF>},
+// what every class has: the generic epilogue (no ring), native 16-bit results (plain, GELU, fused q/k RMSNorm), fp32 with either ring form
+#define BD_PC_CLASS(TC, NS, BK)                                                                                                  \
+    BD_PC_ROW(TC, NS, BK, 0, OUT_OPERAND, false, 0, false) BD_PC_ROW(TC, NS, BK, 1, OUT_OPERAND, false, 1, false)                \
+    BD_PC_ROW(TC, NS, BK, 1, OUT_OPERAND, true, 1, false) BD_PC_ROW(TC, NS, BK, 2, OUT_OPERAND, false, 1, false)                 \
+    BD_PC_ROW(TC, NS, BK, 3, OUT_F32, false, 0, false) BD_PC_ROW(TC, NS, BK, 3, OUT_F32, false, 1, false)
+// a non-native 16-bit output kind of a class: plain and with the fused q/k RMSNorm
+#define BD_PC_OUTK(TC, NS, BK, OUTK) BD_PC_ROW(TC, NS, BK, 1, OUTK, false, 1, false) BD_PC_ROW(TC, NS, BK, 2, OUTK, false, 1, false)
+bd_gemm_table pc_table() {
+    static const bd_gemm_row rows[] = {
+        BD_PC_CLASS(0, 1, 64)
+        BD_PC_CLASS(1, 1, 64) BD_PC_ROW(1, 1, 64, 2, OUT_OPERAND, false, 1, true)       // LayerNorm-fold consumer: the f16 q, k launch of the default mode
+        BD_PC_CLASS(0, 2, 32) BD_PC_OUTK(0, 2, 32, OUT_F16)                             // f16 from split-bf16 (strict f16 attention)
+        BD_PC_CLASS(1, 2, 32) BD_PC_OUTK(1, 2, 32, OUT_F16) BD_PC_OUTK(1, 2, 32, OUT_BF16X2)   // split-f16 QKV feeding split-bf16 attention
+        BD_PC_CLASS(2, 1, 128) BD_PC_OUTK(2, 1, 128, OUT_BF16)                          // bf16 from e4m3
+    };
+    return {BD_GEMM_FAMILY_PC, rows, (int)(sizeof(rows) / sizeof(rows[0]))};
+}
+#undef BD_PC_ROW
+#undef BD_PC_CLASS
+#undef BD_PC_OUTK
+
+#define BD_GLDS_ROW(TC, NS, BK, WM, WN, MI, NI, NSTG) \
+    {{TC, NS, BK, WM, WN, MI, NI, NSTG}, gemm_kernel_glds<elem_of<TC>::type, NS, BK, WM, WN, MI, NI, NSTG>},
+// 256 x 256; 128 x 128 and 64 x 64 on the two-stage ring (2 / 4 workgroups per CU) and on the sparse launches' four-stage ring
+#define BD_GLDS_CLASS(TC, NS, BK)                                                                                    \
+    BD_GLDS_ROW(TC, NS, BK, 2, 4, 4, 2, 2) BD_GLDS_ROW(TC, NS, BK, 2, 2, 2, 2, 2) BD_GLDS_ROW(TC, NS, BK, 2, 2, 2, 2, 4) \
+    BD_GLDS_ROW(TC, NS, BK, 2, 2, 1, 1, 2) BD_GLDS_ROW(TC, NS, BK, 2, 2, 1, 1, 4)
+bd_gemm_table glds_table() {
+    static const bd_gemm_row rows[] = {
+        BD_GLDS_CLASS(0, 1, 64) BD_GLDS_ROW(0, 1, 64, 4, 2, 2, 3, 2)           // (256 x 192: the one-plane classes)
+        BD_GLDS_CLASS(1, 1, 64) BD_GLDS_ROW(1, 1, 64, 4, 2, 2, 3, 2)
+        BD_GLDS_CLASS(0, 2, 32)
+        BD_GLDS_CLASS(1, 2, 32)
+        BD_GLDS_CLASS(2, 1, 128) BD_GLDS_ROW(2, 1, 128, 4, 2, 2, 3, 2)
+    };
+    return {BD_GEMM_FAMILY_GLDS, rows, (int)(sizeof(rows) / sizeof(rows[0]))};
+}
+#undef BD_GLDS_ROW
+#undef BD_GLDS_CLASS
+
 // Which epilogue specialisation of gemm_kernel_pc serves these arguments (0 = the generic one): see the kernel's header
-template <class T, int NS> int pc_epilogue_kind(const bd_gemm_args& a, int& outk, bool& gelu) {
-    outk = a.out_f32;
-    gelu = a.act == BD_ACT_GELU;
+int pc_epilogue_kind(const bd_gemm_args& a, const op_class& c) {
+    const int outk = a.out_f32;
+    const bool gelu = a.act == BD_ACT_GELU;
     if (a.addtab || a.rpg_in > 0) return 0;
     if (a.bias && ((uintptr_t)a.bias & 15)) return 0;
-    if (a.out_f32 == OUT_F32) {
-        if (gelu || a.rms_wq) return 0;
-        if (a.wscale && (sizeof(T) != 1 || ((uintptr_t)a.wscale & 15))) return 0;
-        return 3;
-    }
+    if (a.wscale && (c.esz != 1 || ((uintptr_t)a.wscale & 15))) return 0;
+    if (outk == OUT_F32) return (gelu || a.rms_wq) ? 0 : 3;
     if (a.resid) return 0;
-    if (a.wscale && (sizeof(T) != 1 || ((uintptr_t)a.wscale & 15))) return 0;
     // output kinds instantiated per operand class: native everywhere; f16 from split-bf16 (strict f16 attention), bf16 from e4m3
-    const bool outk_ok = outk == OUT_OPERAND || (outk == OUT_F16 && NS == 2 && sizeof(T) == 2) || (outk == OUT_BF16 && sizeof(T) == 1) ||
-                         (outk == OUT_BF16X2 && NS == 2 && std::is_same<T, _Float16>::value);   // split-f16 QKV feeding split-bf16 attention
+    const bool outk_ok = outk == OUT_OPERAND || (outk == OUT_F16 && c.ns == 2) || (outk == OUT_BF16 && c.esz == 1) ||
+                         (outk == OUT_BF16X2 && c.ns == 2 && c.tc == 1);   // split-f16 QKV feeding split-bf16 attention
     if (!outk_ok) return 0;
     if (a.rms_wq) return gelu ? 0 : 2;
     if (gelu && outk != OUT_OPERAND) return 0;
     return 1;
 }
 
-template <class T, int NS, int BK, int WM, int WN, int MI, int NI> void launch_pc(const bd_gemm_args& a, hipStream_t s, int cus) {
-    constexpr int TBM = WM * MI * 32, TBN = WN * NI * 32;
-    constexpr int NPW = 4;        // one producer wave per SIMD: a single wave issues one LDS-DMA piece per ~70 cycles, the CU ~23
-    const int tiles = ((a.M + TBM - 1) / TBM) * ((a.N + TBN - 1) / TBN);
-    const int grid = tiles < cus ? tiles : cus;
-    const dim3 g(grid), b((WM * WN + NPW) * 64);
-    int outk = 0;
-    bool gelu = false;
-    const int ep = (a.N % TBN == 0) ? pc_epilogue_kind<T, NS>(a, outk, gelu) : 0;
+// One launch of the persistent 256 x 192 kernel over `rows` rows from row0 (a: those rows' arguments)
+int plan_pc(const bd_gemm_args& a, const op_class& c, int cus, int row0, bd_gemm_plan_t& plan) {
+    const int tiles = ((a.M + 255) / 256) * ((a.N + 191) / 192);
+    const int ep = (a.N % 192 == 0) ? pc_epilogue_kind(a, c) : 0;
     // Operand ring: the asymmetric A3 / W2 form for every specialised epilogue (same-box A/B, profiles/r4_gemm_ring.md: K = 3072 +8-16 %,
     // split classes +3-9 %, e4m3 +4 %, K = 768 within 1 %) except the shallow fp32-residual Linears of the plain 16-bit classes (proj,
     // K = 768: HBM-bound, 2.5-5 % slower with it).  A row's result does not depend on the choice (same K order): it follows the
     // launch's class, K and epilogue only, never M.
-    const bool ring0_ep3 = NS == 1 && sizeof(T) == 2 && a.K < 1536;
-#define BD_PC_LAUNCH_R(EP_, OUTK_, GELU_, RING_) hipLaunchKernelGGL((gemm_kernel_pc<T, NS, BK, WM, WN, MI, NI, NPW, EP_, OUTK_, GELU_, RING_>), g, b, 0, s, a)
-#define BD_PC_LAUNCH(EP_, OUTK_, GELU_) BD_PC_LAUNCH_R(EP_, OUTK_, GELU_, ((EP_) != 0 ? 1 : 0))
-    constexpr int ALT = (NS == 2 && sizeof(T) == 2) ? OUT_F16 : (sizeof(T) == 1 ? OUT_BF16 : OUT_OPERAND);   // the one non-native 16-bit kind
-    constexpr bool X2 = NS == 2 && std::is_same<T, _Float16>::value;     // split-f16 also emits split-bf16 planes (attention input)
-    if (ln_fold_consumer(a)) {          // LayerNorm fold, consumer side: the f16 q, k launch of the default mode (bd_gemm_takes_ln_fold)
-        if constexpr (NS == 1 && std::is_same<T, _Float16>::value)
-            hipLaunchKernelGGL((gemm_kernel_pc<T, NS, BK, WM, WN, MI, NI, NPW, 2, OUT_OPERAND, false, 1, true>), g, b, 0, s, a);
-    }
-    else if (ep == 3 && ring0_ep3) BD_PC_LAUNCH_R(3, OUT_F32, false, 0);
-    else if (ep == 3) BD_PC_LAUNCH(3, OUT_F32, false);
-    else if (ep == 2 && outk == OUT_BF16X2) { if constexpr (X2) BD_PC_LAUNCH(2, OUT_BF16X2, false); }
-    else if (ep == 2) { if (outk == OUT_OPERAND) BD_PC_LAUNCH(2, OUT_OPERAND, false); else BD_PC_LAUNCH(2, ALT, false); }
-    else if (ep == 1 && gelu && outk == OUT_OPERAND) BD_PC_LAUNCH(1, OUT_OPERAND, true);
-    else if (ep == 1 && !gelu && outk == OUT_BF16X2) { if constexpr (X2) BD_PC_LAUNCH(1, OUT_BF16X2, false); }
-    else if (ep == 1 && !gelu) { if (outk == OUT_OPERAND) BD_PC_LAUNCH(1, OUT_OPERAND, false); else BD_PC_LAUNCH(1, ALT, false); }
-    else BD_PC_LAUNCH(0, OUT_OPERAND, false);
-#undef BD_PC_LAUNCH
-#undef BD_PC_LAUNCH_R
+    const bool ring0_ep3 = c.ns == 1 && c.esz == 2 && a.K < 1536;
+    const bool lnf = ln_fold_consumer(a);      // (only the f16 launch with the fused q/k RMSNorm and native output has such a row)
+    if (lnf && !(ep == 2 && a.out_f32 == OUT_OPERAND)) return BD_ERR_SHAPE;
+    const int ring = ep != 0 && !(ep == 3 && ring0_ep3);
+    return bd_plan_add(plan, pc_table(), {c.tc, c.ns, c.bk, 4, 2, 2, 3, 4, ep, ep == 0 ? (int)OUT_OPERAND : a.out_f32, ep == 1 && a.act == BD_ACT_GELU, ring, lnf},
+                       tiles < cus ? tiles : cus, 768, row0, a.M);
 }
 
-template <class T, int NS, int BK, int WM, int WN, int MI, int NI, int NSTG = 2> void launch_glds(const bd_gemm_args& a, hipStream_t s) {
-    constexpr int TBM = WM * MI * 32, TBN = WN * NI * 32;
-    const int tiles = ((a.M + TBM - 1) / TBM) * ((a.N + TBN - 1) / TBN);
-    hipLaunchKernelGGL((gemm_kernel_glds<T, NS, BK, WM, WN, MI, NI, NSTG>), dim3(tiles), dim3(WM * WN * 64), 0, s, a);
+int plan_glds(const bd_gemm_args& a, const op_class& c, int wm, int wn, int mi, int ni, int nstg, int row0, int rows, bd_gemm_plan_t& plan) {
+    const int tbm = wm * mi * 32, tbn = wn * ni * 32;
+    return bd_plan_add(plan, glds_table(), {c.tc, c.ns, c.bk, wm, wn, mi, ni, nstg}, ((rows + tbm - 1) / tbm) * ((a.N + tbn - 1) / tbn), wm * wn * 64, row0, rows);
 }
 
-template <class T> bd_gemm_args row_slice(const bd_gemm_args& a, int64_t row0, int rows) {
+// rows [row0, row0 + rows) of the problem as its own launch (no row remap / table: checked by the caller)
+bd_gemm_args row_slice(const bd_gemm_args& a, int esz, int64_t row0, int rows) {
     bd_gemm_args sub = a;
-    constexpr int ESZ = OpGeom<T>::ESZ;
-    const int osz = a.out_f32 == OUT_F32 ? 4 : (a.out_f32 == OUT_OPERAND ? ESZ : 2);
-    sub.A = (const unsigned char*)a.A + row0 * a.lda * ESZ;
+    const int osz = a.out_f32 == OUT_F32 ? 4 : (a.out_f32 == OUT_OPERAND ? esz : 2);
+    sub.A = (const unsigned char*)a.A + row0 * a.lda * esz;
     sub.out = (unsigned char*)a.out + row0 * a.ldo * osz;
     if (a.resid) sub.resid = a.resid + row0 * a.ldr;
     sub.M = rows;
@@ -703,13 +732,13 @@ template <class T> bd_gemm_args row_slice(const bd_gemm_args& a, int64_t row0, i
 inline bool pc192_possible(const bd_gemm_args& a, int ns, int esz) {
     return wide_epilogue_ok(a, ns) && 256 * a.lda * esz < ((int64_t)1 << 31) && 256 * a.ldw * esz < ((int64_t)1 << 31);
 }
-inline bool uses_pc192(const bd_gemm_args& a, int ns, int esz, int cus) {
-    if (!pc192_possible(a, ns, esz)) return false;
+inline bool uses_pc192(const bd_gemm_args& a, const op_class& c, int cus, int concurrent) {
+    if (!pc192_possible(a, c.ns, c.esz)) return false;
     if (a.rms_wq) return true;       // a fused q/k RMSNorm pins the tile shape for EVERY batch size: a sample's q, k must not
                                      // depend on whether its batch filled the CUs (bit-exact batch independence is tested)
     if (a.N % 192 || a.M < 1024) return false;
     // (sub-batch lanes enqueue this launch once per lane, side by side: the round their tiles fill is the round of all of them)
-    const int64_t t192 = (int64_t)((a.M + 255) / 256) * (a.N / 192) * bd_concurrent_launches();
+    const int64_t t192 = (int64_t)((a.M + 255) / 256) * (a.N / 192) * concurrent;
     // (0.75: DINOv2's N = 768 GEMMs at M = 50112 are 784 tiles = 3.06 rounds, fill 0.77.  One batch at a time the persistent kernel
     // is then +1.8 % on the step against the one-tile kernels' hybrid split; with two batches in flight -- the other batch's kernels
     // run on the CUs this kernel's tail leaves idle -- +5 %: 1221 -> 1282 poses/s same box.)
@@ -717,49 +746,30 @@ inline bool uses_pc192(const bd_gemm_args& a, int ns, int esz, int cus) {
     // 0.45 is never slower than 0.75 and 5-11 % faster at batch 5, 6, 12, 14 (0.35 loses 2 % at batch 3).
     return (double)t192 / (double)(((t192 + cus - 1) / cus) * cus) >= 0.45;       // occupancy of the CUs over the launch's rounds
 }
+
+int plan_one_tile(const bd_gemm_args& a, const op_class& oc, int kCUs, int row0, bd_gemm_plan_t& plan);
+
+// The plan of a launch in the 16-bit and e4m3 classes.
 // a fused q/k RMSNorm needs: 16-bit output of a plain Linear, N = 3 x heads x 96, row-identity output map, and N a multiple of
 // the 192-column workgroup tile: with an odd head count (N = 288 h, h odd) the last column tile's second wave tile would lie
-// past N, and the fused branch stores whole 96-column heads without a column guard
-
-template <class T, int NS, int BK> void launch_one_tile(const bd_gemm_args& a, hipStream_t s, int kCUs);
-
-// LayerNorm fold in the classes of this file: the consumer side only, and only the f16 launch with the fused q/k RMSNorm (which pins the
-// persistent 256 x 192 kernel for every row count)
-template <class T, int NS> bool takes_ln_fold(const bd_gemm_args& a) {
-    if (ln_fold_producer(a)) return false;
-    if (!ln_fold_consumer(a)) return true;
-    if (!(NS == 1 && std::is_same<T, _Float16>::value)) return false;
-    int outk = 0;
-    bool gelu = false;
-    return ln_fold_consumer_ok(a) && a.rms_wq && rms_geometry_ok(a) && pc192_possible(a, NS, OpGeom<T>::ESZ) && a.out_f32 == OUT_OPERAND &&
-           pc_epilogue_kind<T, NS>(a, outk, gelu) == 2;
-}
-
-template <class T, int NS, int BK> int launch(const bd_gemm_args& a, hipStream_t s) {
-    const int kCUs = cu_count();
-    if (a.rms_wq && !(rms_geometry_ok(a) && pc192_possible(a, NS, OpGeom<T>::ESZ))) return BD_ERR_SHAPE;
-    if ((ln_fold_producer(a) || ln_fold_consumer(a)) && !takes_ln_fold<T, NS>(a)) return BD_ERR_SHAPE;
-    const int slot = bd_trace_open(s, 0, a.M, a.N, a.K);
-    constexpr int ESZ_ = OpGeom<T>::ESZ;
+// past N, and the fused branch stores whole 96-column heads without a column guard.
+// LayerNorm fold in these classes: the consumer side only, and only the f16 launch with the fused q/k RMSNorm (which pins the
+// persistent 256 x 192 kernel for every row count): no other row of pc_table has it.
+int plan_gemm(const bd_gemm_args& a, const op_class& c, int cus, int concurrent, bd_gemm_plan_t& plan) {
+    if (a.rms_wq && !(rms_geometry_ok(a) && pc192_possible(a, c.ns, c.esz))) return BD_ERR_SHAPE;
+    if (ln_fold_producer(a) || (ln_fold_consumer(a) && !(ln_fold_consumer_ok(a) && a.rms_wq))) return BD_ERR_SHAPE;
     // 256 x 192 tiles (8 consumer waves of 64 x 96: 96 accumulator + 2 x 20 fragment registers fit the 168-VGPR budget
     // of three waves per SIMD with the fragment double-buffering intact) whenever they tile N exactly -- every Linear of
     // both stacks except the head (N = 2304, 3072, 768 are multiples of 192).
-    if (uses_pc192(a, NS, ESZ_, kCUs)) {
-        const int64_t rows_main = pc192_main_rows(a, kCUs);
-        if (rows_main < a.M) {
-            launch_pc<T, NS, BK, 4, 2, 2, 3>(row_slice<T>(a, 0, (int)rows_main), s, kCUs);
-            launch_one_tile<T, NS, BK>(row_slice<T>(a, rows_main, (int)(a.M - rows_main)), s, kCUs);
-        } else
-            launch_pc<T, NS, BK, 4, 2, 2, 3>(a, s, kCUs);
-    } else
-        launch_one_tile<T, NS, BK>(a, s, kCUs);
-    bd_trace_close(s, slot);
-    BD_CHECK_LAUNCH();
-    return BD_OK;
+    if (!uses_pc192(a, c, cus, concurrent)) return plan_one_tile(a, c, cus, 0, plan);
+    const int rows_main = (int)pc192_main_rows(a, cus);
+    if (rows_main == a.M) return plan_pc(a, c, cus, 0, plan);
+    if (const int rc = plan_pc(row_slice(a, c.esz, 0, rows_main), c, cus, 0, plan)) return rc;
+    return plan_one_tile(row_slice(a, c.esz, rows_main, a.M - rows_main), c, cus, rows_main, plan);
 }
 
-// the one-tile-per-workgroup kernels: everything the persistent kernel does not take
-template <class T, int NS, int BK> void launch_one_tile(const bd_gemm_args& a, hipStream_t s, int kCUs) {
+// the one-tile-per-workgroup kernels over a's rows (the problem's rows from row0): everything the persistent kernel does not take
+int plan_one_tile(const bd_gemm_args& a, const op_class& oc, int kCUs, int row0, bd_gemm_plan_t& plan) {
     {
         // Tile choice = best estimated efficiency: wave quantisation over the resident slots (256x256: one workgroup
         // per CU; 128x128: two; 64x64: four) times the measured relative mainloop efficiency of the tile
@@ -810,45 +820,61 @@ template <class T, int NS, int BK> void launch_one_tile(const bd_gemm_args& a, h
             const double ehyb = k256 > 0 ? (double)((a.M + 255) / 256) * (a.N / 256) / kCUs / hybrid_cost : e128;
             use192 = e192 > ehyb && e192 > e128;
         }
-        if constexpr (NS == 1) {
-            if (use192) {
-                launch_glds<T, NS, BK, 4, 2, 2, 3>(a, s);
-                return;
-            }
-        }
+        if (oc.ns == 1 && use192) return plan_glds(a, oc, 4, 2, 2, 3, 2, row0, a.M, plan);       // (the one-plane classes only)
         if (k256 > 0) {
-            const bd_gemm_args big = row_slice<T>(a, 0, (int)rows256);
-            launch_glds<T, NS, BK, 2, 4, 4, 2>(big, s);
-            if (rows256 < a.M) {
-                const bd_gemm_args rest = row_slice<T>(a, rows256, (int)(a.M - rows256));
-                launch_glds<T, NS, BK, 2, 2, 2, 2>(rest, s);
-            }
+            if (const int rc = plan_glds(a, oc, 2, 4, 4, 2, 2, row0, (int)rows256, plan)) return rc;
+            return rows256 < a.M ? plan_glds(a, oc, 2, 2, 2, 2, 2, row0 + (int)rows256, (int)(a.M - rows256), plan) : BD_OK;
         } else if (e256 >= e128 && e256 >= e64)
-            launch_glds<T, NS, BK, 2, 4, 4, 2>(a, s);             // 256 x 256, one tile per workgroup
+            return plan_glds(a, oc, 2, 4, 4, 2, 2, row0, a.M, plan);             // 256 x 256, one tile per workgroup
         else {
             // Sparse launches (small batch: every tile gets its own workgroup slot at once, so the launch lasts one tile's chain of
             // slab latencies): the 4-stage ring form of the same tile (three slabs in flight; 128 / 64 KiB of LDS: one / two per CU).
             const int64_t t128 = (int64_t)((a.M + 127) / 128) * ((a.N + 127) / 128), t64 = (int64_t)((a.M + 63) / 64) * ((a.N + 63) / 64);
-            if (e128 >= e64) {
-                if (t128 <= kCUs) launch_glds<T, NS, BK, 2, 2, 2, 2, 4>(a, s);
-                else launch_glds<T, NS, BK, 2, 2, 2, 2>(a, s);    // 128 x 128, 2 workgroups / CU
-            } else {
-                if (t64 <= 2 * kCUs) launch_glds<T, NS, BK, 2, 2, 1, 1, 4>(a, s);
-                else launch_glds<T, NS, BK, 2, 2, 1, 1>(a, s);    // 64 x 64 (latency mode: batch 1, M = 1536)
-            }
+            if (e128 >= e64) return plan_glds(a, oc, 2, 2, 2, 2, t128 <= kCUs ? 4 : 2, row0, a.M, plan);    // 128 x 128, 2 workgroups / CU
+            return plan_glds(a, oc, 2, 2, 1, 1, t64 <= 2 * kCUs ? 4 : 2, row0, a.M, plan);                  // 64 x 64 (latency mode: batch 1, M = 1536)
         }
     }
 }
+
+bool class_of(int prec, op_class& c) {
+    switch (prec) {
+        case BD_PREC_BF16: c = {0, 1, 64, 2}; return true;
+        case BD_PREC_F16: c = {1, 1, 64, 2}; return true;
+        case BD_PREC_BF16X3: c = {0, 2, 32, 2}; return true;
+        case BD_PREC_F16X3: c = {1, 2, 32, 2}; return true;
+        case BD_PREC_FP8: c = {2, 1, 128, 1}; return true;
+        default: return false;
+    }
+}
+
+// The plan of a launch that passed bd_gemm's argument checks, in whichever class
+int plan_class(const bd_gemm_args& a, int prec, int cus, int concurrent, bd_gemm_plan_t& plan) {
+    op_class c;
+    plan.n_launches = 0;
+    if (prec == BD_PREC_F16C8) return bd_plan_gemm_f16c8(a, cus, concurrent, plan);
+    return class_of(prec, c) ? plan_gemm(a, c, cus, concurrent, plan) : BD_ERR_DTYPE;
+}
+// Device-independent questions to the plan (forward.hip's plan_stack asks before any device is involved): the epilogue of a launch
+// follows its arguments alone, so any device parameters give the answer.
+int plan_any_device(const bd_gemm_args& a, int prec, bd_gemm_plan_t& plan) { return plan_class(a, prec, 256, 1, plan); }
 
 }  // namespace
 
 extern "C" int bd_gemm_fuses_qk_rmsnorm(const bd_gemm_args* args, int prec) {
     if (!args || !rms_geometry_ok(*args)) return 0;
+    const bd_gemm_args& a = *args;
+    // Fused = the launch runs on a persistent kernel: its EP 2, or its generic epilogue, whose rms branch normalises at run time.  With
+    // rms_wq set the plan either names such a launch or refuses.
+    bd_gemm_plan_t plan;
+    if (plan_any_device(a, prec, plan) == BD_OK) return plan.n_launches == 1 && plan.launch[0].family != BD_GEMM_FAMILY_GLDS ? 1 : 0;
+    // A refused launch still answers "yes" where the refusal has nothing to do with the RMSNorm (a LayerNorm fold that no form serves, the
+    // F16C8 operand layout): the answer has always looked at the head geometry and the persistent kernels' alignment conditions only, and
+    // it stays that way here -- tightening it is a change of its own (the cases are in tests/golden/gemm_forms.json).
     switch (prec) {
-        case BD_PREC_BF16: case BD_PREC_F16: return pc192_possible(*args, 1, 2) ? 1 : 0;
-        case BD_PREC_BF16X3: case BD_PREC_F16X3: return pc192_possible(*args, 2, 2) ? 1 : 0;
-        case BD_PREC_FP8: return pc192_possible(*args, 1, 1) ? 1 : 0;
-        case BD_PREC_F16C8: return wide_epilogue_ok(*args, 2) ? 1 : 0;
+        case BD_PREC_BF16: case BD_PREC_F16: return pc192_possible(a, 1, 2) ? 1 : 0;
+        case BD_PREC_BF16X3: case BD_PREC_F16X3: return pc192_possible(a, 2, 2) ? 1 : 0;
+        case BD_PREC_FP8: return pc192_possible(a, 1, 1) ? 1 : 0;
+        case BD_PREC_F16C8: return wide_epilogue_ok(a, 2) ? 1 : 0;
         default: return 0;
     }
 }
@@ -857,14 +883,14 @@ extern "C" int bd_gemm_takes_ln_fold(const bd_gemm_args* args, int prec) {
     if (!args) return 0;
     const bd_gemm_args& a = *args;
     if (!ln_fold_producer(a) && !ln_fold_consumer(a)) return 1;
-    switch (prec) {
-        case BD_PREC_F16: return takes_ln_fold<_Float16, 1>(a) ? 1 : 0;
-        case BD_PREC_F16C8: return bd_f16c8_takes_ln_fold(a) ? 1 : 0;
-        default: return 0;
-    }
+    // (F16C8: the epilogue half of its plan, without the refusals that concern the operands' layout -- the answer never looked at those)
+    if (prec == BD_PREC_F16C8) return bd_f16c8_takes_ln_fold(a) ? 1 : 0;
+    bd_gemm_plan_t plan;
+    return plan_any_device(a, prec, plan) == BD_OK ? 1 : 0;       // (only the f16 class has a row with the consumer epilogue)
 }
 
-extern "C" int bd_gemm(const bd_gemm_args* args, int prec, void* stream) {
+// bd_gemm's argument checks: everything that does not depend on the kernel form
+static int validate(const bd_gemm_args* args, int prec) {
     if (!args || !args->A || !args->W || !args->out) return BD_ERR_NULL;
     const bd_gemm_args& a = *args;
     const int kmult = prec == BD_PREC_FP8 ? 128 : 64;
@@ -881,15 +907,46 @@ extern "C" int bd_gemm(const bd_gemm_args* args, int prec, void* stream) {
     const bool needs_wide = a.out_f32 >= 2 || (prec == BD_PREC_FP8 && a.out_f32 == 0);
     if (needs_wide && ((a.N % 8) || (a.ldo % 8) || ((uintptr_t)a.out & 15))) return BD_ERR_ALIGN;
     if (a.wscale && ((uintptr_t)a.wscale & 15)) return BD_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    switch (prec) {
-        case BD_PREC_BF16: return launch<__bf16, 1, 64>(a, s);
-        case BD_PREC_F16: return launch<_Float16, 1, 64>(a, s);
-        case BD_PREC_BF16X3: return launch<__bf16, 2, 32>(a, s);
-        case BD_PREC_F16X3: return launch<_Float16, 2, 32>(a, s);
-        case BD_PREC_FP8: return launch<fp8e4, 1, 128>(a, s);
-        case BD_PREC_F16C8: return bd_launch_gemm_f16c8(a, s);
-        default: return BD_ERR_DTYPE;
-    }
+    return BD_OK;
 }
 
+// validate -> plan, for bd_gemm and bd_gemm_plan alike.  The two inputs of a plan that are not arguments are read here and nowhere else:
+// the device's size (cus <= 0), and -- by bd_gemm, passed in -- how many launches of this shape the caller (forward.hip's sub-batch
+// lanes) enqueues side by side.
+static int plan_checked(const bd_gemm_args* args, int prec, int cus, int concurrent, bd_gemm_plan_t& plan) {
+    plan.n_launches = 0;
+    if (const int rc = validate(args, prec)) return rc;
+    const int rc = plan_class(*args, prec, cus > 0 ? cus : cu_count(), concurrent > 0 ? concurrent : 1, plan);
+    if (rc != BD_OK) plan.n_launches = 0;
+    return rc;
+}
+
+extern "C" int bd_gemm_plan(const bd_gemm_args* args, int prec, int cus, int concurrent_launches, bd_gemm_plan_t* out) {
+    return out ? plan_checked(args, prec, cus, concurrent_launches, *out) : BD_ERR_NULL;
+}
+
+extern "C" int bd_gemm_instance(int family, int index, int* key) {
+    const bd_gemm_table t = family == BD_GEMM_FAMILY_PC ? pc_table() : family == BD_GEMM_FAMILY_GLDS ? glds_table()
+                            : family == BD_GEMM_FAMILY_PC_F16C8 ? bd_f16c8_table() : bd_gemm_table{0, nullptr, 0};
+    if (!key || index < 0 || index >= t.n) return 0;
+    for (int i = 0; i < BD_GEMM_KEY_LEN; ++i) key[i] = t.rows[index].key[i];
+    return 1;
+}
+
+extern "C" int bd_gemm(const bd_gemm_args* args, int prec, void* stream) {
+    bd_gemm_plan_t plan;
+    if (const int rc = plan_checked(args, prec, 0, bd_concurrent_launches(), plan)) return rc;
+    const bd_gemm_args& a = *args;
+    hipStream_t s = (hipStream_t)stream;
+    const int slot = bd_trace_open(s, 0, a.M, a.N, a.K);
+    for (int i = 0; i < plan.n_launches; ++i) {
+        const bd_gemm_launch& l = plan.launch[i];
+        const bd_gemm_table t = l.family == BD_GEMM_FAMILY_PC ? pc_table() : l.family == BD_GEMM_FAMILY_GLDS ? glds_table() : bd_f16c8_table();
+        bd_gemm_args la = l.rows == a.M ? a : row_slice(a, prec == BD_PREC_FP8 ? 1 : 2, l.row0, l.rows);
+        if (l.split_k > 1) la.sk_split = l.split_k;
+        hipLaunchKernelGGL(t.rows[l.row].fn, dim3(l.grid), dim3(l.block), 0, s, la);
+    }
+    bd_trace_close(s, slot);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}

@@ -859,6 +859,31 @@ inline int64_t pc192_main_rows(const bd_gemm_args& a, int cus) {
     return rows > 0 ? rows : a.M;
 }
 
+// ---- Plans and instance tables (include/boxdreamer_hip.h: bd_gemm_plan).  bd_gemm = validate -> plan -> launch: a plan function decides
+// everything on the host (no HIP call, no global state, no allocation) and names each launch's kernel by its template arguments; a table
+// per kernel family lists every instantiated kernel next to that key; launching is a lookup.  A key without a row is a plan error.
+typedef void (*bd_gemm_kernel)(const bd_gemm_args);
+struct bd_gemm_row { int key[BD_GEMM_KEY_LEN]; bd_gemm_kernel fn; };
+struct bd_gemm_table { int family; const bd_gemm_row* rows; int n; };
+
+// Appends one launch to a plan; BD_ERR_SHAPE when no instance has this key (or the plan is full): never a neighbouring instance.
+inline int bd_plan_add(bd_gemm_plan_t& p, const bd_gemm_table& t, const int (&key)[BD_GEMM_KEY_LEN], int grid, int block, int row0, int rows, int split_k = 1) {
+    if (p.n_launches >= BD_GEMM_PLAN_MAX_LAUNCHES) return BD_ERR_SHAPE;
+    for (int r = 0; r < t.n; ++r) {
+        int i = 0;
+        while (i < BD_GEMM_KEY_LEN && t.rows[r].key[i] == key[i]) ++i;
+        if (i < BD_GEMM_KEY_LEN) continue;
+        bd_gemm_launch& l = p.launch[p.n_launches++];
+        l.family = t.family;
+        l.row = r;
+        for (i = 0; i < BD_GEMM_KEY_LEN; ++i) l.key[i] = key[i];
+        l.grid = grid; l.block = block; l.row0 = row0; l.rows = rows; l.split_k = split_k;
+        return BD_OK;
+    }
+    return BD_ERR_SHAPE;
+}
+
 // the F16C8 class has its own persistent kernel (gemm_f16c8.hip); every shape goes through it
-int bd_launch_gemm_f16c8(const bd_gemm_args& a, hipStream_t s);
+bd_gemm_table bd_f16c8_table();
+int bd_plan_gemm_f16c8(const bd_gemm_args& a, int cus, int concurrent, bd_gemm_plan_t& plan);
 bool bd_f16c8_takes_ln_fold(const bd_gemm_args& a);

@@ -463,55 +463,87 @@ int& bd_concurrent_launches() {
     return n;
 }
 
-// Epilogue specialisation of a launch (gemm_kernel_pc's header): 0 generic, 1 / 2 16-bit results (2: fused q/k RMSNorm), 3 fp32 (+ residual)
-static int f16c8_epilogue_kind(const bd_gemm_args& a, int& outk, bool& gelu) {
+// Every instantiated gemm_kernel_pc_f16c8: one argument list gives a row's key and its kernel, so a key cannot name another instance.
+#define BD_C8_ROW(NSTAGE, EP, OUTK, GELU, WM, WN, NPW, LNF, SK) \
+    {{NSTAGE, EP, OUTK, GELU, WM, WN, NPW, LNF, SK}, gemm_kernel_pc_f16c8<NSTAGE, EP, OUTK, GELU, WM, WN, NPW, LNF, SK>},
+// a specialised epilogue in the small (128 x 192) and the large (256 x 192) form on three stages, and the large form on two
+#define BD_C8_FORMS(EP, OUTK, GELU) \
+    BD_C8_ROW(3, EP, OUTK, GELU, 2, 2, 4, false, false) BD_C8_ROW(3, EP, OUTK, GELU, 4, 2, 4, false, false) BD_C8_ROW(2, EP, OUTK, GELU, 4, 2, 4, false, false)
+// the LayerNorm-fold epilogues: three stages only, small and large form
+#define BD_C8_FORMS_LN(EP, OUTK, GELU, LNF) \
+    BD_C8_ROW(3, EP, OUTK, GELU, 2, 2, 4, LNF, false) BD_C8_ROW(3, EP, OUTK, GELU, 4, 2, 4, LNF, false)
+// the fp32-residual kinds on 128 x 96 tiles (2 + 2 waves), unsplit and split-K
+#define BD_C8_FORMS_96(EP, OUTK) BD_C8_ROW(3, EP, OUTK, false, 2, 1, 2, false, false) BD_C8_ROW(3, EP, OUTK, false, 2, 1, 2, false, true)
+bd_gemm_table bd_f16c8_table() {
+    static const bd_gemm_row rows[] = {
+        // generic epilogue: either ring depth, small and large form
+        BD_C8_ROW(3, 0, OUT_OPERAND, false, 2, 2, 4, false, false) BD_C8_ROW(2, 0, OUT_OPERAND, false, 2, 2, 4, false, false)
+        BD_C8_ROW(3, 0, OUT_OPERAND, false, 4, 2, 4, false, false) BD_C8_ROW(2, 0, OUT_OPERAND, false, 4, 2, 4, false, false)
+        BD_C8_FORMS(1, OUT_OPERAND, false) BD_C8_FORMS(1, OUT_OPERAND, true) BD_C8_FORMS(1, OUT_F16, false) BD_C8_FORMS(1, OUT_BF16X2, false)
+        BD_C8_FORMS(2, OUT_OPERAND, false) BD_C8_FORMS(2, OUT_F16, false) BD_C8_FORMS(2, OUT_BF16X2, false)
+        BD_C8_FORMS(3, OUT_F32, false)
+        BD_C8_FORMS_LN(4, OUT_F32, false, false) BD_C8_FORMS_LN(5, OUT_F32, false, false) BD_C8_FORMS_LN(5, OUT_OPERAND, false, false)
+        BD_C8_FORMS_LN(1, OUT_OPERAND, true, true) BD_C8_FORMS_LN(1, OUT_F16, false, true) BD_C8_FORMS_LN(1, OUT_BF16X2, false, true)
+        BD_C8_FORMS_LN(2, OUT_F16, false, true)
+        BD_C8_FORMS_96(3, OUT_F32) BD_C8_FORMS_96(4, OUT_F32) BD_C8_FORMS_96(5, OUT_F32) BD_C8_FORMS_96(5, OUT_OPERAND)
+    };
+    return {BD_GEMM_FAMILY_PC_F16C8, rows, (int)(sizeof(rows) / sizeof(rows[0]))};
+}
+#undef BD_C8_ROW
+#undef BD_C8_FORMS
+#undef BD_C8_FORMS_LN
+#undef BD_C8_FORMS_96
+
+// The epilogue instance of a launch -- the half of the plan that does not depend on the device, and what the predicates ask about.
+// ep (gemm_kernel_pc's header): 0 generic, 1 / 2 16-bit results (2: fused q/k RMSNorm), 3 fp32 (+ residual), 4 / 5 the LayerNorm-fold
+// producers (5: the residual comes from, and goes back to, the operand copy); lnf: LayerNorm-fold consumer.
+struct f16c8_form { int ep, outk; bool gelu, lnf; };
+
+// BD_OK, or BD_ERR_SHAPE for a LayerNorm fold (bd_gemm_args.ln_*) that no kernel form of this class serves.  Producer: the fp32-residual
+// epilogue (EP 3 -> 4, 5) of a three-stage launch.  Consumer: K = 768 (three stages), the 16-bit epilogues fc1 (+ GELU), DINOv2's QKV
+// (split-bf16 planes), BETR's v columns / whole QKV (f16 plane; with the fused q/k RMSNorm).
+static int f16c8_plan_form(const bd_gemm_args& a, f16c8_form& f) {
+    const int outk = a.out_f32;
+    const bool gelu = a.act == BD_ACT_GELU;
+    const bool special = !a.addtab && a.rpg_in <= 0 && !a.wscale && a.N % 192 == 0 && a.K >= 128 && !(a.bias && ((uintptr_t)a.bias & 15));
     int ep = 0;
-    outk = a.out_f32;
-    gelu = a.act == BD_ACT_GELU;
-    if (!a.addtab && a.rpg_in <= 0 && !a.wscale && a.N % 192 == 0 && a.K >= 128 && !(a.bias && ((uintptr_t)a.bias & 15))) {
-        if (a.out_f32 == OUT_F32) ep = (gelu || a.rms_wq) ? 0 : 3;
+    if (special) {
+        if (outk == OUT_F32) ep = (gelu || a.rms_wq) ? 0 : 3;
         else if (!a.resid && (outk == OUT_OPERAND || outk == OUT_F16 || outk == OUT_BF16X2)) ep = a.rms_wq ? (gelu ? 0 : 2) : 1;
     }
     if (ep == 1 && gelu && outk != OUT_OPERAND) ep = 0;
-    return ep;
+    f = {ep, ep == 0 ? (int)OUT_OPERAND : outk, ep != 0 && gelu, false};       // (the generic epilogue reads kind and activation at run time)
+    const bool lnp = ln_fold_producer(a), lnc = ln_fold_consumer(a);
+    if (!lnp && !lnc) return BD_OK;
+    if ((a.K / 32) % 3 != 0 || !wide_epilogue_ok(a, 2)) return BD_ERR_SHAPE;
+    if (lnp) {
+        // the fp32-residual epilogue's launch conditions, also for the form that reads the residual from the operand copy and may write
+        // no fp32 rows at all (its out_f32 may be 0: ep is 1 there)
+        if (!ln_fold_producer_ok(a) || !special || gelu || a.rms_wq || (!a.ln_resid_in_op && ep != 3)) return BD_ERR_SHAPE;
+        f.ep = a.ln_resid_in_op ? 5 : 4;
+    }
+    if (lnc) {
+        if (!ln_fold_consumer_ok(a) || lnp) return BD_ERR_SHAPE;
+        if (!((ep == 1 && gelu) || (ep == 1 && (outk == OUT_F16 || outk == OUT_BF16X2)) || (ep == 2 && outk == OUT_F16))) return BD_ERR_SHAPE;
+        f.lnf = true;
+    }
+    return BD_OK;
 }
 
-// LayerNorm fold (bd_gemm_args.ln_*): which of the requested sides this class's kernel forms serve.  Producer: the fp32-residual epilogue
-// (EP 3 -> 4) of a three-stage launch.  Consumer: K = 768 (three stages), the 16-bit epilogues fc1 (+ GELU), DINOv2's QKV (split-bf16
-// planes), BETR's v columns / whole QKV (f16 plane; with the fused q/k RMSNorm).
 bool bd_f16c8_takes_ln_fold(const bd_gemm_args& a) {
-    int outk = 0;
-    bool gelu = false;
-    const int ep = f16c8_epilogue_kind(a, outk, gelu);
-    const bool s3 = (a.K / 32) % 3 == 0;
-    if (!s3 || !wide_epilogue_ok(a, 2)) return false;
-    if (ln_fold_producer(a)) {
-        if (!ln_fold_producer_ok(a)) return false;
-        // the fp32-residual epilogue's launch conditions (f16c8_epilogue_kind's ep == 3), also for the form that reads the residual from the
-        // operand copy and may write no fp32 rows at all
-        const bool base = !a.addtab && a.rpg_in <= 0 && !a.wscale && a.N % 192 == 0 && a.K >= 128 && !(a.bias && ((uintptr_t)a.bias & 15)) &&
-                          !gelu && !a.rms_wq;
-        if (!base || (!a.ln_resid_in_op && ep != 3)) return false;
-    }
-    if (ln_fold_consumer(a)) {
-        if (!ln_fold_consumer_ok(a)) return false;
-        const bool form = (ep == 1 && gelu && outk == OUT_OPERAND) || (ep == 1 && !gelu && (outk == OUT_F16 || outk == OUT_BF16X2)) ||
-                          (ep == 2 && outk == OUT_F16);
-        if (!form) return false;
-    }
-    return true;
+    f16c8_form f;
+    return f16c8_plan_form(a, f) == BD_OK;
 }
 
 // Split-K factor of a launch (1 = none).  Only with a scratch region from the caller, only the fp32-residual epilogue kinds on the 128 x 96
 // form (one tile per workgroup), only where S workgroups per tile still fit the chip's 2 x CUs slots of that form at once.  args.sk_split
 // forces a factor (tests, tuning); otherwise the largest of 2 .. 4 that fits, with at least 6 slabs per workgroup.
-static int f16c8_split_k(const bd_gemm_args& a, int ep, bool r5, bool lnp, bool s3, int cus) {
-    (void)lnp;                             // (a producer launch that is not r5 has ep == 3: bd_f16c8_takes_ln_fold)
-    if (!a.sk_ws || ((uintptr_t)a.sk_ws & 255) || !s3 || a.N % 96 != 0 || !bd_gemm_splitk_flag_bytes(a.M, a.N) || !(ep == 3 || r5)) return 1;
+static int f16c8_split_k(const bd_gemm_args& a, int ep, bool s3, int cus, int concurrent) {
+    if (!a.sk_ws || ((uintptr_t)a.sk_ws & 255) || !s3 || a.N % 96 != 0 || !bd_gemm_splitk_flag_bytes(a.M, a.N) || ep < 3) return 1;
     const int t96 = ((a.M + 127) / 128) * (a.N / 96), nk = a.K / 32;
     // one workgroup per CU: two of this form on a CU put both their consumer-wave pairs on the same two SIMDs (measured: fc2 at 1536 rows
     // 34 us with S = 2 = 192 workgroups, 43 us with S = 3 = 288; profiles/r6_split_k.md)
-    const int slots = cus / (bd_concurrent_launches() > 0 ? bd_concurrent_launches() : 1);
+    const int slots = cus / concurrent;
     int sk = a.sk_split;
     if (sk <= 0) {
         sk = 1;
@@ -534,96 +566,40 @@ extern "C" size_t bd_gemm_splitk_workspace_bytes(int M, int N) {
     return fb + t96 * 3 * 2 * (size_t)(64 * 96 * 4);               // + [tile][3][2][64 x 96 fp32 accumulators of a wave tile]
 }
 
-// F16C8 has its own persistent kernel; every shape goes through it
-int bd_launch_gemm_f16c8(const bd_gemm_args& a, hipStream_t s) {
+// The plan of a BD_PREC_F16C8 launch: the class has its own persistent kernel, every shape is one launch of it.
+int bd_plan_gemm_f16c8(const bd_gemm_args& a, int cus, int concurrent, bd_gemm_plan_t& plan) {
     if (!wide_epilogue_ok(a, 2) || 256 * a.lda * 2 >= ((int64_t)1 << 31) || 256 * a.ldw * 2 >= ((int64_t)1 << 31)) return BD_ERR_ALIGN;
     if ((a.K % 32) || (a.lda % 32) || (a.ldw % 32)) return BD_ERR_SHAPE;            // the lo8 planes are laid out in 32-element blocks
     if (a.out_f32 == OUT_OPERAND && (a.ldo % 32)) return BD_ERR_SHAPE;
     if (a.w_qexp + BD_F16C8_D < -100 || a.w_qexp + BD_F16C8_D > 120) return BD_ERR_SHAPE;
     if (a.rms_wq && !rms_geometry_ok(a)) return BD_ERR_SHAPE;
-    const bool lnp = ln_fold_producer(a), lnc = ln_fold_consumer(a);
-    if ((lnp || lnc) && !bd_f16c8_takes_ln_fold(a)) return BD_ERR_SHAPE;
-    const int slot = bd_trace_open(s, 0, a.M, a.N, a.K);
-    const int cus = cu_count();
-    const int tiles = ((a.M + 255) / 256) * ((a.N + 191) / 192);
-    // epilogue specialisation (gemm_kernel_pc's header): native / f16 / split-bf16 16-bit results, fp32 (+ residual)
-    int outk = 0;
-    bool gelu = false;
-    const int ep = f16c8_epilogue_kind(a, outk, gelu);
+    // epilogue specialisation (gemm_kernel_pc's header): native / f16 / split-bf16 16-bit results, fp32 (+ residual), LayerNorm fold
+    f16c8_form f;
+    if (const int rc = f16c8_plan_form(a, f)) return rc;
+    const int ep = f.ep;
+    const bd_gemm_table table = bd_f16c8_table();
     const bool s3 = (a.K / 32) % 3 == 0;
-    // The SMALL form (128 x 192 tiles, one consumer wave per SIMD) where the large tiles would occupy at most half of the CUs -- one pose at
-    // a time: M = 1536 is 24-96 large tiles on 256 CUs; with sub-batch lanes, of the CUs' share of one lane.  Measured per shape and row count (profiles/r5_f16c8_small_form.md): up to 128 large
-    // tiles the small form is 5-35 % faster, from 144 on it is slower (a lone consumer wave per SIMD needs ~1400 cycles per slab where two
-    // need ~2000 for twice the work).  Three-stage ring (K / 32 a multiple of 3: every K of the path) and specialised epilogues only.
-    // Every row's result is unchanged.
-    const int tiles_small = ((a.M + 127) / 128) * ((a.N + 191) / 192);
-    const bool small = s3 && ep != 0 && 2 * tiles * bd_concurrent_launches() <= cus;      // (sub-batch lanes: their launches share the CUs)
-    const bool small0 = ep == 0 && 2 * tiles * bd_concurrent_launches() <= cus;             // the generic epilogue's small form (either ring depth)
-    const dim3 g0(tiles_small < cus ? tiles_small : cus);
-    const int grid = small ? (tiles_small < cus ? tiles_small : cus) : (tiles < cus ? tiles : cus);
-    const dim3 g(grid), b(small ? 512 : 768);
-#define BD_C8_LAUNCH(EP_, OUTK_, GELU_)                                                                     \
-    { if (small) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, EP_, OUTK_, GELU_, 2, 2, 4>), g, b, 0, s, a);     \
-      else if (s3) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, EP_, OUTK_, GELU_>), g, b, 0, s, a);            \
-      else hipLaunchKernelGGL((gemm_kernel_pc_f16c8<2, EP_, OUTK_, GELU_>), g, b, 0, s, a); }
-    // (LayerNorm fold: three-stage forms only -- bd_f16c8_takes_ln_fold)
-#define BD_C8_LAUNCH_LN(EP_, OUTK_, GELU_, LNF_)                                                                        \
-    { if (small) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, EP_, OUTK_, GELU_, 2, 2, 4, LNF_>), g, b, 0, s, a);         \
-      else hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, EP_, OUTK_, GELU_, 4, 2, 4, LNF_>), g, b, 0, s, a); }
-    // fc2 (deep K, 4 column tiles) below ~4096 rows: 128 x 96 tiles on 2 + 2 waves -- four times the workgroups of the large form, still at most
-    // one per CU -- is another 17 % faster than the 128 x 192 form (52 vs 63 us at 1536 rows; everywhere else it is slower:
-    // profiles/r5_f16c8_small_form.md).  One instance (+ its LayerNorm-fold producer twin).
-    const bool r5 = lnp && a.ln_resid_in_op;              // the residual comes from (and goes back to) the operand copy: EP 5
-    const bool fc2_96 = (ep == 3 || r5) && small && a.K >= 2048 && a.N % 96 == 0 && 4 * tiles * bd_concurrent_launches() <= cus;
     // Split-K (the caller lent a scratch region: bd_gemm_args.sk_ws): the fp32-residual Linears of a launch whose 128 x 96 tiles would still
     // leave most of the chip idle -- one pose at a time, fc2 / proj on 1536 rows: 96 tiles on 256 CUs (two workgroups of this form fit a CU);
     // the last decoder block's query rows: 16 tiles.  S workgroups per tile, see the kernel's header.
-    const int sk = f16c8_split_k(a, ep, r5, lnp, s3, cus);
-    if (sk > 1) {
-        bd_gemm_args b2 = a;
-        b2.sk_split = sk;
-        const int t96 = ((a.M + 127) / 128) * (a.N / 96);
-        const dim3 gs(((t96 + 7) / 8) * 8 * sk), bs(256);
-        if (r5 && a.out_f32 == OUT_F32) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 5, OUT_F32, false, 2, 1, 2, false, true>), gs, bs, 0, s, b2);
-        else if (r5) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 5, OUT_OPERAND, false, 2, 1, 2, false, true>), gs, bs, 0, s, b2);
-        else if (lnp) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 4, OUT_F32, false, 2, 1, 2, false, true>), gs, bs, 0, s, b2);
-        else hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 3, OUT_F32, false, 2, 1, 2, false, true>), gs, bs, 0, s, b2);
-        bd_trace_close(s, slot);
-        BD_CHECK_LAUNCH();
-        return BD_OK;
-    }
-    if (r5 && fc2_96 && a.out_f32 == OUT_F32)
-        hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 5, OUT_F32, false, 2, 1, 2>), dim3(((a.M + 127) / 128) * (a.N / 96)), dim3(256), 0, s, a);
-    else if (r5 && fc2_96)
-        hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 5, OUT_OPERAND, false, 2, 1, 2>), dim3(((a.M + 127) / 128) * (a.N / 96)), dim3(256), 0, s, a);
-    else if (r5 && a.out_f32 == OUT_F32) BD_C8_LAUNCH_LN(5, OUT_F32, false, false)
-    else if (r5) BD_C8_LAUNCH_LN(5, OUT_OPERAND, false, false)
-    else if (lnp && fc2_96)
-        hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 4, OUT_F32, false, 2, 1, 2>), dim3(((a.M + 127) / 128) * (a.N / 96)), dim3(256), 0, s, a);
-    else if (lnp) BD_C8_LAUNCH_LN(4, OUT_F32, false, false)
-    else if (lnc && ep == 1 && gelu) BD_C8_LAUNCH_LN(1, OUT_OPERAND, true, true)
-    else if (lnc && ep == 1 && outk == OUT_F16) BD_C8_LAUNCH_LN(1, OUT_F16, false, true)
-    else if (lnc && ep == 1) BD_C8_LAUNCH_LN(1, OUT_BF16X2, false, true)
-    else if (lnc) BD_C8_LAUNCH_LN(2, OUT_F16, false, true)
-    else if (fc2_96)
-        hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 3, OUT_F32, false, 2, 1, 2>), dim3(((a.M + 127) / 128) * (a.N / 96)), dim3(256), 0, s, a);
-    else if (ep == 3) BD_C8_LAUNCH(3, OUT_F32, false)
-    else if (ep == 2 && outk == OUT_OPERAND) BD_C8_LAUNCH(2, OUT_OPERAND, false)
-    else if (ep == 2 && outk == OUT_F16) BD_C8_LAUNCH(2, OUT_F16, false)
-    else if (ep == 2) BD_C8_LAUNCH(2, OUT_BF16X2, false)
-    else if (ep == 1 && gelu) BD_C8_LAUNCH(1, OUT_OPERAND, true)
-    else if (ep == 1 && outk == OUT_OPERAND) BD_C8_LAUNCH(1, OUT_OPERAND, false)
-    else if (ep == 1 && outk == OUT_F16) BD_C8_LAUNCH(1, OUT_F16, false)
-    else if (ep == 1) BD_C8_LAUNCH(1, OUT_BF16X2, false)
-    // generic epilogue (table add, row remap, hand-offs between operand classes: the patch / heat-map embeddings, the adapter): round 6 gives
-    // it the small form too -- one pose at a time these launches were 24 workgroups of the large form, 64 us each (rows bit-identical)
-    else if (small0 && s3) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 0, OUT_OPERAND, false, 2, 2, 4>), g0, dim3(512), 0, s, a);
-    else if (small0) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<2, 0, OUT_OPERAND, false, 2, 2, 4>), g0, dim3(512), 0, s, a);
-    else if (s3) hipLaunchKernelGGL((gemm_kernel_pc_f16c8<3, 0, OUT_OPERAND, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((gemm_kernel_pc_f16c8<2, 0, OUT_OPERAND, false>), g, b, 0, s, a);
-#undef BD_C8_LAUNCH
-#undef BD_C8_LAUNCH_LN
-    bd_trace_close(s, slot);
-    BD_CHECK_LAUNCH();
-    return BD_OK;
+    const int t96 = ((a.M + 127) / 128) * (a.N / 96);
+    const int sk = f16c8_split_k(a, ep, s3, cus, concurrent);
+    if (sk > 1) return bd_plan_add(plan, table, {3, ep, f.outk, false, 2, 1, 2, false, true}, ((t96 + 7) / 8) * 8 * sk, 256, 0, a.M, sk);
+    // The SMALL form (128 x 192 tiles, one consumer wave per SIMD) where the large tiles would occupy at most half of the CUs -- one pose at
+    // a time: M = 1536 is 24-96 large tiles on 256 CUs; with sub-batch lanes, of the CUs' share of one lane (their launches share the CUs).
+    // Measured per shape and row count (profiles/r5_f16c8_small_form.md): up to 128 large
+    // tiles the small form is 5-35 % faster, from 144 on it is slower (a lone consumer wave per SIMD needs ~1400 cycles per slab where two
+    // need ~2000 for twice the work).  The specialised epilogues on the three-stage ring only (K / 32 a multiple of 3: every K of the path);
+    // the generic epilogue (table add, row remap, hand-offs between operand classes: the patch / heat-map embeddings, the adapter) on either
+    // ring depth since round 6 -- one pose at a time these launches were 24 workgroups of the large form, 64 us each.
+    // Every row's result is unchanged.
+    const int tiles = ((a.M + 255) / 256) * ((a.N + 191) / 192), tiles_small = ((a.M + 127) / 128) * ((a.N + 191) / 192);
+    const bool small = (s3 || ep == 0) && 2 * tiles * concurrent <= cus;
+    // fc2 (deep K, 4 column tiles) below ~4096 rows: 128 x 96 tiles on 2 + 2 waves -- four times the workgroups of the large form, still at most
+    // one per CU -- is another 17 % faster than the 128 x 192 form (52 vs 63 us at 1536 rows; everywhere else it is slower:
+    // profiles/r5_f16c8_small_form.md).  The fp32-residual kinds only.
+    if (ep >= 3 && small && a.K >= 2048 && a.N % 96 == 0 && 4 * tiles * concurrent <= cus)
+        return bd_plan_add(plan, table, {3, ep, f.outk, false, 2, 1, 2, false, false}, t96, 256, 0, a.M);
+    const int nt = small ? tiles_small : tiles;
+    return bd_plan_add(plan, table, {s3 ? 3 : 2, ep, f.outk, f.gelu, small ? 2 : 4, 2, 4, f.lnf, false}, nt < cus ? nt : cus, small ? 512 : 768, 0, a.M);
 }

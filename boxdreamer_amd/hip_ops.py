@@ -101,16 +101,68 @@ _OUT_DTYPES = {2: torch.float16, 3: torch.bfloat16}      # single planes; 4 / 5:
 _OUT_SPLIT = {4: torch.bfloat16, 5: torch.float16}
 
 
+_FAMILY = {_lib.GEMM_FAMILY_PC: "pc", _lib.GEMM_FAMILY_GLDS: "glds", _lib.GEMM_FAMILY_PC_F16C8: "pc_f16c8"}
+
+
+def gemm_plan(g, prec, cus=0, concurrent=1):
+    """bd_gemm_plan (host only): the launches bd_gemm(g, prec) makes on a device of `cus` CUs (0: the current one), one dict each --
+    family ("pc": persistent, "glds": one tile per workgroup, "pc_f16c8"), tile (rows, columns), stages (of the slab ring; "pc": 3 = the
+    A3 / W2 operand ring, 2 = none), ep / outk / gelu / lnf (None for "glds": its epilogue is chosen at run time), split_k, grid, block,
+    row0, rows, key.  Raises HipLibraryError where bd_gemm refuses the arguments."""
+    plan = _lib.GemmPlan()
+    check(_lib.load().bd_gemm_plan(C.byref(g), prec_id(prec), int(cus), int(concurrent), C.byref(plan)), "bd_gemm_plan")
+    out = []
+    for l in plan.launch[:plan.n_launches]:
+        k = list(l.key)
+        d = {"family": _FAMILY[l.family], "key": k, "grid": l.grid, "block": l.block, "row0": l.row0, "rows": l.rows, "split_k": l.split_k,
+             "ep": None, "outk": None, "gelu": None, "lnf": None}
+        if l.family == _lib.GEMM_FAMILY_PC_F16C8:
+            d.update(tile=(k[4] * 64, k[5] * 96), stages=k[0], ep=k[1], outk=k[2], gelu=bool(k[3]), lnf=bool(k[7]))
+        else:
+            d.update(tile=(k[3] * k[5] * 32, k[4] * k[6] * 32))
+            if l.family == _lib.GEMM_FAMILY_PC:
+                d.update(stages=3 if k[11] else 2, ep=k[8], outk=k[9], gelu=bool(k[10]), lnf=bool(k[12]))
+            else:
+                d.update(stages=k[7])
+        out.append(d)
+    return out
+
+
+def gemm_shape_args(M, N, K, **fields):
+    """bd_gemm_args of an M x N x K launch on dense operands at made-up, aligned addresses: for asking gemm_plan about a shape before
+    any tensor exists.  fields: further members, a pointer given as True (an aligned address)."""
+    g = _lib.GemmArgs()
+    g.M, g.N, g.K, g.lda, g.ldw, g.ldo, g.ldr, g.ln_op_ld = M, N, K, K, K, N, N, N
+    g.a_plane = g.w_plane = g.out_plane = g.ln_op_plane = 1 << 28
+    kinds = dict(_lib.GemmArgs._fields_)
+    for i, name in enumerate(("A", "W", "out", "bias") + tuple(fields)):
+        v = fields.get(name, True)
+        setattr(g, name, (0x7F0000000000 + 0x1000 * (i + 1) if v else None) if kinds[name] is C.c_void_p and isinstance(v, bool) else v)
+    return g
+
+
+def _check_expect(g, prec, expect):
+    """expect: what gemm_plan must say of the launch about to be made -- a dict (every launch has these values) or a list of dicts (one
+    per launch, in order)."""
+    plan = gemm_plan(g, prec)
+    wants = expect if isinstance(expect, (list, tuple)) else [expect] * len(plan)
+    assert len(wants) == len(plan), f"{len(plan)} launches planned, {len(wants)} expected: {plan}"
+    for want, got in zip(wants, plan):
+        for k, v in want.items():
+            assert got[k] == (tuple(v) if k == "tile" else v), f"the plan's {k} is {got[k]}, the test expects {v}: {got}"
+
+
 def gemm(a16, w16, bias=None, *, prec="bf16", act=_lib.ACT_NONE, resid=None, addtab=None, out=None,
          out_f32=False, n=None, out_rows=None, rpg=(0, 0, 0), wscale=None, out_mode=None, w_qexp=0, rms=None,
-         ln_emit=None, ln_apply=None, ln_resid_in_op=False, split_k=None):
+         ln_emit=None, ln_apply=None, ln_resid_in_op=False, split_k=None, expect=None):
     """out[map(r)] = act(wscale * (A W^T) + bias) + addtab[r % rows(addtab)] + resid[map(r)].
     out_mode: None -> operand dtype (or fp32 with out_f32), 2 -> f16 single plane, 3 -> bf16 single plane, 4 -> split-bf16 (hi, lo)
     planes, 5 -> split-f16 (hi, lo) planes (bd_gemm_args.out_f32, include/boxdreamer_hip.h).
     LayerNorm fold (ABI 8): ln_emit = (stats [M, N / 96, 2] fp32, operand copy [2, M, N] F16C8 storage) -- the producer side;
     ln_apply = (stats [M, 8, 2], column sums [N], eps) -- the consumer side.
     split_k = (scratch uint8 tensor of splitk_workspace_bytes(M, N) whose first 16 KiB are zero, factor 0 = library's choice | 2 .. 4):
-    bd_gemm_args.sk_ws / sk_split (ABI 9)."""
+    bd_gemm_args.sk_ws / sk_split (ABI 9).
+    expect (tests): the kernel form this launch must take, checked against gemm_plan before the launch (_check_expect)."""
     lib = _lib.load()
     np_ = planes(prec)
     A2 = a16[0] if np_ == 2 else a16
@@ -154,6 +206,8 @@ def gemm(a16, w16, bias=None, *, prec="bf16", act=_lib.ACT_NONE, resid=None, add
         g.sk_ws, g.sk_split = ptr(split_k[0]), int(split_k[1])
     if (ln_emit is not None or ln_apply is not None) and not lib.bd_gemm_takes_ln_fold(C.byref(g), prec_id(prec)):
         raise ValueError("bd_gemm_takes_ln_fold: this launch has no kernel form with the LayerNorm-fold epilogues")
+    if expect is not None:
+        _check_expect(g, prec, expect)
     check(lib.bd_gemm(C.byref(g), prec_id(prec), stream()), "bd_gemm")
     return out
 

@@ -205,6 +205,37 @@ int bd_gemm_takes_ln_fold(const bd_gemm_args* args /*[host]*/, int prec);
 /* 1 if bd_gemm(args, prec) with args->rms_wq set would fuse the q/k RMSNorm (tile shape and head geometry fit), else 0. */
 int bd_gemm_fuses_qk_rmsnorm(const bd_gemm_args* args /*[host]*/, int prec);
 
+/* Which kernel instances bd_gemm(args, prec) launches, decided on the host (no GPU needed, nothing is launched or dereferenced; for
+ * tests and tools -- nothing on the product path calls these).  bd_gemm plans with the same function and then launches the plan.
+ * A launch names one row of its kernel family's instance table: `key` holds the instance's template arguments as integers, in
+ * declaration order, unused entries 0:
+ *   BD_GEMM_FAMILY_PC        gemm_kernel_pc        T (0 bf16, 1 f16, 2 e4m3), NS, BK, WM, WN, MI, NI, NPW, EP, OUTK, GELU, RING, LNF
+ *   BD_GEMM_FAMILY_GLDS      gemm_kernel_glds      T, NS, BK, WM, WN, MI, NI, NSTG
+ *   BD_GEMM_FAMILY_PC_F16C8  gemm_kernel_pc_f16c8  NSTAGE, EP, OUTK, GELU, WM, WN, NPW, LNF, SK
+ * (a workgroup tile is WM MI 32 x WN NI 32; EP: 0 generic epilogue, 1 16-bit result, 2 fused q/k RMSNorm, 3 fp32 + residual, 4 / 5 the
+ * LayerNorm-fold producers; LNF: LayerNorm-fold consumer; OUTK: a value of bd_gemm_args.out_f32).  The launches of a plan cover the
+ * disjoint row ranges [row0, row0 + rows) of the problem; split_k is 1 or the split-K factor S the launch runs with. */
+#define BD_GEMM_FAMILY_PC 1
+#define BD_GEMM_FAMILY_GLDS 2
+#define BD_GEMM_FAMILY_PC_F16C8 3
+#define BD_GEMM_KEY_LEN 13
+#define BD_GEMM_PLAN_MAX_LAUNCHES 3
+typedef struct bd_gemm_launch {
+    int family, row;                               /* row: index into the family's table (bd_gemm_instance) */
+    int key[BD_GEMM_KEY_LEN];
+    int grid, block;                               /* workgroups, threads per workgroup */
+    int row0, rows;
+    int split_k;
+} bd_gemm_launch;
+typedef struct bd_gemm_plan_t { int n_launches; bd_gemm_launch launch[BD_GEMM_PLAN_MAX_LAUNCHES]; } bd_gemm_plan_t;
+/* Writes the plan bd_gemm(args, prec) would execute on a device of `cus` compute units (<= 0: the current device's count; 256 without
+ * a device) while `concurrent_launches` launches of the same shape share it (<= 0: 1; the sub-batch lanes).  Returns BD_OK, or the
+ * BD_ERR_* code with which bd_gemm refuses these arguments (out->n_launches = 0 then). */
+int bd_gemm_plan(const bd_gemm_args* args /*[host]*/, int prec, int cus, int concurrent_launches, bd_gemm_plan_t* out /*[host]*/);
+/* Row `index` of a family's instance table: writes its key (BD_GEMM_KEY_LEN ints) and returns 1; returns 0 past the end of the
+ * table or for an unknown family.  The tables hold every instantiated GEMM kernel. */
+int bd_gemm_instance(int family, int index, int* key /*[host]*/);
+
 /* LayerNorm over the last dim (fp32 statistics), optional affine, fp32 input rows gathered by
  * in_row(r) = r if rpg_in == 0 else (r / rpg_in) * rpg_out + r % rpg_in + row_off.
  * Writes a 16-bit copy (next GEMM's A operand) and/or an fp32 copy.

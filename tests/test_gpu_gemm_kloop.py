@@ -32,9 +32,19 @@ def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
+LARGE, SMALL = (256, 192), (128, 192)        # workgroup tiles of the two forms (hip_ops.gemm_plan: "tile")
+
+
+def _stages(K):
+    """ring depth of a launch: three stages where the slab count is a multiple of three"""
+    return 3 if (K // 32) % 3 == 0 else 2
+
+
+@functools.lru_cache(maxsize=None)
 def _large_rows(N):
-    """rows at which the launcher takes the 256 x 192 form: more large tiles than half the CUs (gemm_f16c8.hip: `small`)"""
-    return 256 * (_cus() // 2 // (N // 192) + 1)
+    """the fewest whole 256-row tiles at which the plan of a three-stage launch on this device names the 256 x 192 form"""
+    return next(256 * j for j in range(1, 1 << 12)
+                if all(l["tile"] == LARGE for l in hip_ops.gemm_plan(hip_ops.gemm_shape_args(256 * j, N, 768), "f16c8")))
 
 
 @functools.lru_cache(maxsize=3)
@@ -86,13 +96,13 @@ def test_slab_counts_around_the_ring_period(hip, M, N, K):
         return
     ap, w16, b, e, ref = _case(HEAD, N, K)
     a = _head(ap, M)
-    out = hip_ops.gemm(a, w16, b, prec="f16c8", out_f32=True, w_qexp=e)
+    out = hip_ops.gemm(a, w16, b, prec="f16c8", out_f32=True, w_qexp=e, expect={"stages": _stages(K), "ep": 3})
     err = (out.double() - ref[:M]).abs().max().item()
     print(f"M {M} N {N} K {K}: max err {err:.3g} (bound {2e-5 * K ** 0.5:.3g})")
     assert err < 2e-5 * K ** 0.5, err
     res = _rand("kr", (HEAD, N))[:M]
     buf = res.clone()
-    hip_ops.gemm(a, w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e)
+    hip_ops.gemm(a, w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e, expect={"stages": _stages(K), "ep": 3})
     assert (buf.double() - (ref[:M] + res.double())).abs().max().item() < 2e-5 * K ** 0.5 + 1e-6
 
 
@@ -109,7 +119,9 @@ def test_stage_carried_to_a_workgroups_second_tile(hip, K):
         return
     M = 256 * -(-(_cus() + 8) // 4)
     (_, a16), w16, b, e, ref = _case(M, N, K)
-    out = hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, w_qexp=e)
+    tiles = (M // 256) * (N // 192)
+    out = hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, w_qexp=e, expect={"tile": LARGE, "stages": _stages(K), "grid": _cus()})
+    assert _cus() < tiles <= 2 * _cus()
     err = (out.double() - ref).abs().max().item()
     print(f"M {M} K {K}: max err {err:.3g} (bound {2e-5 * K ** 0.5:.3g})")
     assert err < 2e-5 * K ** 0.5, err
@@ -129,12 +141,14 @@ def test_large_form_rows_equal_the_small_form(hip, N, K, kind):
     ap, w16, b, e, ref = _case(big_rows, N, K, HEAD)
     a16 = ap[1]
     kw = {"act": _lib.ACT_GELU} if kind == "gelu_f32" else {}
-    big = hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, w_qexp=e, **kw)
+    ep = 0 if kind == "gelu_f32" else 3
+    big = hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, w_qexp=e, expect={"tile": LARGE, "stages": _stages(K), "ep": ep}, **kw)
     want = F.gelu(ref.float()).double() if kind == "gelu_f32" else ref
     tol = 2e-5 * K ** 0.5 * (1.13 if kind == "gelu_f32" else 1.0) + (1e-6 if kind == "gelu_f32" else 0.0)      # (|GELU'| <= 1.13)
     assert (big[:HEAD].double() - want).abs().max().item() < tol
     for rows in (256, 300):
-        small = hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, w_qexp=e, **kw)
+        form = SMALL if ep == 0 or _stages(K) == 3 else LARGE
+        small = hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, w_qexp=e, expect={"tile": form, "stages": _stages(K), "ep": ep}, **kw)
         _bits_equal(big, small, rows, N, (kind, N, K, rows))
 
 
@@ -164,8 +178,10 @@ def test_layernorm_fold_consumer_with_gelu(hip, K):
     rstd = torch.rsqrt(var[:HEAD] + eps)[:, None]
     pre = rstd * (ref - b.double()) - (mean[:HEAD, None] * rstd) * colsum.double() + b.double()
     g = F.gelu(pre.float())
-    big = hip_ops.gemm(a16, w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, ln_apply=(st, colsum, eps))
-    small = hip_ops.gemm(_head(ap, HEAD), w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, ln_apply=(st[:HEAD].contiguous(), colsum, eps))
+    form = {"stages": 3, "ep": 1, "gelu": True, "lnf": True}
+    big = hip_ops.gemm(a16, w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, ln_apply=(st, colsum, eps), expect={"tile": LARGE, **form})
+    small = hip_ops.gemm(_head(ap, HEAD), w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, ln_apply=(st[:HEAD].contiguous(), colsum, eps),
+                         expect={"tile": SMALL, **form})
     _bits_equal(big, small, HEAD, N, "fold consumer + GELU")
     oh, ol, oq = hip_ops.f16c8_decode(small)
     err = ((oh + ol) - g).abs().max().item()
@@ -184,8 +200,9 @@ def test_gelu_instance(hip, K):
     ap, w16, b, e, ref = _case(big_rows, N, K, HEAD)
     a16 = ap[1]
     g = F.gelu(ref.float())
-    big = hip_ops.gemm(a16, w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e)
-    small = hip_ops.gemm(_head(ap, HEAD), w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e)
+    form = {"stages": 3, "ep": 1, "gelu": True, "lnf": False}
+    big = hip_ops.gemm(a16, w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, expect={"tile": LARGE, **form})
+    small = hip_ops.gemm(_head(ap, HEAD), w16, b, prec="f16c8", act=_lib.ACT_GELU, w_qexp=e, expect={"tile": SMALL, **form})
     _bits_equal(big, small, HEAD, N, "GELU")
     oh, ol, oq = hip_ops.f16c8_decode(small)
     assert ((oh + ol) - g).abs().max().item() < 4e-4 * max(1.0, g.abs().max().item()) * 2.0 ** -4 + 2e-5
@@ -207,14 +224,15 @@ def test_layernorm_fold_producers(hip, ep, K):
         res = (rh + rl).float()
 
     def go(rows):
+        form = {"tile": LARGE if rows == big_rows else SMALL, "stages": 3, "ep": ep}
         st = torch.zeros((rows, 8, 2), dtype=torch.float32, device="cuda")
         buf = res[:rows].clone()
         if ep == 4:
             op = torch.zeros_like(hip_ops.f16c8_encode(res[:rows], 0, False))
-            hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e, ln_emit=(st, op))
+            hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e, ln_emit=(st, op), expect=form)
         else:
             op = hip_ops.f16c8_encode(res[:rows], 0, False)
-            hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, out=buf, w_qexp=e, ln_emit=(st, op), ln_resid_in_op=True)
+            hip_ops.gemm(_head(ap, rows), w16, b, prec="f16c8", out_f32=True, out=buf, w_qexp=e, ln_emit=(st, op), ln_resid_in_op=True, expect=form)
         return buf, op, st
 
     if K < 128:
@@ -253,7 +271,9 @@ def test_split_k_slab_ranges(hip, M, K, split):
     outs = []
     for _ in range(2):
         buf = res.clone()
-        hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e, split_k=(ws, split))
+        # a forced factor is the plan's factor, on 128 x 96 tiles; the factor the library picks is its own business
+        hip_ops.gemm(a16, w16, b, prec="f16c8", out_f32=True, out=buf, resid=buf, w_qexp=e, split_k=(ws, split),
+                     expect={"split_k": split, "tile": (128, 96), "ep": 3} if split else {"ep": 3})
         outs.append(buf)
     assert int(ws[:16384].view(torch.int32).abs().max()) == 0, "split-K flags must be left zero"
     assert torch.equal(outs[0], outs[1])

@@ -205,9 +205,33 @@ RPG = (256, 261, 5)
 SHAPE, ALIGN = -1, -3                                                # BD_ERR_SHAPE, BD_ERR_ALIGN
 
 
+def _cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
 def _needs_256_cus():
-    if torch.cuda.get_device_properties(0).multi_processor_count != 256:
-        pytest.skip("the form this shape reaches is derived for 256 CUs")
+    """for tables of shapes worked out by hand for 256 CUs (tests/test_gpu_range.py); the launches still assert their form through the plan"""
+    if _cus() != 256:
+        pytest.skip("the shapes of this table are worked out for 256 CUs")
+
+
+def _rows(prec, N, K, ok, prefer, **fields):
+    """The row count of a test that is about one launch form: `prefer` (the count worked out for 256 CUs) if this device's plan gives
+    it that form -- ok(hip_ops.gemm_plan(..)) -- else the nearest count with a ragged last tile (128 j + 44) whose plan does."""
+    if prec == "fp8":
+        fields["wscale"] = True
+    for M in [prefer] + sorted((128 * j + 44 for j in range(2, 600)), key=lambda m: abs(m - prefer)):
+        if ok(hip_ops.gemm_plan(hip_ops.gemm_shape_args(M, N, K, **fields), prec)):
+            return M
+    pytest.fail(f"no row count gives {prec} N {N} K {K} the form under test on {_cus()} CUs")
+
+
+def _is(plan, *launches):
+    """does a plan consist of these launches (one dict of hip_ops.gemm_plan's fields each)?"""
+    return len(plan) == len(launches) and all(all(l[k] == v for k, v in want.items()) for l, want in zip(plan, launches))
+
+
+PC, LARGE, SMALL = {"family": "pc", "tile": (256, 192)}, {"tile": (256, 192)}, {"tile": (128, 192)}      # gemm.hip's persistent kernel; F16C8's forms
 
 
 def _randn(shape, std=1.0, seed=3, mean=0.0):
@@ -242,8 +266,9 @@ def _same_bits(x, y, what):
 
 
 def _gemm(prec, A, W, out, M, N, K, kind, *, bias=None, wscale=None, resid=None, addtab=None, rpg=(0, 0, 0), act=0, w_qexp=0, rms=None,
-          ln_emit=None, ln_apply=None, resid_in_op=False, split_k=None, w_row0=0, out_col0=0, expect=None, edit=None):
-    """bd_gemm on arenas: every leading dimension, plane distance and base pointer comes from the arena, not from N / K / rows."""
+          ln_emit=None, ln_apply=None, resid_in_op=False, split_k=None, w_row0=0, out_col0=0, expect=None, edit=None, form=None):
+    """bd_gemm on arenas: every leading dimension, plane distance and base pointer comes from the arena, not from N / K / rows.
+    form: the kernel form the test is about -- bd_gemm_plan on these very arguments must name it (hip_ops._check_expect)."""
     g = _lib.GemmArgs()
     g.A, g.lda, g.a_plane = A.ptr, A.ld, A.plane
     g.W, g.ldw, g.w_plane = W.ptr + w_row0 * W.ld * _CLS[W.cls][1][0], W.ld, W.plane
@@ -268,6 +293,8 @@ def _gemm(prec, A, W, out, M, N, K, kind, *, bias=None, wscale=None, resid=None,
     if edit is not None:
         edit(g)
     lib = _lib.load()
+    if form is not None:
+        hip_ops._check_expect(g, prec, form)
     if (ln_emit is not None or ln_apply is not None) and expect is None:
         assert lib.bd_gemm_takes_ln_fold(C.byref(g), _lib.prec_id(prec)), "no kernel form with the LayerNorm-fold epilogues"
     rc = lib.bd_gemm(C.byref(g), _lib.prec_id(prec), _lib.stream())
@@ -322,7 +349,7 @@ def _rms_w():
     return (_randn((96,), 0.1, 21) + 1), (_randn((96,), 0.1, 22) + 1)
 
 
-def _run(P, kind, tol, *, act=0, resid=None, ldo=None, ldr=None, rms_parts=None, maptab=False, split=0):
+def _run(P, kind, tol, *, act=0, resid=None, ldo=None, ldr=None, rms_parts=None, maptab=False, split=0, form=None):
     """One Linear of problem P, contiguous and on arenas, checked as the module docstring says.  resid: None, "inplace" (resid == out) or
     "separate" (its own arena, ldr); maptab: the row map RPG + an added table (test_gemm_epilogues).  tol(|ref| max) -> bound."""
     prec, M, N, K = P.prec, P.M, P.N, P.K
@@ -353,7 +380,7 @@ def _run(P, kind, tol, *, act=0, resid=None, ldo=None, ldr=None, rms_parts=None,
         R = out if resid == "inplace" else (place(res, "f32", ldr if arena else None) if resid else None)
         ws = hip_ops.splitk_workspace(M, N) if split else None
         _gemm(prec, A, W, out, M, N, K, kind, bias=P.b, wscale=P.ws, resid=R, addtab=tab, rpg=RPG if maptab else (0, 0, 0), act=act,
-              w_qexp=P.e, rms=rms, split_k=(ws, split) if split else None)
+              w_qexp=P.e, rms=rms, split_k=(ws, split) if split else None, form=form)
         torch.cuda.synchronize()
         for name, ar in (("A", A), ("W", W), ("out", out), ("resid", R)):
             if ar is not None:
@@ -404,7 +431,7 @@ def test_one_tile_narrow_epilogue(hip, prec, kind):                             
     """M = 300, N = 204, K = 128: N % 8 != 0, so wide_epilogue_ok fails -- no persistent kernel (pc192_possible), and the one-tile kernel
     (launch_one_tile: 64 x 64 tiles, e64 wins at 5 x 4 tiles) stores through the scalar epilogue.  ldo = 212."""
     P = _Problem(prec, 300, 204, 128)
-    _run(P, kind, _tol_f32(prec, 128) if kind else _tol_16(prec, 128), ldo=212)
+    _run(P, kind, _tol_f32(prec, 128) if kind else _tol_16(prec, 128), ldo=212, form={"family": "glds", "tile": (64, 64)})
 
 
 @gpu
@@ -415,10 +442,10 @@ def test_one_tile_wide_epilogue(hip, prec, form):
     LDS-staged 16-byte epilogue of the one-tile kernel.  The residual of f32_resid lives in its own arena with ldr = 264 != ldo."""
     P = _Problem(prec, 300, 200, 128)
     if form == "gelu16":
-        _run(P, 0, _tol_16(prec, 128), act=1, ldo=232)
+        _run(P, 0, _tol_16(prec, 128), act=1, ldo=232, form={"family": "glds"})
     else:
         tol = (lambda m: 2e-4 * 128 ** 0.5) if prec == "fp8" else (lambda m: 3e-4)        # test_gemm_epilogues' residual form
-        _run(P, 1, tol, resid="inplace" if form == "f32_inplace" else "separate", ldo=232, ldr=264)
+        _run(P, 1, tol, resid="inplace" if form == "f32_inplace" else "separate", ldo=232, ldr=264, form={"family": "glds"})
 
 
 @gpu
@@ -434,45 +461,56 @@ def test_row_map_and_table_in_place(hip, prec):
 @gpu
 @pytest.mark.parametrize("prec,form", [(p, f) for p in LIN for f in ("plain", "rms", "alt_rms") if f != "alt_rms" or p not in ("bf16", "fp16")])
 def test_persistent_192_16bit_outputs(hip, prec, form):
-    """M = 4000, N = 2304, K = 768: uses_pc192 -- N % 192 == 0, M >= 1024, 16 x 12 = 192 tiles of 256 x 192 on 256 CUs = 0.75 of one round
-    (>= 0.45); pc192_main_rows keeps one launch (k = 0).  plain -> EP 1, fused q/k RMSNorm (8 heads x 96) -> EP 2; alt_rms: the
+    """N = 2304, K = 768 in ONE launch of the persistent 256 x 192 kernel (M = 4000 on 256 CUs: 16 x 12 = 192 tiles, 0.75 of one round).
+    plain -> EP 1, fused q/k RMSNorm (8 heads x 96) -> EP 2; alt_rms: the
     non-native 16-bit kind of the class (2 = f16 plane from the split classes, 3 = bf16 plane from e4m3; the plain classes have none).  ldo = 2336."""
-    _needs_256_cus()
     kind = 0 if form != "alt_rms" else (3 if prec == "fp8" else 2)
     eps = EPS[prec] if kind == 0 else (2.0 ** -8 if kind == 3 else 2.0 ** -11)
-    P = _Problem(prec, 4000, 2304, 768)
-    _run(P, kind, _tol_rms(eps) if form != "plain" else _tol_16(prec, 768, eps), rms_parts=0 if form == "plain" else 3)
+    want = {**PC, "ep": 1 if form == "plain" else 2, "outk": kind}
+    rms = {} if form == "plain" else {"rms_wq": True, "rms_wk": True, "rms_parts": 3}
+    M = _rows(prec, 2304, 768, lambda plan: _is(plan, want), 4000, out_f32=kind, **rms)
+    P = _Problem(prec, M, 2304, 768)
+    _run(P, kind, _tol_rms(eps) if form != "plain" else _tol_16(prec, 768, eps), rms_parts=0 if form == "plain" else 3, form=want)
 
 
 @gpu
 @pytest.mark.parametrize("prec", LIN)
 def test_persistent_192_narrow_output_in_place(hip, prec):
-    """N = 768, K = 768, fp32 + residual in place (EP 3).  uses_pc192 needs ceil(M / 256) * 4 tiles to fill 0.45 of their rounds on 256
-    CUs: 116 tiles, M > 7168 (M = 4000 is 64 tiles = 0.25 and goes to the one-tile kernels).  M = 7300: 29 x 4 = 116 tiles, one round,
-    pc192_main_rows k = 0 -> one launch, ragged last row tile.  ldo = ldr = 800."""
-    _needs_256_cus()
-    P = _Problem(prec, 7300, 768, 768)
-    _run(P, 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 768 ** 0.5, resid="inplace", ldo=800)       # test_gemm_block_sized, in place
+    """N = 768, K = 768, fp32 + residual in place (EP 3) in ONE launch of the persistent kernel with a ragged last row tile: on 256 CUs the
+    tiles must fill 0.45 of their rounds, M = 7300 is 29 x 4 = 116 tiles in one round (M = 4000 goes to the one-tile kernels).
+    ldo = ldr = 800."""
+    want = {**PC, "ep": 3}
+    M = _rows(prec, 768, 768, lambda plan: _is(plan, want), 7300, out_f32=1, resid=True)
+    assert M % 256
+    P = _Problem(prec, M, 768, 768)
+    _run(P, 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 768 ** 0.5, resid="inplace", ldo=800, form=want)       # test_gemm_block_sized, in place
 
 
 @gpu
 @pytest.mark.parametrize("form", ["tail_rows", "hybrid", "two_rounds_separate_resid"])
 @pytest.mark.parametrize("prec", LIN)
 def test_two_launch_forms(hip, prec, form):
-    """row_slice re-bases A, out and resid by row0 * lda / ldo / ldr.
-    tail_rows: M = 16500, N = 768, K = 128 -- 65 x 4 = 260 tiles = 0.51 of two rounds (uses_pc192); pc192_main_rows: k = 1, rem = 4 <= 64
-      -> 16384 rows on the persistent kernel + 116 rows on the one-tile kernels.  In place, lda = 160, ldo = ldr = 800.
-    hybrid: M = 16500, N = 1024, K = 2048 -- N % 192 != 0; launch_one_tile: N % 256 == 0, N < 1536, K >= 2048: one round of 256 x 256 tiles
-      (k256 = 1: 64 row tiles x 4 = 256 tiles, cost 1 + 0.36) beats 128 x 128 everywhere (1.51): 16384 + 116 rows.  In place, ldo = ldr = 1056.
-    two_rounds_separate_resid: M = 33000, N = 768, K = 128 -- 129 x 4 = 516 tiles, k = 2, rem = 4: 32768 rows = 512 tiles on 256 workgroups, so
-      every workgroup prefetches the residual of a NEXT tile; the residual has its own arena with ldr = 832 != ldo = 800."""
-    _needs_256_cus()
+    """Two launches over disjoint row ranges: the second one's A, out and resid are re-based by row0 * lda / ldo / ldr.  On 256 CUs:
+    tail_rows: M = 16500, N = 768, K = 128 -- 65 x 4 = 260 tiles, a second round of 4: 16384 rows on the persistent kernel + 116 rows on
+      the one-tile kernels.  In place, lda = 160, ldo = ldr = 800.
+    hybrid: M = 16500, N = 1024, K = 2048 -- no persistent kernel (N % 192 != 0); one round of 256 x 256 tiles (64 row tiles x 4) over
+      16384 rows + 128 x 128 tiles over 116 rows.  In place, ldo = ldr = 1056.
+    two_rounds_separate_resid: M = 33000, N = 768, K = 128 -- 32768 rows = two tiles for every workgroup of the persistent kernel, so
+      every workgroup prefetches the residual of a NEXT tile, + 232 rows; the residual has its own arena with ldr = 832 != ldo = 800."""
+    tail = lambda plan: _is(plan, {**PC, "ep": 3, "row0": 0}, {"family": "glds"}) and plan[1]["row0"] == plan[0]["rows"]
     if form == "tail_rows":
-        _run(_Problem(prec, 16500, 768, 128), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 128 ** 0.5, resid="inplace", ldo=800)
+        M = _rows(prec, 768, 128, tail, 16500, out_f32=1, resid=True)
+        _run(_Problem(prec, M, 768, 128), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 128 ** 0.5, resid="inplace", ldo=800,
+             form=[{**PC, "ep": 3}, {"family": "glds"}])
     elif form == "hybrid":
-        _run(_Problem(prec, 16500, 1024, 2048), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 2048 ** 0.5, resid="inplace", ldo=1056)
+        want = [{"family": "glds", "tile": (256, 256), "row0": 0}, {"family": "glds", "tile": (128, 128)}]
+        M = _rows(prec, 1024, 2048, lambda plan: _is(plan, *want) and plan[1]["row0"] == plan[0]["rows"], 16500, out_f32=1, resid=True)
+        _run(_Problem(prec, M, 1024, 2048), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 2048 ** 0.5, resid="inplace", ldo=1056, form=want)
     else:
-        _run(_Problem(prec, 33000, 768, 128), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 128 ** 0.5, resid="separate", ldo=800, ldr=832)
+        two = lambda plan: tail(plan) and plan[0]["rows"] // 256 * 4 == 2 * plan[0]["grid"]
+        M = _rows(prec, 768, 128, two, 33000, out_f32=1, resid=True)
+        _run(_Problem(prec, M, 768, 128), 1, lambda m: (4e-4 if prec == "bf16x3" else 2e-4) * 128 ** 0.5, resid="separate", ldo=800, ldr=832,
+             form=[{**PC, "ep": 3}, {"family": "glds"}])
 
 
 @gpu
@@ -537,10 +575,11 @@ def _fold_ref(acc, x, s, bias, eps):
 def test_f16c8_v_columns_of_a_split_qkv(hip, M, fold):
     """forward.hip's qk16_v_lin: ONE [3 D, K] weight encoded once; the launch takes W + 2 D rows with w_plane still the full weight's,
     bias + 2 D (ln_colsum + 2 D with the LayerNorm-fold consumer), N = D, out = qkv + 2 D columns with ldo = 3 D, an f16 plane (kind 2).
-    M = 1536: 6 x 4 = 24 large tiles, 2 x 24 <= 256 -> the small form; M = 8400: 33 x 4 = 132, 264 > 256 -> the large form.
+    M = 1536: the small form (on 256 CUs: 6 x 4 = 24 large tiles, 2 x 24 <= 256); M = 8400: the large form (33 x 4 = 132 tiles).
     The reference is columns [2 D, 3 D) of the full product; columns [0, 2 D) of qkv stay bytewise."""
-    _needs_256_cus()
     K, eps = 768, 1e-5
+    want = {**(SMALL if M == 1536 else LARGE), "ep": 1, "outk": 2, "lnf": fold}
+    M = _rows("f16c8", D, K, lambda plan: _is(plan, want), M, out_f32=2, **({"ln_stats_in": True, "ln_colsum": True} if fold else {}))
     P = _Problem("f16c8", M, 3 * D, K, seed=5, w_std=0.04, a_mean=0.4 if fold else 0.0, a_std=1.5 if fold else 1.0)
     wh, wl, _ = hip_ops.f16c8_decode(P.w_t, P.e, True)
     s = (wh.double() + wl.double()).sum(1).float().contiguous()
@@ -552,7 +591,7 @@ def test_f16c8_v_columns_of_a_split_qkv(hip, M, fold):
         A, W = P.A(arena), P.W(arena)
         out = place(first, "fp16", 3 * D if arena else None, poison="out")
         _gemm("f16c8", A, W, out, M, D, K, 2, bias=P.b[2 * D:], w_qexp=P.e, w_row0=2 * D, out_col0=2 * D,
-              ln_apply=(st, s[2 * D:], eps) if fold else None)
+              ln_apply=(st, s[2 * D:], eps) if fold else None, form=want)
         torch.cuda.synchronize()
         for ar in (A, W, out):
             untouched(ar)
@@ -587,7 +626,8 @@ def test_f16_qk_columns_on_plane_0_of_an_f16c8_operand(hip, fold):
         A = place(a_t, "f16c8", K + 32 if arena else None)
         W = place(w16, "fp16", K + 32 if arena else None)
         out = place(first, "fp16", 3 * D if arena else None, poison="out")
-        _gemm("fp16", A, W, out, M, 2 * D, K, 0, bias=b, rms=(wq, wk, 2), ln_apply=(st, s, eps) if fold else None)
+        _gemm("fp16", A, W, out, M, 2 * D, K, 0, bias=b, rms=(wq, wk, 2), ln_apply=(st, s, eps) if fold else None,
+              form={**PC, "ep": 2, "lnf": fold})
         torch.cuda.synchronize()
         for ar in (A, W, out):
             untouched(ar)
@@ -604,17 +644,17 @@ def test_f16_qk_columns_on_plane_0_of_an_f16c8_operand(hip, fold):
 @gpu
 @pytest.mark.parametrize("form", ["plain", "gelu", "split_bf16", "split_f16"])
 def test_f16c8_operand_class_outputs(hip, form):
-    """M = 300, N = 3072, K = 768, ldo = N + 32: 2 x 16 = 32 large tiles -> the small form, EP 1.  The operand-class output's lo8 plane is rows
+    """M = 300, N = 3072, K = 768, ldo = N + 32: EP 1 (2 x 16 = 32 large tiles: on 64 CUs or more the small form).  The operand-class output's lo8 plane is rows
     of ldo BYTES; kinds 4 / 5 (split-bf16 / split-f16 planes) with out_plane = (M + 64) ldo > M ldo (kind 5 takes the generic epilogue)."""
     P = _Problem("f16c8", 300, 3072, 768)
     K = 768
     if form in ("plain", "gelu"):
         # test_gemm_f16c8, operand-class output (hi + lo against the exact value)
-        _run(P, 0, lambda m: 4e-4 * m * 2.0 ** -4 + 2e-5, act=int(form == "gelu"))
+        _run(P, 0, lambda m: 4e-4 * m * 2.0 ** -4 + 2e-5, act=int(form == "gelu"), form={"ep": 1, "outk": 0, "gelu": form == "gelu", "stages": 3})
     elif form == "split_bf16":
-        _run(P, 4, lambda m: 2.0 ** -15 * m + 2e-5 * K ** 0.5)        # test_gemm_f16c8, kind 4
+        _run(P, 4, lambda m: 2.0 ** -15 * m + 2e-5 * K ** 0.5, form={"ep": 1, "outk": 4, "stages": 3})        # test_gemm_f16c8, kind 4
     else:
-        _run(P, 5, lambda m: 2.0 ** -20 * m + 2e-5 * K ** 0.5)        # test_gemm_f16c8, kind 5
+        _run(P, 5, lambda m: 2.0 ** -20 * m + 2e-5 * K ** 0.5, form={"ep": 0, "stages": 3})        # test_gemm_f16c8, kind 5
 
 
 @gpu
@@ -622,13 +662,21 @@ def test_f16c8_operand_class_outputs(hip, form):
                                             ("inplace", 300, 768, 2), ("inplace", 300, 768, 3), ("inplace", 300, 768, 4)])
 def test_f16c8_fp32_residual_forms(hip, form, M, K, split):
     """N = 768, fp32 + residual (EP 3), ldo = 800; in place (ldr = ldo) or the residual in its own arena with ldr = 832.
-    M = 4000: 16 x 4 = 64 tiles, 128 <= 256 -> small form.  M = 16500: 65 x 4 = 260 tiles on 256 workgroups -> large form, and the
-    first workgroups prefetch a NEXT tile's residual rows.  K = 3072, M = 1536: 24 tiles, small, K >= 2048, 4 x 24 <= 256 -> the
-    128 x 96 form (fc2_96).  M = 300 with a split-K workspace and a forced factor 2 / 3 / 4: compared with the contiguous launch of the
-    same factor."""
-    _needs_256_cus()
+    M = 4000: the small form (on 256 CUs: 16 x 4 = 64 tiles).  M = 16500: the large form with more tiles than workgroups (65 x 4 = 260 on
+    256), so the first workgroups prefetch a NEXT tile's residual rows.  K = 3072, M = 1536: the 128 x 96 form (24 large tiles, deep K).
+    M = 300 with a split-K workspace and a forced factor 2 / 3 / 4: compared with the contiguous launch of the same factor."""
+    if split:
+        want, ok = {"tile": (128, 96), "ep": 3, "split_k": split}, None
+    elif K == 3072:
+        want, ok = {"tile": (128, 96), "ep": 3, "split_k": 1}, None
+    elif M == 4000:
+        want, ok = {**SMALL, "ep": 3}, None
+    else:
+        want, ok = {**LARGE, "ep": 3}, lambda plan: _is(plan, want) and -(-plan[0]["rows"] // 256) * 4 > plan[0]["grid"]
+    if not split:
+        M = _rows("f16c8", 768, K, ok or (lambda plan: _is(plan, want)), M, out_f32=1, resid=True)
     P = _Problem("f16c8", M, 768, K, w_std=0.03)
-    _run(P, 1, lambda m: 2e-5 * K ** 0.5 + 1e-6, resid=form, ldo=800, ldr=832, split=split)           # test_gemm_f16c8, in-place residual
+    _run(P, 1, lambda m: 2e-5 * K ** 0.5 + 1e-6, resid=form, ldo=800, ldr=832, split=split, form=want)           # test_gemm_f16c8, in-place residual
 
 
 @gpu
@@ -656,7 +704,8 @@ def test_f16c8_layernorm_fold_producer(hip, ep, M):
         else:
             out = place(x0, "f32", 800 if arena else None, poison="out")
         st = torch.full((M, 8, 2), float("nan"), dtype=torch.float32, device="cuda")
-        _gemm("f16c8", A, W, out, M, N, K, int(f32), bias=P.b, w_qexp=P.e, resid=None if r5 else out, ln_emit=(st, op), resid_in_op=r5)
+        _gemm("f16c8", A, W, out, M, N, K, int(f32), bias=P.b, w_qexp=P.e, resid=None if r5 else out, ln_emit=(st, op), resid_in_op=r5,
+              form={"ep": 5 if r5 else 4, "outk": int(f32), "stages": 3})
         torch.cuda.synchronize()
         for name, ar in (("A", A), ("W", W), ("out", out), ("operand copy", op)):
             untouched(ar, name)
@@ -690,7 +739,7 @@ def test_f16c8_generic_epilogue(hip, K):
     """N = 200 (N % 192 != 0 -> EP 0), row map + table + in-place residual as in test_row_map_and_table_in_place, ldo = ldr = 232.
     K = 128: K / 32 = 4 slabs, not a multiple of 3 -> the two-stage ring; K = 192: 6 slabs -> the three-stage ring."""
     P = _Problem("f16c8", 512, 200, K, w_std=0.03)
-    _run(P, 1, lambda m: 2e-5 * K ** 0.5 + 1e-6, resid="inplace", ldo=232, maptab=True)               # test_gemm_f16c8, in-place residual
+    _run(P, 1, lambda m: 2e-5 * K ** 0.5 + 1e-6, resid="inplace", ldo=232, maptab=True, form={"ep": 0, "stages": 3 if K == 192 else 2})               # test_gemm_f16c8, in-place residual
 
 
 # ---- bd_layernorm

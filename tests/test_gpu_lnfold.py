@@ -37,13 +37,21 @@ def _emit(M, K, with_fold=True, resid=True, seed=3):
         st = torch.full((M, N // 96, 2), float("nan"), dtype=torch.float32, device="cuda")
         op = torch.zeros((2, M, N), dtype=torch.float16, device="cuda")
         kw["ln_emit"] = (st, op)
-    out = hip_ops.gemm(hip_ops.f16c8_encode(a, 0, False), hip_ops.f16c8_encode(w, e, True), b, **kw)
+    out = hip_ops.gemm(hip_ops.f16c8_encode(a, 0, False), hip_ops.f16c8_encode(w, e, True), b, expect={"ep": 4 if with_fold else 3, "stages": 3}, **kw)
     return out, st, op
+
+
+def _tiles(rows, K, N=768, **fields):
+    """the workgroup tile the plan of this device gives each row count: tests about form independence need more than one"""
+    return {r: hip_ops.gemm_plan(hip_ops.gemm_shape_args(r, N, K, **fields), "f16c8")[0]["tile"] for r in rows}
 
 
 @pytest.mark.parametrize("M,K", [(49152, 768), (1536, 768), (1000, 3072), (1536, 3072), (300, 768), (50112, 3072)])
 def test_producer_emits_operand_copy_and_row_statistics(hip, M, K):
-    """proj (K = 768) / fc2 (K = 3072) of both stacks, large / small / 128 x 96 forms, ragged last tiles."""
+    """proj (K = 768) / fc2 (K = 3072) of both stacks, ragged last tiles; over the cases the large, the small and the 128 x 96 form."""
+    cases = [(49152, 768), (1536, 768), (1000, 3072), (1536, 3072), (300, 768), (50112, 3072)]
+    emit = dict(out_f32=1, resid=True, ln_stats_out=True, ln_op_out=True)
+    assert {_tiles([m], k, **emit)[m] for m, k in cases} == {(256, 192), (128, 192), (128, 96)}
     plain, _, _ = _emit(M, K, with_fold=False)
     out, st, op = _emit(M, K)
     assert torch.equal(out, plain), "the fp32 rows must not change"
@@ -60,6 +68,8 @@ def test_producer_emits_operand_copy_and_row_statistics(hip, M, K):
 
 @pytest.mark.parametrize("K", [768, 3072])
 def test_producer_rows_do_not_depend_on_the_launch_form(hip, K):
+    tiles = _tiles((49152, 1536, 300, 4096), K, out_f32=1, resid=True, ln_stats_out=True, ln_op_out=True)
+    assert tiles[49152] == (256, 192) and set(tiles.values()) > {(256, 192)}, tiles
     big = _emit(49152, K)
     for rows in (1536, 300, 4096):
         a = _rand("a", (49152, K)).cuda()[:rows]
@@ -69,7 +79,7 @@ def test_producer_rows_do_not_depend_on_the_launch_form(hip, K):
         st = torch.zeros((rows, 8, 2), dtype=torch.float32, device="cuda")
         op = torch.zeros((2, rows, 768), dtype=torch.float16, device="cuda")
         out = hip_ops.gemm(hip_ops.f16c8_encode(a, 0, False), hip_ops.f16c8_encode(w, e, True), b, prec="f16c8", w_qexp=e, out_f32=True,
-                           resid=res.clone(), ln_emit=(st, op))
+                           resid=res.clone(), ln_emit=(st, op), expect={"ep": 4, "tile": tiles[rows]})
         assert torch.equal(out, big[0][:rows]) and torch.equal(st, big[1][:rows]), (K, rows)
         assert torch.equal(op[0], big[2][0][:rows]) and torch.equal(_lo8(op, rows, 768), _lo8(big[2], rows, 768)), (K, rows)
 
@@ -88,7 +98,8 @@ def test_producer_with_the_residual_in_the_operand_copy(hip, M, K):
         op = hip_ops.f16c8_encode(x0, 0, False)                          # the stream as the previous residual Linear left it
         st = torch.full((M, 8, 2), float("nan"), dtype=torch.float32, device="cuda")
         dummy = torch.zeros((2, M, N), dtype=torch.float16, device="cuda") if not f32 else None
-        out = hip_ops.gemm(a16, w16, b, prec="f16c8", w_qexp=e, out_f32=f32, out=dummy, ln_emit=(st, op), ln_resid_in_op=True)
+        out = hip_ops.gemm(a16, w16, b, prec="f16c8", w_qexp=e, out_f32=f32, out=dummy, ln_emit=(st, op), ln_resid_in_op=True,
+                           expect={"ep": 5, "outk": int(f32)})
         outs.append((out, st, op))
     (_, st0, op0), (o32, st1, op1) = outs
     assert torch.equal(op0[0], op1[0]) and torch.equal(_lo8(op0, M, N), _lo8(op1, M, N)) and torch.equal(st0, st1)
@@ -106,11 +117,14 @@ def test_producer_with_the_residual_in_the_operand_copy(hip, M, K):
     assert ((st1[..., 1].double() - m2).abs() / m2.clamp_min(1e-3)).max().item() <= 2e-5
     # form independence: the head rows of the large launch launched alone (small forms)
     if M == 49152:
+        tiles = _tiles((M, 1536, 300), K, ln_stats_out=True, ln_op_out=True, ln_resid_in_op=1)
+        assert tiles[M] == (256, 192) and tiles[300] != (256, 192), tiles
         for rws in (1536, 300):
             op = hip_ops.f16c8_encode(x0[:rws], 0, False)
             st = torch.zeros((rws, 8, 2), dtype=torch.float32, device="cuda")
             hip_ops.gemm(hip_ops.f16c8_encode(a[:rws], 0, False), w16, b, prec="f16c8", w_qexp=e, out_f32=False,
-                         out=torch.zeros((2, rws, N), dtype=torch.float16, device="cuda"), ln_emit=(st, op), ln_resid_in_op=True)
+                         out=torch.zeros((2, rws, N), dtype=torch.float16, device="cuda"), ln_emit=(st, op), ln_resid_in_op=True,
+                         expect={"ep": 5, "outk": 0, "tile": tiles[rws]})
             assert torch.equal(op[0], op0[0][:rws]) and torch.equal(_lo8(op, rws, N), _lo8(op0, rws, N)) and torch.equal(st, st0[:rws]), rws
 
 
@@ -163,7 +177,8 @@ def test_consumer_f16c8_applies_row_statistics(hip, kind, M):
         kw.update(out_mode=4)
     else:
         kw.update(out_mode=2, rms=rms)
-    out = hip_ops.gemm(a16, w16, bf, **kw)
+    want = {"gelu": (1, 0), "f16": (1, 2), "split_bf16": (1, 4), "rms_f16": (2, 2)}[kind]
+    out = hip_ops.gemm(a16, w16, bf, expect={"ep": want[0], "outk": want[1], "gelu": kind == "gelu", "lnf": True, "stages": 3}, **kw)
     # reference on a row sample (fp64 on the decoded planes)
     rows = torch.arange(0, M, max(1, M // 257), device="cuda")
     ah, al, aq = (t.double()[rows] for t in hip_ops.f16c8_decode(a16))
@@ -201,8 +216,12 @@ def test_consumer_rows_do_not_depend_on_the_launch_form(hip):
     s = wf.double().sum(1).float().contiguous()
     st = _stats_of(x)
 
+    tiles = _tiles((49152, 1536, 300), 768, 3072, act=1, ln_stats_in=True, ln_colsum=True)
+    assert tiles[49152] == (256, 192) and tiles[300] == (128, 192), tiles
+
     def go(rows):
-        return hip_ops.gemm(hip_ops.f16c8_encode(x[:rows], 0, False), w16, bf, prec="f16c8", w_qexp=e, act=1, ln_apply=(st[:rows].contiguous(), s, 1e-6))
+        return hip_ops.gemm(hip_ops.f16c8_encode(x[:rows], 0, False), w16, bf, prec="f16c8", w_qexp=e, act=1, ln_apply=(st[:rows].contiguous(), s, 1e-6),
+                            expect={"ep": 1, "gelu": True, "lnf": True, "tile": tiles[rows]})
     big = go(49152)
     for rows in (1536, 300):
         small = go(rows)
@@ -219,7 +238,8 @@ def test_consumer_f16_qk_launch(hip, M):
     s = w16.double().sum(1).float().contiguous()
     st = _stats_of(x)
     rms = ((_rand("wq", (96,), 0.1) + 1).cuda(), (_rand("wk", (96,), 0.1) + 1).cuda(), 1e-6, 2)
-    out = hip_ops.gemm(a16[0], w16, bf, prec="fp16", rms=rms, ln_apply=(st, s, eps))
+    pinned = {"family": "pc", "tile": (256, 192), "ep": 2, "lnf": True}
+    out = hip_ops.gemm(a16[0], w16, bf, prec="fp16", rms=rms, ln_apply=(st, s, eps), expect=pinned)
     rows = torch.arange(0, M, max(1, M // 257), device="cuda")
     acc = a16[0][rows].double() @ w16.double().t()
     mean, rstd = _ref_rows(x[rows], eps)
@@ -229,7 +249,7 @@ def test_consumer_f16_qk_launch(hip, M):
     err = (out[rows].double() - y).abs().max().item()
     assert err <= 2.0 ** -10 * float(y.abs().max()) + 1e-4, (M, err)
     # form independence: the launch is pinned to the persistent 256 x 192 kernel for every row count
-    head = hip_ops.gemm(a16[0][:300].contiguous(), w16, bf, prec="fp16", rms=rms, ln_apply=(st[:300].contiguous(), s, eps))
+    head = hip_ops.gemm(a16[0][:300].contiguous(), w16, bf, prec="fp16", rms=rms, ln_apply=(st[:300].contiguous(), s, eps), expect=pinned)
     assert torch.equal(head, out[:300])
 
 
@@ -295,7 +315,8 @@ def _splitk_case(M, K, kind, split, seed=11):
     if split is not None:
         ws = hip_ops.splitk_workspace(M, N)
         kw["split_k"] = (ws, split)
-    out = hip_ops.gemm(a16, w16, b, **kw)
+    ep = {"resid": 3, "emit": 4, "c8": 5, "c8f32": 5}[kind]
+    out = hip_ops.gemm(a16, w16, b, expect={"ep": ep, "tile": (128, 96), "split_k": split} if split else {"ep": ep, "split_k": 1}, **kw)
     torch.cuda.synchronize()
     return out, st, op, ws
 

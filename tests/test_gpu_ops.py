@@ -195,7 +195,8 @@ def test_qk_rmsnorm(hip, prec, hd, heads):
 def test_gemm_row_result_independent_of_tile_shape(hip, prec, N, K, kind):
     """A row's result must not depend on the kernel / tile shape that computed it: the first rows of a 49152-row launch
     (persistent 256x192 kernel, specialised epilogues) equal, bit for bit, the same rows launched alone at 1536 / 300 / 4096
-    rows (128x128, 64x64 and hybrid tiles, generic epilogue).  This is what makes a sample's output independent of its batch
+    rows (at 1536 and 300 the one-tile kernels, except where the fused q/k RMSNorm pins the persistent one; at 4096 whatever the device's
+    plan gives: the forms are asserted through hip_ops.gemm_plan).  This is what makes a sample's output independent of its batch
     (tests/test_gpu_path.py::test_full_size_properties); it pins the accumulator-start / bias / residual convention, the
     GELU arithmetic and the separate fp32 -> 16-bit rounding across every kernel."""
     M = 49152
@@ -215,7 +216,12 @@ def test_gemm_row_result_independent_of_tile_shape(hip, prec, N, K, kind):
             kw.update(out_f32=True)
         elif kind == "rms":
             kw.update(rms=((_rand("wq", (96,), 0.1) + 1).cuda(), (_rand("wk", (96,), 0.1) + 1).cuda(), 1e-6))
-        return hip_ops.gemm(aa, w16, b, prec=prec, **kw)
+        ep = {"plain": 1, "rms": 2, "gelu": 1, "resid": 3, "f32": 3}[kind]
+        if rows == M or kind == "rms":
+            form = {"family": "pc", "tile": (256, 192), "ep": ep}
+        else:
+            form = {"family": "glds"} if rows < 4096 else None
+        return hip_ops.gemm(aa, w16, b, prec=prec, expect=form, **kw)
 
     big = go(M)
     for rows in (1536, 300, 4096):
@@ -230,7 +236,8 @@ def test_gemm_f16c8_small_form_rows_equal_the_large_form(hip, N, K, kind):
     """The F16C8 class's persistent kernel has two forms (round 5): 256 x 192 tiles on 8 + 4 waves, and -- for launches whose large tiles would
     fill their rounds badly (one pose at a time: 1536 rows) -- 128 x 192 tiles on 4 + 4 waves, one consumer wave per SIMD.  Same wave tile, K
     order and epilogue arithmetic: the first rows of a 49152-row launch (large form) must equal, bit for bit, the same rows launched alone at
-    1536 / 300 / 4096 rows (small form; ragged last tile at 300), for every specialised epilogue of the path."""
+    1536 / 300 / 4096 rows (1536 and 300: the small form or, for deep K, the 128 x 96 one, ragged last tile at 300; 4096: the form of the
+    device's plan), for every specialised epilogue of the path.  The forms are asserted through hip_ops.gemm_plan."""
     M = 49152
     a, w, b = _rand("a", (M, K)).cuda(), _rand("w", (N, K), 0.05).cuda(), _rand("b", (N,), 0.5).cuda()
     e = hip_ops.f16c8_qexp(w)
@@ -252,7 +259,10 @@ def test_gemm_f16c8_small_form_rows_equal_the_large_form(hip, N, K, kind):
             kw.update(rms=rms)
         elif kind == "split_bf16":
             kw.update(out_mode=4)
-        return hip_ops.gemm(hip_ops.f16c8_encode(a[:rows], 0, False), w16, b, prec="f16c8", **kw)
+        ep = {"resid": 3, "f32": 3, "gelu": 1, "plain": 1, "rms_f16": 2, "rms_operand": 2, "split_bf16": 1}[kind]
+        tile = (256, 192) if rows == M else ((128, 96) if kind == "resid" and K == 3072 else (128, 192))
+        form = {"ep": ep, "stages": 3, **({"tile": tile} if rows != 4096 else {})}
+        return hip_ops.gemm(hip_ops.f16c8_encode(a[:rows], 0, False), w16, b, prec="f16c8", expect=form, **kw)
 
     big = go(M)
     for rows in (1536, 300, 4096):

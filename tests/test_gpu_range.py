@@ -123,26 +123,30 @@ def _check_bias_only(prec, M, N, K, modes, *, aligned=True, cols=None, **kw):
 
 
 # ------------------------------------------------------------------------------------------------------------------ part 2: GEMM epilogues
-# The one-tile kernels of gemm.hip (gemm_kernel_glds), by the dispatch of launch_one_tile on 256 CUs.  name -> (M, N, K, aligned bias, modes).
-# K = 64 (one slab; 128 for e4m3) except where K >= 2048 selects the form.
+# The one-tile kernels of gemm.hip (gemm_kernel_glds) on 256 CUs.  name -> (M, N, K, aligned bias, modes, the form hip_ops.gemm_plan must
+# name: asserted in front of every launch).  K = 64 (one slab; 128 for e4m3) except where K >= 2048 selects the form.
+def _glds(tm, tn, stages=2, **kw):
+    return {"family": "glds", "tile": (tm, tn), "stages": stages, **kw}
+
+
 GLDS = {
-    # gemm.hip:833  e128 >= e64 (12 tiles of 128 against 36 of 64), t128 <= CUs: launch_glds<.., 2, 2, 2, 2, 4>; wide epilogue (gemm.hip:177)
-    "128x128_ring4": (192, 768, 64, True, MODES),
-    # gemm.hip:836  24 tiles of 64 x 64 against 6 of 128 x 128: e64 > e128, t64 <= 2 CUs: launch_glds<.., 2, 2, 1, 1, 4>
-    "64x64_ring4": (128, 768, 64, True, MODES),
-    # gemm.hip:837  t64 = 576 > 2 CUs: launch_glds<.., 2, 2, 1, 1>; 48 tiles of 256 x 192 fill 0.19 of a round < 0.45 (gemm.hip:718)
-    "64x64": (3072, 768, 64, True, MODES),
-    # gemm.hip:834  t128 = 288 > CUs, e128 = 0.49 > e64 = 0.31: launch_glds<.., 2, 2, 2, 2>; 96 tiles of 256 x 192: 0.375 < 0.45
-    "128x128": (6144, 768, 64, True, MODES),
-    # gemm.hip:827  N >= 1536 and 256 tiles = one whole round: launch_glds<.., 2, 4, 4, 2>; N % 192 != 0 keeps the persistent kernel out
-    "256x256": (8192, 2048, 64, True, MODES),
-    # gemm.hip:819-825  hybrid row split (N % 256 == 0, N < 1536, K >= 2048): 256 x 256 tiles on 32768 rows, 128 x 128 on the last 128
-    "hybrid": (32896, 512, 2048, True, (0, 1)),
-    # gemm.hip:179  the scalar epilogue gemm_epilogue (operand class / fp32 only): bias 4 bytes off a 16-byte boundary, 128 x 128 ring form
-    "narrow_128x128": (192, 768, 64, False, (0, 1)),
-    # gemm.hip:815  256 x 192 one-tile form (one-plane classes, K >= 2048, e192 = 0.93 > e128 = 0.65); reachable only where the persistent
-    # kernel is not (pc192_possible, gemm.hip:703), i.e. with the scalar epilogue; the two-plane classes take 128 x 128 tiles here
-    "narrow_256x192": (16384, 768, 2048, False, (0, 1)),
+    # 12 tiles of 128 x 128 beat 36 of 64 x 64 and fit the CUs at once: the four-stage ring; wide epilogue
+    "128x128_ring4": (192, 768, 64, True, MODES, _glds(128, 128, 4)),
+    # 24 tiles of 64 x 64 beat 6 of 128 x 128 and fit the slots at once
+    "64x64_ring4": (128, 768, 64, True, MODES, _glds(64, 64, 4)),
+    # 576 tiles of 64 x 64: more than the slots; 48 tiles of 256 x 192 fill too little of a round for the persistent kernel
+    "64x64": (3072, 768, 64, True, MODES, _glds(64, 64)),
+    # 288 tiles of 128 x 128: more than the CUs, better than 64 x 64; 96 tiles of 256 x 192: still no persistent kernel
+    "128x128": (6144, 768, 64, True, MODES, _glds(128, 128)),
+    # N >= 1536 and 256 tiles = one whole round; N % 192 != 0 keeps the persistent kernel out
+    "256x256": (8192, 2048, 64, True, MODES, _glds(256, 256)),
+    # hybrid row split (N % 256 == 0, N < 1536, K >= 2048): 256 x 256 tiles on 32768 rows, 128 x 128 on the last 128
+    "hybrid": (32896, 512, 2048, True, (0, 1), [_glds(256, 256, rows=32768), _glds(128, 128, row0=32768, rows=128)]),
+    # the scalar epilogue gemm_epilogue (operand class / fp32 only): bias 4 bytes off a 16-byte boundary, 128 x 128 ring form
+    "narrow_128x128": (192, 768, 64, False, (0, 1), _glds(128, 128, 4)),
+    # 256 x 192 one-tile form (one-plane classes, K >= 2048); reachable only where the persistent kernel is not, i.e. with the scalar
+    # epilogue; the two-plane classes take 128 x 128 tiles here
+    "narrow_256x192": (16384, 768, 2048, False, (0, 1), _glds(256, 192)),
 }
 
 
@@ -150,64 +154,80 @@ GLDS = {
 @pytest.mark.parametrize("prec", LIN)
 def test_gemm_one_tile_stores_the_table_bit_for_bit(hip, prec, form):
     _needs_256_cus()
-    M, N, K, aligned, modes = GLDS[form]
+    M, N, K, aligned, modes, want = GLDS[form]
     if prec == "fp8":
         K = max(K, 128)
         if not aligned:
             modes = (1,)                                    # e4m3 results exist only in the wide epilogue (bd_gemm: needs_wide)
-    _check_bias_only(prec, M, N, K, modes, aligned=aligned)
+    if form == "narrow_256x192" and prec in ("bf16x3", "f16x3"):
+        want = _glds(128, 128)
+    _check_bias_only(prec, M, N, K, modes, aligned=aligned, form=want)
 
 
 def _rms():
     return (_randn((96,), 0.1, seed=21) + 1).contiguous(), (_randn((96,), 0.1, seed=22) + 1).contiguous(), 0
 
 
-# The persistent 256 x 192 kernel (gemm_kernel_pc, launch_pc).  M = 7424: 29 x 4 = 116 tiles fill 0.453 >= 0.45 of a round (gemm.hip:718).
-#   mode 0 -> pc_epilogue EP 1 (gemm.hip:679; the one-plane 16-bit classes: the paired-row store of gemm_common.h:671-714), mode 1 -> EP 3
-#   (gemm.hip:673-674), the class's one non-native kind (f16 from the split classes, bf16 from e4m3, split-bf16 from split-f16) -> EP 1
-#   with store8 of gemm_common.h:718; every other mode -> EP 0 = gemm_epilogue_lds<.., LEAN> (gemm.hip:680, 610).
-# "rms": the fused q/k RMSNorm geometry pins this kernel at any M (gemm.hip:708): EP 2 (gemm.hip:675-676) or, for the other kinds, the
-#   LEAN generic epilogue's rms branch (gemm_common.h:292-336); the v third of the columns is stored untouched and carries the table.
+# The persistent 256 x 192 kernel (gemm_kernel_pc).  M = 7424: 29 x 4 = 116 tiles fill 0.453 >= 0.45 of a round of 256 CUs.
+#   mode 0 -> pc_epilogue EP 1 (the one-plane 16-bit classes: the paired-row store), mode 1 -> EP 3, the class's non-native kinds (f16 from
+#   the split classes, bf16 from e4m3, split-bf16 from split-f16) -> EP 1 with store8; every other mode -> EP 0 = gemm_epilogue_lds<.., LEAN>.
+# "rms": the fused q/k RMSNorm geometry pins this kernel at any M: EP 2 or, for the other kinds, the LEAN generic epilogue's rms branch;
+#   the v third of the columns is stored untouched and carries the table.
+_PC_KINDS = {"bf16": (0,), "fp16": (0,), "bf16x3": (0, 2), "f16x3": (0, 2, 4), "fp8": (0, 3)}       # 16-bit kinds with an EP 1 / EP 2 instance
+
+
+def _pc_form(prec, mode, rms):
+    ep = 3 if mode == 1 and not rms else ((2 if rms else 1) if mode in _PC_KINDS[prec] else 0)
+    return {"family": "pc", "tile": (256, 192), "ep": ep}
+
+
 @pytest.mark.parametrize("form", ["plain", "rms"])
 @pytest.mark.parametrize("prec", LIN)
 def test_gemm_persistent_192_stores_the_table_bit_for_bit(hip, prec, form):
     _needs_256_cus()
     K = 128 if prec == "fp8" else 64
-    if form == "plain":
-        _check_bias_only(prec, 7424, 768, K, MODES)
-    else:
-        _check_bias_only(prec, 300, 2304, K, (0, 2, 3, 4, 5), rms=_rms(), cols=(1536, 2304))
+    for mode in (MODES if form == "plain" else (0, 2, 3, 4, 5)):
+        if form == "plain":
+            _check_bias_only(prec, 7424, 768, K, (mode,), form=_pc_form(prec, mode, False))
+        else:
+            _check_bias_only(prec, 300, 2304, K, (mode,), rms=_rms(), cols=(1536, 2304), form=_pc_form(prec, mode, True))
 
 
-# gemm_kernel_pc_f16c8 by the dispatch of bd_launch_gemm_f16c8 on 256 CUs.  name -> (M, N, K, modes).  Modes 0, 2, 4 take pc_epilogue EP 1
-# (gemm_f16c8.hip:555-557), 1 EP 3 (:550), 3 and 5 the generic epilogue (gemm_f16c8.hip:381, dispatch :560-563).
+# gemm_kernel_pc_f16c8 on 256 CUs.  name -> (M, N, K, modes, tile, ring stages).  Where K >= 128, modes 0, 2, 4 take pc_epilogue EP 1, 1 EP 3,
+# 3 and 5 the generic epilogue (EP 0); the form is asserted in front of every launch.
 C8 = {
-    # gemm_f16c8.hip:507  4 x 33 = 132 large tiles: 2 x 132 > CUs -> the large form, three-stage ring (K / 32 = 6)
-    "large": (8448, 768, 192, MODES),
-    # gemm_f16c8.hip:506  2 x 4 = 8 tiles, 16 <= CUs -> the small form (128 x 192 tiles)
-    "small": (300, 768, 192, MODES),
-    # gemm_f16c8.hip:549  the 128 x 96 form: fp32 results, small, K >= 2048 (K / 32 = 66, a multiple of 3), 4 x 8 <= CUs
-    "128x96": (300, 768, 2112, (1,)),
-    # gemm_f16c8.hip:561  K < 128: generic epilogue for every kind, two-stage ring (K / 32 = 2), small form
-    "generic_small_2stage": (300, 768, 64, MODES),
-    # gemm_f16c8.hip:563  K < 128: generic epilogue, two-stage ring, large form (the three-stage generic forms, :560 and :562, are what
-    # kinds 3 and 5 of "small" and "large" above take)
-    "generic_large_2stage": (8448, 768, 64, MODES),
+    # 4 x 33 = 132 large tiles: 2 x 132 > CUs -> the large form, three-stage ring (K / 32 = 6)
+    "large": (8448, 768, 192, MODES, (256, 192), 3),
+    # 2 x 4 = 8 tiles, 16 <= CUs -> the small form (128 x 192 tiles)
+    "small": (300, 768, 192, MODES, (128, 192), 3),
+    # the 128 x 96 form: fp32 results, small, K >= 2048 (K / 32 = 66, a multiple of 3), 4 x 8 <= CUs
+    "128x96": (300, 768, 2112, (1,), (128, 96), 3),
+    # K < 128: generic epilogue for every kind, two-stage ring (K / 32 = 2), small form
+    "generic_small_2stage": (300, 768, 64, MODES, (128, 192), 2),
+    # K < 128: generic epilogue, two-stage ring, large form (the three-stage generic forms are what kinds 3 and 5 of "small" and "large"
+    # above take)
+    "generic_large_2stage": (8448, 768, 64, MODES, (256, 192), 2),
 }
+
+
+def _c8_ep(mode, K):
+    return 0 if K < 128 or mode in (3, 5) else (3 if mode == 1 else 1)
 
 
 @pytest.mark.parametrize("form", sorted(C8))
 def test_gemm_f16c8_stores_the_table_bit_for_bit(hip, form):
     _needs_256_cus()
-    M, N, K, modes = C8[form]
-    _check_bias_only("f16c8", M, N, K, modes)
+    M, N, K, modes, tile, stages = C8[form]
+    for mode in modes:
+        _check_bias_only("f16c8", M, N, K, (mode,), form={"tile": tile, "stages": stages, "ep": _c8_ep(mode, K)})
 
 
 @pytest.mark.parametrize("M", [300, 8448])
 def test_gemm_f16c8_fused_rms_keeps_the_v_columns(hip, M):
-    """EP 2 of both forms (gemm_f16c8.hip:551-553): operand class, f16 plane, split-bf16 planes; the v third carries the table."""
+    """EP 2 of both forms: operand class, f16 plane, split-bf16 planes; the v third carries the table."""
     _needs_256_cus()
-    _check_bias_only("f16c8", M, 2304, 192, (0, 2, 4), rms=_rms(), cols=(1536, 2304))
+    _check_bias_only("f16c8", M, 2304, 192, (0, 2, 4), rms=_rms(), cols=(1536, 2304),
+                     form={"tile": (128, 192) if M == 300 else (256, 192), "stages": 3, "ep": 2})
 
 
 def _any_stats(M):
@@ -221,17 +241,18 @@ def _any_stats(M):
 @pytest.mark.parametrize("M", [300, 8448])
 def test_gemm_layernorm_fold_consumer_stores_the_table(hip, kind, M):
     """The consumer side of the LayerNorm fold (K = 768) with ln_colsum = 0: the value in front of the store is bias[n] exactly.
-    F16C8: EP 1 with LNF (gemm_f16c8.hip:545-546; the GELU form :544 is in the GELU sweep below), EP 2 with LNF (:547), small and large forms
-    (BD_C8_LAUNCH_LN).  f16: the q / k / v launch of gemm.hip:669-671 (persistent kernel, EP 2 with LNF)."""
+    F16C8: EP 1 with LNF (the GELU form is in the GELU sweep below), EP 2 with LNF, small and large forms.  f16: the q / k / v launch
+    (persistent kernel, EP 2 with LNF)."""
     _needs_256_cus()
     N = 2304
     ln = (_any_stats(M), torch.zeros(N, device="cuda"), 1e-6)
+    c8 = {"tile": (128, 192) if M == 300 else (256, 192), "stages": 3, "lnf": True}
     if kind == "gemm_f16c8_operand_f16_bf16x2":
-        _check_bias_only("f16c8", M, 768, 768, (2, 4), ln_apply=(ln[0], torch.zeros(768, device="cuda"), 1e-6))
+        _check_bias_only("f16c8", M, 768, 768, (2, 4), ln_apply=(ln[0], torch.zeros(768, device="cuda"), 1e-6), form={**c8, "ep": 1})
     elif kind == "gemm_f16c8_rms_f16":
-        _check_bias_only("f16c8", M, N, 768, (2,), rms=_rms(), ln_apply=ln, cols=(1536, 2304))
+        _check_bias_only("f16c8", M, N, 768, (2,), rms=_rms(), ln_apply=ln, cols=(1536, 2304), form={**c8, "ep": 2})
     else:
-        _check_bias_only("fp16", M, N, 768, (0,), rms=_rms(), ln_apply=ln, cols=(1536, 2304))
+        _check_bias_only("fp16", M, N, 768, (0,), rms=_rms(), ln_apply=ln, cols=(1536, 2304), form={"family": "pc", "tile": (256, 192), "ep": 2, "lnf": True})
 
 
 # ---- the value split over two of bias / addtab / resid, different in every row, through the row map
@@ -257,14 +278,14 @@ def _per_row_case(cls, M, N, combo):
     return (c, other, None, pre) if combo == "bias+tab" else (c, None, other, pre)
 
 
-# name -> (prec list, M, N, K, row map (rows per group in, out, offset)): launches with a table / row map take the generic epilogue
-# everywhere (pc_epilogue_kind, gemm.hip:633; f16c8_epilogue_kind, gemm_f16c8.hip:411): gemm_common.h:356-365 adds, :355 maps the row
+# name -> (prec list, M, N, K, row map (rows per group in, out, offset), form): launches with a table / row map take the generic epilogue
+# everywhere (EP 0 of the persistent kernels: gemm_epilogue_lds LEAN)
 PER_ROW = {
-    "glds_128x128_ring4": (LIN, 192, 768, 64, (64, 70, 3)),              # gemm.hip:833
-    "glds_64x64_ring4": (LIN, 128, 768, 64, (32, 33, 1)),                # gemm.hip:836
-    "persistent_192_generic": (LIN, 7424, 768, 64, (256, 261, 5)),       # gemm.hip:680 (EP 0 of gemm_kernel_pc: gemm_epilogue_lds LEAN)
-    "f16c8_small_generic": (["f16c8"], 300, 768, 192, (50, 57, 2)),      # gemm_f16c8.hip:560
-    "f16c8_large_generic": (["f16c8"], 8448, 768, 192, (256, 261, 5)),   # gemm_f16c8.hip:562
+    "glds_128x128_ring4": (LIN, 192, 768, 64, (64, 70, 3), _glds(128, 128, 4)),
+    "glds_64x64_ring4": (LIN, 128, 768, 64, (32, 33, 1), _glds(64, 64, 4)),
+    "persistent_192_generic": (LIN, 7424, 768, 64, (256, 261, 5), {"family": "pc", "tile": (256, 192), "ep": 0}),
+    "f16c8_small_generic": (["f16c8"], 300, 768, 192, (50, 57, 2), {"tile": (128, 192), "stages": 3, "ep": 0}),
+    "f16c8_large_generic": (["f16c8"], 8448, 768, 192, (256, 261, 5), {"tile": (256, 192), "stages": 3, "ep": 0}),
 }
 
 
@@ -272,7 +293,7 @@ PER_ROW = {
 @pytest.mark.parametrize("form,prec", [(f, p) for f in sorted(PER_ROW) for p in PER_ROW[f][0]])
 def test_gemm_per_row_values_through_table_residual_and_row_map(hip, prec, form, combo):
     _needs_256_cus()
-    _, M, N, K, rpg = PER_ROW[form]
+    _, M, N, K, rpg, want = PER_ROW[form]
     if prec == "fp8":
         K = 128
     rows = torch.arange(M)
@@ -290,7 +311,7 @@ def test_gemm_per_row_values_through_table_residual_and_row_map(hip, prec, form,
             full = torch.zeros(out_rows, N)
             full[orow] = res
             kw["resid"] = _Flat(full.cuda(), "f32")
-        got, _ = _launch(prec, M, N, K, mode, bias=bias.cuda() if bias is not None else None, out_rows=out_rows, rpg=rpg, **kw)
+        got, _ = _launch(prec, M, N, K, mode, bias=bias.cuda() if bias is not None else None, out_rows=out_rows, rpg=rpg, form=want, **kw)
         fill = blank(cls, out_rows, N, "cuda")
         for p, (g, w, f) in enumerate(zip(_planes(got, cls), _expect(pre, cls), _planes(fill, cls))):
             g, f = g.cpu(), f.cpu()
@@ -299,10 +320,10 @@ def test_gemm_per_row_values_through_table_residual_and_row_map(hip, prec, form,
 
 
 # ---- F16C8: the LayerNorm-fold producer, the 3-byte residual, split-K
-C8_PRODUCER = {"small": (300, 192), "large": (8448, 192), "128x96": (300, 2112)}      # gemm_f16c8.hip:543 (BD_C8_LAUNCH_LN small / large), :541-542
+C8_PRODUCER = {"small": (300, 192, (128, 192)), "large": (8448, 192, (256, 192)), "128x96": (300, 2112, (128, 96))}      # M, K, tile
 
 
-def _producer(M, K, *, r5, f32, split=None):
+def _producer(M, K, *, r5, f32, split=None, tile=None):
     """One producer launch with a zero accumulator.  r5: the residual is the F16C8 copy at ln_op_out (EP 5), else none (EP 4).
     Returns (fp32 rows or None, operand copy, statistics, pre)."""
     N = 768
@@ -322,7 +343,8 @@ def _producer(M, K, *, r5, f32, split=None):
     kw = {}
     if split:
         kw["split_k"] = (hip_ops.splitk_workspace(M, N), split)
-    _gemm("f16c8", _zero_a("f16c8", M, K), W, out, M, N, K, int(f32), bias=table.cuda(), w_qexp=e, ln_emit=(st, op), resid_in_op=r5, **kw)
+    form = {"ep": 5 if r5 else 4, "outk": int(f32), "split_k": split or 1, "tile": (128, 96) if split else tile}
+    _gemm("f16c8", _zero_a("f16c8", M, K), W, out, M, N, K, int(f32), bias=table.cuda(), w_qexp=e, ln_emit=(st, op), resid_in_op=r5, form=form, **kw)
     torch.cuda.synchronize()
     untouched(out, "fp32 rows")
     untouched(op, "operand copy")
@@ -348,26 +370,26 @@ def _check_producer(o32, opc, st, pre, what):
 @pytest.mark.parametrize("form", sorted(C8_PRODUCER))
 @pytest.mark.parametrize("ep", ["4", "5", "5_f32"])
 def test_gemm_f16c8_producer_copy_is_the_packing_of_the_table(hip, form, ep):
-    """pc_epilogue EP 4 (fp32 rows + the operand copy at ln_op_out, gemm_common.h:512-571) and EP 5 (ln_resid_in_op, gemm_common.h:581-670)
-    with out_f32 0 and 1, in the three kernel forms."""
+    """pc_epilogue EP 4 (fp32 rows + the operand copy at ln_op_out) and EP 5 (ln_resid_in_op) with out_f32 0 and 1, in the three kernel
+    forms."""
     _needs_256_cus()
-    M, K = C8_PRODUCER[form]
-    _check_producer(*_producer(M, K, r5=ep != "4", f32=ep != "5"), f"EP {ep} {form}")
+    M, K, tile = C8_PRODUCER[form]
+    _check_producer(*_producer(M, K, r5=ep != "4", f32=ep != "5", tile=tile), f"EP {ep} {form}")
 
 
 @pytest.mark.parametrize("split", [2, 3, 4])
 @pytest.mark.parametrize("ep", ["3", "4", "5", "5_f32"])
 def test_gemm_f16c8_split_k_of_a_zero_accumulator_is_bit_identical(hip, ep, split):
-    """Split-K (gemm_f16c8.hip:522-534) sums partial accumulators in a fixed order; all of them are zero here, so the stores must see the very
+    """Split-K sums partial accumulators in a fixed order; all of them are zero here, so the stores must see the very
     same values as the unsplit launch."""
-    _needs_256_cus()
-    M, K, N = 300, 192, 768
+    M, K, N = 300, 192, 768               # (a forced factor: the form does not depend on the device)
     if ep == "3":
         ws = hip_ops.splitk_workspace(M, N)
         W, e = _weights("f16c8", N, K)
         table = steered_table("f16c8", N)
         out = place(blank("f32", M, N, "cuda"), "f32", N + 32, poison="out")
-        _gemm("f16c8", _zero_a("f16c8", M, K), W, out, M, N, K, 1, bias=table.cuda(), w_qexp=e, split_k=(ws, split))
+        _gemm("f16c8", _zero_a("f16c8", M, K), W, out, M, N, K, 1, bias=table.cuda(), w_qexp=e, split_k=(ws, split),
+              form={"tile": (128, 96), "ep": 3, "split_k": split})
         torch.cuda.synchronize()
         untouched(out)
         assert torch.equal(lift(out).cpu(), (0.0 + table[None, :]).expand(M, N))
@@ -446,27 +468,29 @@ def _value_of(t, cls):
     return (t.double() if len(_CLS[cls][1]) == 1 else t[0].double() + t[1].double()).cpu()
 
 
-# name -> (classes, M, K, aligned, mode -> GELU form or None for "the class's own").  N = 4224 = 22 x 192 everywhere.
+# name -> (classes, M, K, aligned, mode -> GELU form or None for "the class's own", mode -> kernel form).  N = 4224 = 22 x 192 everywhere.
+_C8S, _C8L = {"tile": (128, 192), "stages": 3}, {"tile": (256, 192), "stages": 3}
 GELU_LAUNCHES = {
-    # gemm.hip:833, wide epilogue: 16/8-bit results take gelu_n<GeluKind<T, NS>> (gemm_common.h:353), fp32 results gelu_erf (:265)
-    "glds_wide": (LIN, 192, 64, True, {0: None, 1: "erf"}),
-    # gemm.hip:179, scalar epilogue: gelu_erf for every result (gemm_common.h:159)
-    "glds_narrow": (["bf16", "fp16", "bf16x3", "f16x3"], 192, 64, False, {0: "erf", 1: "erf"}),
-    # gemm.hip:677, persistent kernel EP 1 with GELU (gemm_common.h:686 paired-row store; :758 for the two-plane classes and e4m3);
-    # fp32 + GELU takes its generic epilogue (pc_epilogue_kind: gemm.hip:636)
-    "persistent_192": (LIN, 7424, 64, True, {0: None, 1: "erf"}),
-    # gemm_f16c8.hip:554 EP 1 with GELU, small and large forms; kinds 1 and 5 with GELU take the generic epilogue (gemm_f16c8.hip:412, 415)
-    "f16c8_small": (["f16c8"], 300, 192, True, {0: "erf", 1: "erf", 5: "erf"}),
-    "f16c8_large": (["f16c8"], 8448, 192, True, {0: "erf"}),
-    # gemm_f16c8.hip:561: K < 128, generic epilogue
-    "f16c8_generic": (["f16c8"], 300, 64, True, {0: "erf"}),
+    # wide epilogue of the one-tile kernels: 16/8-bit results take gelu_n<GeluKind<T, NS>>, fp32 results gelu_erf
+    "glds_wide": (LIN, 192, 64, True, {0: None, 1: "erf"}, {0: {"family": "glds"}, 1: {"family": "glds"}}),
+    # scalar epilogue: gelu_erf for every result
+    "glds_narrow": (["bf16", "fp16", "bf16x3", "f16x3"], 192, 64, False, {0: "erf", 1: "erf"}, {0: {"family": "glds"}, 1: {"family": "glds"}}),
+    # persistent kernel EP 1 with GELU (paired-row store; store8 for the two-plane classes and e4m3); fp32 + GELU takes its generic epilogue
+    "persistent_192": (LIN, 7424, 64, True, {0: None, 1: "erf"},
+                       {0: {"family": "pc", "ep": 1, "gelu": True}, 1: {"family": "pc", "ep": 0}}),
+    # EP 1 with GELU, small and large forms; kinds 1 and 5 with GELU take the generic epilogue
+    "f16c8_small": (["f16c8"], 300, 192, True, {0: "erf", 1: "erf", 5: "erf"},
+                    {0: {**_C8S, "ep": 1, "gelu": True}, 1: {**_C8S, "ep": 0}, 5: {**_C8S, "ep": 0}}),
+    "f16c8_large": (["f16c8"], 8448, 192, True, {0: "erf"}, {0: {**_C8L, "ep": 1, "gelu": True}}),
+    # K < 128, generic epilogue
+    "f16c8_generic": (["f16c8"], 300, 64, True, {0: "erf"}, {0: {"tile": (128, 192), "stages": 2, "ep": 0}}),
 }
 
 
 @pytest.mark.parametrize("launch,prec", [(f, p) for f in sorted(GELU_LAUNCHES) for p in GELU_LAUNCHES[f][0]])
 def test_gelu_epilogue_element_by_element(hip, launch, prec):
     _needs_256_cus()
-    _, M, K, aligned, modes = GELU_LAUNCHES[launch]
+    _, M, K, aligned, modes, kforms = GELU_LAUNCHES[launch]
     if prec == "fp8":
         K = 128
     x = gelu_sweep()
@@ -478,7 +502,7 @@ def test_gelu_epilogue_element_by_element(hip, launch, prec):
         cls = _out_cls(prec, mode)
         form = form or GELU_FORM.get(prec, "erf")
         bias = x.cuda() if aligned else _misaligned(x.cuda())
-        got, _ = _launch(prec, M, N, K, mode, bias=bias, act=1)
+        got, _ = _launch(prec, M, N, K, mode, bias=bias, act=1, form=kforms[mode])
         for g in _planes(got, cls):
             assert torch.equal(g, g[:1].expand_as(g)), f"{launch} {prec} mode {mode}: a row differs from row 0"
         row0 = got[:, :1].contiguous() if got.dim() == 3 else got[:1].contiguous()
@@ -498,11 +522,12 @@ def test_gelu_epilogue_element_by_element(hip, launch, prec):
 
 @pytest.mark.parametrize("M", [300, 8448])
 def test_gelu_f16c8_layernorm_fold_consumer(hip, M):
-    """gemm_f16c8.hip:544: EP 1 with GELU and the LayerNorm fold's consumer side (K = 768), ln_colsum = 0."""
+    """EP 1 with GELU and the LayerNorm fold's consumer side (K = 768), ln_colsum = 0, small and large form."""
     _needs_256_cus()
     x = gelu_sweep()
     N = x.numel()
-    got, _ = _launch("f16c8", M, N, 768, 0, bias=x.cuda(), act=1, ln_apply=(_any_stats(M), torch.zeros(N, device="cuda"), 1e-6))
+    got, _ = _launch("f16c8", M, N, 768, 0, bias=x.cuda(), act=1, ln_apply=(_any_stats(M), torch.zeros(N, device="cuda"), 1e-6),
+                     form={**(_C8S if M == 300 else _C8L), "ep": 1, "gelu": True, "lnf": True})
     for g in _planes(got, "f16c8"):
         assert torch.equal(g, g[:1].expand_as(g))
     check_gelu(x, _value_of(got[:, :1].contiguous(), "f16c8")[0], "erf", "f16c8", f"fold consumer + GELU, M = {M}")
@@ -696,8 +721,8 @@ def test_im2col_normalises_pixels_far_outside_the_range(hip, prec, form, patch):
 
 
 # ------------------------------------------------------------------------------------------------------------------ part 5: the consuming side
-# name -> (M, split-K factor): gemm_f16c8.hip:507 (large: 132 tiles), :506 (small), :530 (the 128 x 96 form, at K = 768 through split-K)
-C8_CONSUMER = {"large": (8448, 0), "small": (300, 0), "128x96": (300, 2)}
+# name -> (M, split-K factor, tile): large (132 tiles), small, the 128 x 96 form (at K = 768 through split-K)
+C8_CONSUMER = {"large": (8448, 0, (256, 192)), "small": (300, 0, (128, 192)), "128x96": (300, 2, (128, 96))}
 
 
 @pytest.mark.parametrize("form", sorted(C8_CONSUMER))
@@ -706,7 +731,7 @@ def test_gemm_f16c8_a_elements_beyond_448(hip, form):
     from {449, 1000, 30000, 65504}, W has one column at 1e-4.  Against fp64 on the three decoded planes (f16c8_decode models the clamp) with
     the dot-product bound 2 K 2^-24 (|A_hi| |W|^T) + 1e-6; everything finite; the other rows have the bits they have without the outliers."""
     _needs_256_cus()
-    M, split = C8_CONSUMER[form]
+    M, split, tile = C8_CONSUMER[form]
     N = K = 768
     rng = np.random.default_rng(77)
     a0 = _randn((M, K), 1.0, seed=51)
@@ -722,7 +747,8 @@ def test_gemm_f16c8_a_elements_beyond_448(hip, form):
     outs = []
     for a in (a0, a1):
         kw = {"split_k": (hip_ops.splitk_workspace(M, N), split)} if split else {}
-        outs.append(hip_ops.gemm(hip_ops.f16c8_encode(a, 0, False), w16, b, prec="f16c8", w_qexp=e, out_f32=True, **kw))
+        outs.append(hip_ops.gemm(hip_ops.f16c8_encode(a, 0, False), w16, b, prec="f16c8", w_qexp=e, out_f32=True,
+                                 expect={"tile": tile, "ep": 3, "split_k": split or 1}, **kw))
     torch.cuda.synchronize()
     base, out = outs
     assert torch.isfinite(out).all()
