@@ -92,6 +92,25 @@ class GemmPlan(C.Structure):
     _fields_ = [("n_launches", C.c_int), ("launch", GemmLaunch * GEMM_PLAN_MAX_LAUNCHES)]
 
 
+ATTN_ENTRY_PLAIN, ATTN_ENTRY_Q, ATTN_ENTRY_PREFIX, ATTN_ENTRY_VARLEN = 0, 1, 2, 3      # BD_ATTN_ENTRY_*
+ATTN_FAMILY_TILED, ATTN_FAMILY_PP = 1, 2               # BD_ATTN_FAMILY_*
+ATTN_KEY_LEN = 6
+
+
+class AttnCall(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("entry", "batch", "seq", "heads", "head_dim", "has_q_view", "q_len", "n_prefix", "prefix_queries",
+                                       "n_views", "max_views", "tokens_per_view", "prec", "latency_forms")]
+
+
+class AttnLaunch(C.Structure):
+    _fields_ = [("family", C.c_int), ("row", C.c_int), ("key", C.c_int * ATTN_KEY_LEN), ("grid", C.c_int), ("block", C.c_int),
+                ("q_len", C.c_int), ("q_off", C.c_int), ("out_rows", C.c_int)]
+
+
+class AttnPlan(C.Structure):
+    _fields_ = [("n_launches", C.c_int), ("launch", AttnLaunch * 1)]
+
+
 class Linear(C.Structure):
     _fields_ = [("w", C.c_void_p), ("b", C.c_void_p), ("wscale", C.c_void_p), ("w_qexp", C.c_int)]
 
@@ -146,7 +165,7 @@ EXPORTS = [
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
     "bd_round_sources", "bd_pose_select_rows",
     "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host",
-    "bd_gemm_plan", "bd_gemm_instance",
+    "bd_gemm_plan", "bd_gemm_instance", "bd_attention_plan", "bd_attention_instance",
 ]
 STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
 
@@ -177,6 +196,8 @@ def load() -> C.CDLL:
     lib.bd_gemm_takes_ln_fold.argtypes = [C.POINTER(GemmArgs), i]
     lib.bd_gemm_plan.argtypes = [C.POINTER(GemmArgs), i, i, i, C.POINTER(GemmPlan)]
     lib.bd_gemm_instance.argtypes = [i, i, C.POINTER(C.c_int)]
+    lib.bd_attention_plan.argtypes = [C.POINTER(AttnCall), vp, vp, vp, C.POINTER(AttnPlan)]
+    lib.bd_attention_instance.argtypes = [i, i, C.POINTER(C.c_int)]
     lib.bd_gemm_splitk_flag_bytes.argtypes = [i, i]
     lib.bd_gemm_splitk_flag_bytes.restype = sz
     lib.bd_gemm_splitk_workspace_bytes.argtypes = [i, i]

@@ -19,6 +19,7 @@
 // NS = 2 is the split-bf16 strict mode: Q, K, V, P each carry (hi, lo) and every product issues
 // hi*hi + hi*lo + lo*hi.
 #include "bd_common.h"
+#include <algorithm>
 #include <type_traits>
 
 #ifdef BD_ATTN_PROBE
@@ -815,60 +816,73 @@ __global__ __launch_bounds__(512, 1) void attn_kernel_pp(const AttnArgs p) {
     }
 }
 
-template <class T, int HD, int OUTMODE> int launch_pp(const AttnArgs& a, hipStream_t s) {
-    const int nqb = (a.q_len + 255) / 256;
-    const int slot = bd_trace_open(s, 1, a.batch * a.heads, a.seq, HD);
-    hipLaunchKernelGGL((attn_kernel_pp<T, HD, OUTMODE>), dim3(nqb * a.heads * a.batch), dim3(512), 0, s, a);
-    bd_trace_close(s, slot);
-    BD_CHECK_LAUNCH();
-    return BD_OK;
+// ---- Host side: validate -> plan -> launch (include/boxdreamer_hip.h: bd_attention_plan).  plan_attention decides everything about a call
+// on the host (no HIP call, no global state, nothing dereferenced) and names the kernel by its template arguments; one table per kernel
+// lists every instantiated kernel next to that key; launching is a lookup.  A key without a row is a plan error.
+typedef bd_attn_call AttnCall;
+struct attn_row { int key[BD_ATTN_KEY_LEN]; void (*fn)(const AttnArgs); };
+struct attn_table { int family; const attn_row* rows; int n; };
+
+// The operand classes, once: ONE(prec, TC, OUTMODE) is a single-plane class (NS = 1, both kernels), SPLIT(...) a split-bf16 one (NS = 2,
+// the tiled kernel only: it is register-bound at one wave per SIMD).  TC is the element type's code in a key: 0 __bf16, 1 _Float16.
+#define BD_ATTN_CLASSES(ONE, SPLIT)                                                                                    \
+    ONE(BD_PREC_BF16, 0, 0) ONE(BD_PREC_F16, 1, 0) SPLIT(BD_PREC_BF16X3, 0, 0)                                         \
+    ONE(BD_PREC_F16_OUT_BF16X3, 1, 1) ONE(BD_PREC_BF16_OUT_FP8, 0, 2)                                                  \
+    ONE(BD_PREC_F16_OUT_F16C8, 1, 3) SPLIT(BD_PREC_BF16X3_OUT_F16C8, 0, 3)                                             \
+    ONE(BD_PREC_F16_OUT_F16X3, 1, 4) SPLIT(BD_PREC_BF16X3_OUT_F16X3, 0, 4)
+template <int TC> using elem_of = typename std::conditional<TC == 0, __bf16, _Float16>::type;
+
+struct attn_class { int prec, tc, ns, om; };
+const attn_class* class_of(int prec) {
+#define BD_CLASS_ONE(PREC, TC, OM) {PREC, TC, 1, OM},
+#define BD_CLASS_SPLIT(PREC, TC, OM) {PREC, TC, 2, OM},
+    static const attn_class classes[] = {BD_ATTN_CLASSES(BD_CLASS_ONE, BD_CLASS_SPLIT)};
+#undef BD_CLASS_ONE
+#undef BD_CLASS_SPLIT
+    for (const attn_class& c : classes)
+        if (c.prec == prec) return &c;
+    return nullptr;
 }
 
-template <class T, int NS, int HD, int NW, int OUTMODE = 0> int launch(const AttnArgs& a, hipStream_t s) {
-    const int nqb = (a.q_len + NW * 32 - 1) / (NW * 32);
-    const int slot = bd_trace_open(s, 1, a.batch * a.heads, a.seq, HD);
-    hipLaunchKernelGGL((attn_kernel<T, NS, HD, NW, OUTMODE>), dim3(nqb * a.heads * a.batch), dim3(NW * 64), 0, s, a);
-    bd_trace_close(s, slot);
-    BD_CHECK_LAUNCH();
-    return BD_OK;
+// Every instantiated kernel: one argument list gives a row's key and its kernel, so a key cannot name another instance.
+// attn_kernel, per class: head_dim 96 and 64 on 4 and on 3 waves, and the ragged (VL) instance -- head_dim 96, 4 waves
+#define BD_TILED_ROW(TC, NS, HD, NW, OM, VL) {{TC, NS, HD, NW, OM, VL}, attn_kernel<elem_of<TC>, NS, HD, NW, OM, VL>},
+#define BD_TILED_CLASS(TC, NS, OM)                                                                                     \
+    BD_TILED_ROW(TC, NS, 96, 4, OM, false) BD_TILED_ROW(TC, NS, 96, 3, OM, false) BD_TILED_ROW(TC, NS, 64, 4, OM, false) \
+    BD_TILED_ROW(TC, NS, 64, 3, OM, false) BD_TILED_ROW(TC, NS, 96, 4, OM, true)
+#define BD_TILED_ONE(PREC, TC, OM) BD_TILED_CLASS(TC, 1, OM)
+#define BD_TILED_SPLIT(PREC, TC, OM) BD_TILED_CLASS(TC, 2, OM)
+attn_table tiled_table() {
+    static const attn_row rows[] = {BD_ATTN_CLASSES(BD_TILED_ONE, BD_TILED_SPLIT)};
+    return {BD_ATTN_FAMILY_TILED, rows, (int)(sizeof(rows) / sizeof(rows[0]))};
 }
+// attn_kernel_pp, per single-plane class: head_dim 96, uniform and ragged
+#define BD_PP_ROW(TC, OM, VL) {{TC, 96, OM, VL}, attn_kernel_pp<elem_of<TC>, 96, OM, VL>},
+#define BD_PP_ONE(PREC, TC, OM) BD_PP_ROW(TC, OM, false) BD_PP_ROW(TC, OM, true)
+#define BD_PP_SPLIT(PREC, TC, OM)
+attn_table pp_table() {
+    static const attn_row rows[] = {BD_ATTN_CLASSES(BD_PP_ONE, BD_PP_SPLIT)};
+    return {BD_ATTN_FAMILY_PP, rows, (int)(sizeof(rows) / sizeof(rows[0]))};
+}
+#undef BD_TILED_ROW
+#undef BD_TILED_CLASS
+#undef BD_TILED_ONE
+#undef BD_TILED_SPLIT
+#undef BD_PP_ROW
+#undef BD_PP_ONE
+#undef BD_PP_SPLIT
 
-// Ragged batches: the same two kernels, VL instances.  Whole q-blocks per view (tpv % 256 == 0 for the ping-pong kernel, % 128 for the
-// 4-wave one), so the grid is EXACTLY the batch's q-blocks -- n_views * (tpv / QB) * heads with every row a query, batch * (tpv / QB) * heads
-// with q_view -- and nothing is sized by the longest sample.  One launch; the trace record carries N = max_views * tpv.
-template <class T, int NS, int OUTMODE> int dispatch_vl(const AttnArgs& a, hipStream_t s) {
-    const int units = a.q_view ? a.batch : a.n_views;
-    const int slot = bd_trace_open(s, 1, a.batch * a.heads, a.max_views * a.tpv, 96);
-    if constexpr (NS == 1) {
-        if (a.tpv % 256 == 0) {
-            hipLaunchKernelGGL((attn_kernel_pp<T, 96, OUTMODE, true>), dim3(units * (a.tpv / 256) * a.heads), dim3(512), 0, s, a);
-            bd_trace_close(s, slot);
-            BD_CHECK_LAUNCH();
-            return BD_OK;
-        }
+// The launch of the table row with this key; BD_ERR_SHAPE when no instance has it: never a neighbouring instance
+int plan_row(const attn_table& t, const int (&key)[BD_ATTN_KEY_LEN], int grid, int block, bd_attn_launch* l) {
+    for (int r = 0; r < t.n; ++r) {
+        if (!std::equal(key, key + BD_ATTN_KEY_LEN, t.rows[r].key)) continue;
+        l->family = t.family;
+        l->row = r;
+        std::copy(key, key + BD_ATTN_KEY_LEN, l->key);
+        l->grid = grid;
+        l->block = block;
+        return BD_OK;
     }
-    hipLaunchKernelGGL((attn_kernel<T, NS, 96, 4, OUTMODE, true>), dim3(units * (a.tpv / 128) * a.heads), dim3(256), 0, s, a);
-    bd_trace_close(s, slot);
-    BD_CHECK_LAUNCH();
-    return BD_OK;
-}
-
-// (file-local) opt-in latency forms of the call being dispatched: set by bd_attention_q_forms around its dispatch, on the calling thread
-static thread_local bool g_latency_forms = false;
-
-template <class T, int NS, int OUTMODE = 0> int dispatch(const AttnArgs& a, int head_dim, hipStream_t s) {
-    // 3 waves (96-query blocks) when that tiles the sequence with less waste (DINOv2: 261 -> 3 x 96)
-    const int waste4 = ((a.q_len + 127) / 128) * 128 - a.q_len, waste3 = ((a.q_len + 95) / 96) * 96 - a.q_len;
-    const bool use3 = waste3 < waste4;
-    if constexpr (NS == 1) {
-        // ping-pong kernel where its 256-query blocks tile the query range without waste (BETR: 1536 = 6 x 256; last block: 256)
-        // (latency forms, round 6: one pose at a time the 256-query blocks are 48 workgroups on 256 CUs, 36 us; the 128-query kernel's 96
-        // take 31 us -- and lose from two poses on: profiles/r6_attn_b1_probe.txt)
-        const bool few = g_latency_forms && 4 * ((a.q_len + 255) / 256) * a.heads * a.batch <= 256;      // (a quarter of MI355X's 256 CUs)
-        if (head_dim == 96 && a.q_len % 256 == 0 && a.seq % KT == 0 && !few) return launch_pp<T, 96, OUTMODE>(a, s);      // (whole key tiles only: the kernel has no tail mask)
-    }
-    if (head_dim == 96) return use3 ? launch<T, NS, 96, 3, OUTMODE>(a, s) : launch<T, NS, 96, 4, OUTMODE>(a, s);
-    if (head_dim == 64) return use3 ? launch<T, NS, 64, 3, OUTMODE>(a, s) : launch<T, NS, 64, 4, OUTMODE>(a, s);
     return BD_ERR_SHAPE;
 }
 
@@ -877,93 +891,129 @@ inline bool sample_bytes_out_of_range(int seq, int heads, int head_dim) {
     return head_dim <= 0 || (int64_t)seq * 3 * heads * head_dim * 2 >= ((int64_t)1 << 31);
 }
 
+// The shape rules of a call: what its entry point refuses before it looks at the pointers' alignment
+int call_shape(const AttnCall& c) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (c.entry < BD_ATTN_ENTRY_PLAIN || c.entry > BD_ATTN_ENTRY_VARLEN) return BD_ERR_SHAPE;
+    if (c.entry == BD_ATTN_ENTRY_VARLEN) {
+        const int tpv = c.tokens_per_view;
+        if (c.batch <= 0 || c.heads <= 0 || c.n_views < c.batch || c.max_views <= 0 || c.max_views > c.n_views - (c.batch - 1)) return BD_ERR_SHAPE;
+        if (tpv <= 0 || tpv % 128) return BD_ERR_SHAPE;      // whole q-blocks and key tiles per view: no tail masks
+        if (c.head_dim != 96) return BD_ERR_SHAPE;            // (DINOv2's head_dim 64 sequences are per image, never ragged)
+        if ((int64_t)c.max_views * tpv >= lim || sample_bytes_out_of_range(c.max_views * tpv, c.heads, c.head_dim)) return BD_ERR_SHAPE;
+        return (int64_t)c.n_views * (tpv / 128) * c.heads >= lim ? BD_ERR_SHAPE : BD_OK;
+    }
+    if (c.batch <= 0 || c.seq <= 0 || c.heads <= 0) return BD_ERR_SHAPE;
+    if (c.entry == BD_ATTN_ENTRY_PREFIX && (c.n_prefix <= 0 || c.n_prefix >= c.seq)) return BD_ERR_SHAPE;
+    if (c.entry == BD_ATTN_ENTRY_Q && (c.has_q_view ? (c.q_len <= 0 || c.q_len > c.seq || c.seq % c.q_len) : (c.q_len != c.seq))) return BD_ERR_SHAPE;
+    return sample_bytes_out_of_range(c.seq, c.heads, c.head_dim) ? BD_ERR_SHAPE : BD_OK;
+}
+
+// The one launch of a call, or the code its entry point refuses it with (pointers apart: plan_checked)
+int plan_attention(const AttnCall& c, bd_attn_launch* l) {
+    if (const int rc = call_shape(c)) return rc;
+    const attn_class* k = class_of(c.prec);
+    if (!k) return BD_ERR_DTYPE;
+    if (c.entry == BD_ATTN_ENTRY_VARLEN) {
+        // Ragged batches, the VL instances.  Whole q-blocks per view (tpv % 256 == 0 for the ping-pong kernel, % 128 for the 4-wave one), so
+        // the grid is EXACTLY the batch's q-blocks -- n_views * (tpv / QB) * heads with every row a query, batch * (tpv / QB) * heads with
+        // q_view -- and nothing is sized by the longest sample.
+        const int tpv = c.tokens_per_view, units = c.has_q_view ? c.batch : c.n_views;
+        l->q_len = l->out_rows = tpv;
+        l->q_off = 0;
+        if (k->ns == 1 && tpv % 256 == 0) return plan_row(pp_table(), {k->tc, 96, k->om, true}, units * (tpv / 256) * c.heads, 512, l);
+        return plan_row(tiled_table(), {k->tc, k->ns, 96, 4, k->om, true}, units * (tpv / 128) * c.heads, 256, l);
+    }
+    // With the prefix queries wanted, one launch over all seq queries IS the fastest form measured (profiles/r4_attention.md: a separate
+    // launch for the prefix rows re-reads the pair's K / V -- 154 MB per DINOv2 launch -- and costs more than the ninth query wave it
+    // saves); without them, the patch queries alone tile exactly: the seq - n_prefix queries behind the prefix, all keys; result rows
+    // [n_prefix, seq) of every sample, the others untouched
+    const bool skip_prefix = c.entry == BD_ATTN_ENTRY_PREFIX && !c.prefix_queries;
+    const int q_len = skip_prefix ? c.seq - c.n_prefix : c.entry == BD_ATTN_ENTRY_Q ? c.q_len : c.seq;
+    l->q_len = q_len;
+    l->q_off = skip_prefix ? c.n_prefix : 0;
+    l->out_rows = skip_prefix ? c.seq : q_len;
+    if (c.head_dim != 96 && c.head_dim != 64) return BD_ERR_SHAPE;
+    // ping-pong kernel where its 256-query blocks tile the query range without waste (BETR: 1536 = 6 x 256; last block: 256)
+    // (latency forms, round 6: one pose at a time the 256-query blocks are 48 workgroups on 256 CUs, 36 us; the 128-query kernel's 96
+    // take 31 us -- and lose from two poses on: profiles/r6_attn_b1_probe.txt)
+    const bool few = c.latency_forms && 4 * ((q_len + 255) / 256) * c.heads * c.batch <= 256;      // (a quarter of MI355X's 256 CUs)
+    if (k->ns == 1 && c.head_dim == 96 && q_len % 256 == 0 && c.seq % KT == 0 && !few)               // (whole key tiles only: the kernel has no tail mask)
+        return plan_row(pp_table(), {k->tc, 96, k->om, false}, (q_len / 256) * c.heads * c.batch, 512, l);
+    // 3 waves (96-query blocks) when that tiles the sequence with less waste (DINOv2: 261 -> 3 x 96)
+    const int waste4 = ((q_len + 127) / 128) * 128 - q_len, waste3 = ((q_len + 95) / 96) * 96 - q_len;
+    const int nw = waste3 < waste4 ? 3 : 4;
+    return plan_row(tiled_table(), {k->tc, k->ns, c.head_dim, nw, k->om, false}, ((q_len + nw * 32 - 1) / (nw * 32)) * c.heads * c.batch, nw * 64, l);
+}
+
+// validate -> plan, for the entry points and bd_attention_plan alike.  Refusals win in the entry points' order: a null pointer, the
+// call's shape, a misaligned pointer, then the class and head_dim.
+int plan_checked(const AttnCall& c, const void* qkv, const void* out, const void* view_start, bd_attn_launch* l) {
+    if (!qkv || !out || (c.entry == BD_ATTN_ENTRY_VARLEN && !view_start)) return BD_ERR_NULL;
+    if (const int rc = call_shape(c)) return rc;
+    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return BD_ERR_ALIGN;
+    return plan_attention(c, l);
+}
+
+// The one launcher.  Launch trace: one kind-1 record over the sample's (ragged: the longest sample's) key rows.
+int run(const AttnCall& c, const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, float scale, const int32_t* q_view,
+        const int32_t* view_start, void* stream) {
+    bd_attn_launch l;
+    if (const int rc = plan_checked(c, qkv, out, view_start, &l)) return rc;
+    const AttnArgs a{qkv, qkv_plane, out, out_plane, c.batch, c.seq, c.heads, scale * 1.4426950408889634f, q_view, l.q_len, l.q_off, l.out_rows,
+                     view_start, c.tokens_per_view, c.n_views, c.max_views};
+    const attn_table t = l.family == BD_ATTN_FAMILY_PP ? pp_table() : tiled_table();
+    hipStream_t s = (hipStream_t)stream;
+    const int slot = bd_trace_open(s, 1, c.batch * c.heads, view_start ? c.max_views * c.tokens_per_view : c.seq, c.head_dim);
+    hipLaunchKernelGGL(t.rows[l.row].fn, dim3(l.grid), dim3(l.block), 0, s, a);
+    bd_trace_close(s, slot);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
 }  // namespace
 
 int bd_attention_q_forms(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch, int seq, int heads, int head_dim,
                          float scale, const int32_t* q_view, int q_len, int prec, int latency_forms, void* stream) {
-    g_latency_forms = latency_forms != 0;
-    const int rc = bd_attention_q(qkv, qkv_plane, out, out_plane, batch, seq, heads, head_dim, scale, q_view, q_len, prec, stream);
-    g_latency_forms = false;
-    return rc;
+    return run({BD_ATTN_ENTRY_Q, batch, seq, heads, head_dim, q_view != nullptr, q_len, 0, 0, 0, 0, 0, prec, latency_forms != 0}, qkv, qkv_plane,
+               out, out_plane, scale, q_view, nullptr, stream);
 }
 
 extern "C" int bd_attention_q(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch, int seq,
                               int heads, int head_dim, float scale, const int32_t* q_view, int q_len, int prec,
                               void* stream) {
-    if (!qkv || !out) return BD_ERR_NULL;
-    if (batch <= 0 || seq <= 0 || heads <= 0) return BD_ERR_SHAPE;
-    if (q_view ? (q_len <= 0 || q_len > seq || seq % q_len) : (q_len != seq)) return BD_ERR_SHAPE;
-    if (sample_bytes_out_of_range(seq, heads, head_dim)) return BD_ERR_SHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return BD_ERR_ALIGN;
-    AttnArgs a{qkv, qkv_plane, out, out_plane, batch, seq, heads, scale * 1.4426950408889634f, q_view, q_len, 0, q_len};
-    hipStream_t s = (hipStream_t)stream;
-    switch (prec) {
-        case BD_PREC_BF16: return dispatch<__bf16, 1>(a, head_dim, s);
-        case BD_PREC_F16: return dispatch<_Float16, 1>(a, head_dim, s);
-        case BD_PREC_BF16X3: return dispatch<__bf16, 2>(a, head_dim, s);
-        case BD_PREC_F16_OUT_BF16X3: return dispatch<_Float16, 1, 1>(a, head_dim, s);
-        case BD_PREC_BF16_OUT_FP8: return dispatch<__bf16, 1, 2>(a, head_dim, s);
-        case BD_PREC_F16_OUT_F16C8: return dispatch<_Float16, 1, 3>(a, head_dim, s);
-        case BD_PREC_BF16X3_OUT_F16C8: return dispatch<__bf16, 2, 3>(a, head_dim, s);
-        case BD_PREC_F16_OUT_F16X3: return dispatch<_Float16, 1, 4>(a, head_dim, s);
-        case BD_PREC_BF16X3_OUT_F16X3: return dispatch<__bf16, 2, 4>(a, head_dim, s);
-        default: return BD_ERR_DTYPE;
-    }
+    return bd_attention_q_forms(qkv, qkv_plane, out, out_plane, batch, seq, heads, head_dim, scale, q_view, q_len, prec, 0, stream);
 }
-
-// prec -> (T, NS, OUTMODE) for both the tiled and the prefix kernel
-#define BD_ATTN_PREC_SWITCH(CALL)                                                       \
-    switch (prec) {                                                                     \
-        case BD_PREC_BF16: return CALL(__bf16, 1, 0);                                   \
-        case BD_PREC_F16: return CALL(_Float16, 1, 0);                                  \
-        case BD_PREC_BF16X3: return CALL(__bf16, 2, 0);                                 \
-        case BD_PREC_F16_OUT_BF16X3: return CALL(_Float16, 1, 1);                       \
-        case BD_PREC_BF16_OUT_FP8: return CALL(__bf16, 1, 2);                           \
-        case BD_PREC_F16_OUT_F16C8: return CALL(_Float16, 1, 3);                        \
-        case BD_PREC_BF16X3_OUT_F16C8: return CALL(__bf16, 2, 3);                       \
-        case BD_PREC_F16_OUT_F16X3: return CALL(_Float16, 1, 4);                        \
-        case BD_PREC_BF16X3_OUT_F16X3: return CALL(__bf16, 2, 4);                       \
-        default: return BD_ERR_DTYPE;                                                   \
-    }
 
 extern "C" int bd_attention_prefix(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch, int seq, int heads,
                                    int head_dim, float scale, int n_prefix, int prefix_queries, int prec, void* stream) {
-    if (!qkv || !out) return BD_ERR_NULL;
-    if (batch <= 0 || seq <= 0 || heads <= 0 || n_prefix <= 0 || n_prefix >= seq) return BD_ERR_SHAPE;
-    if (sample_bytes_out_of_range(seq, heads, head_dim)) return BD_ERR_SHAPE;
-    // With the prefix queries wanted, one launch over all seq queries IS the fastest form measured (profiles/r4_attention.md: a separate
-    // launch for the prefix rows re-reads the pair's K / V -- 154 MB per DINOv2 launch -- and costs more than the ninth query wave it
-    // saves); without them, the patch queries alone tile exactly.
-    if (prefix_queries) return bd_attention_q(qkv, qkv_plane, out, out_plane, batch, seq, heads, head_dim, scale, nullptr, seq, prec, stream);
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return BD_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    // the seq - n_prefix queries behind the prefix, all keys; result rows [n_prefix, seq) of every sample, the others untouched
-    AttnArgs a{qkv, qkv_plane, out, out_plane, batch, seq, heads, scale * 1.4426950408889634f, nullptr, seq - n_prefix, n_prefix, seq};
-#define BD_CALL_MAIN(T_, NS_, OM_) dispatch<T_, NS_, OM_>(a, head_dim, s)
-    BD_ATTN_PREC_SWITCH(BD_CALL_MAIN)
-#undef BD_CALL_MAIN
+    return run({BD_ATTN_ENTRY_PREFIX, batch, seq, heads, head_dim, 0, 0, n_prefix, prefix_queries, 0, 0, 0, prec, 0}, qkv, qkv_plane, out,
+               out_plane, scale, nullptr, nullptr, stream);
 }
 
 extern "C" int bd_attention(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, int batch,
                             int seq, int heads, int head_dim, float scale, int prec, void* stream) {
-    return bd_attention_q(qkv, qkv_plane, out, out_plane, batch, seq, heads, head_dim, scale, nullptr, seq, prec, stream);
+    return run({BD_ATTN_ENTRY_PLAIN, batch, seq, heads, head_dim, 0, 0, 0, 0, 0, 0, 0, prec, 0}, qkv, qkv_plane, out, out_plane, scale, nullptr,
+               nullptr, stream);
 }
 
 extern "C" int bd_attention_varlen(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, const int32_t* view_start, int batch,
                                    int n_views, int max_views, int tokens_per_view, int heads, int head_dim, float scale,
                                    const int32_t* q_view, int prec, void* stream) {
-    if (!qkv || !out || !view_start) return BD_ERR_NULL;
-    if (batch <= 0 || heads <= 0 || n_views < batch || max_views <= 0 || max_views > n_views - (batch - 1)) return BD_ERR_SHAPE;
-    if (tokens_per_view <= 0 || tokens_per_view % 128) return BD_ERR_SHAPE;      // whole q-blocks and key tiles per view: no tail masks
-    if (head_dim != 96) return BD_ERR_SHAPE;                                     // (DINOv2's head_dim 64 sequences are per image, never ragged)
-    if ((int64_t)max_views * tokens_per_view >= ((int64_t)1 << 31) || sample_bytes_out_of_range(max_views * tokens_per_view, heads, head_dim))
-        return BD_ERR_SHAPE;
-    if ((int64_t)n_views * (tokens_per_view / 128) * heads >= ((int64_t)1 << 31)) return BD_ERR_SHAPE;
-    if (((uintptr_t)qkv & 15) || ((uintptr_t)out & 7)) return BD_ERR_ALIGN;
-    AttnArgs a{qkv, qkv_plane, out, out_plane, batch, 0, heads, scale * 1.4426950408889634f, q_view, tokens_per_view, 0, tokens_per_view,
-               view_start, tokens_per_view, n_views, max_views};
-    hipStream_t s = (hipStream_t)stream;
-#define BD_CALL_VL(T_, NS_, OM_) dispatch_vl<T_, NS_, OM_>(a, s)
-    BD_ATTN_PREC_SWITCH(BD_CALL_VL)
-#undef BD_CALL_VL
+    return run({BD_ATTN_ENTRY_VARLEN, batch, 0, heads, head_dim, q_view != nullptr, 0, 0, 0, n_views, max_views, tokens_per_view, prec, 0}, qkv,
+               qkv_plane, out, out_plane, scale, q_view, view_start, stream);
+}
+
+extern "C" int bd_attention_plan(const bd_attn_call* call, const void* qkv, const void* out, const void* view_start, bd_attn_plan_t* plan) {
+    if (!plan) return BD_ERR_NULL;
+    const int rc = call ? plan_checked(*call, qkv, out, view_start, &plan->launch[0]) : BD_ERR_NULL;
+    plan->n_launches = rc == BD_OK;
+    return rc;
+}
+
+extern "C" int bd_attention_instance(int family, int index, int* key) {
+    const attn_table t = family == BD_ATTN_FAMILY_TILED ? tiled_table() : family == BD_ATTN_FAMILY_PP ? pp_table() : attn_table{0, nullptr, 0};
+    if (!key || index < 0 || index >= t.n) return 0;
+    std::copy(t.rows[index].key, t.rows[index].key + BD_ATTN_KEY_LEN, key);
+    return 1;
 }

@@ -239,6 +239,27 @@ def qk_rmsnorm_(qkv16, wq, wk, eps, heads, head_dim, *, prec="bf16"):
     return qkv16
 
 
+_ATTN_ENTRY = {"plain": _lib.ATTN_ENTRY_PLAIN, "q": _lib.ATTN_ENTRY_Q, "prefix": _lib.ATTN_ENTRY_PREFIX, "varlen": _lib.ATTN_ENTRY_VARLEN}
+
+
+def attention_plan(entry, *, prec="bf16", latency_forms=False, q_view=False, pointers=(0x7F0000001000, 0x7F0000002000, 0x7F0000003000), **fields):
+    """bd_attention_plan (host only): the launch attention / attention_q / attention_prefix / attention_varlen (entry "plain", "q",
+    "prefix", "varlen") makes of a call with these integer arguments (fields of bd_attn_call; q_view: whether one is given).  A dict:
+    kernel ("tiled": attn_kernel, "pp": the ping-pong kernel attn_kernel_pp), waves, planes, head_dim, out_mode, vl, key, grid, block,
+    q_len, q_off, out_rows.  pointers: (qkv, out, view_start) addresses, made-up aligned ones by default.  Raises HipLibraryError where
+    the entry point refuses the call."""
+    call, plan = _lib.AttnCall(entry=_ATTN_ENTRY[entry], has_q_view=int(bool(q_view)), prec=prec_id(prec), latency_forms=int(bool(latency_forms)), **fields), _lib.AttnPlan()
+    check(_lib.load().bd_attention_plan(C.byref(call), *pointers, C.byref(plan)), "bd_attention_plan")
+    l = plan.launch[0]
+    k = list(l.key)
+    d = {"key": k, "grid": l.grid, "block": l.block, "q_len": l.q_len, "q_off": l.q_off, "out_rows": l.out_rows}
+    if l.family == _lib.ATTN_FAMILY_PP:
+        d.update(kernel="pp", waves=8, planes=1, head_dim=k[1], out_mode=k[2], vl=bool(k[3]))
+    else:
+        d.update(kernel="tiled", waves=k[3], planes=k[1], head_dim=k[2], out_mode=k[4], vl=bool(k[5]))
+    return d
+
+
 def attention(qkv16, batch, seq, heads, head_dim, scale, *, prec="bf16"):
     lib = _lib.load()
     dev = qkv16.device

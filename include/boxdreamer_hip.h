@@ -287,14 +287,55 @@ int bd_attention_prefix(const void* qkv, int64_t qkv_plane, void* out, int64_t o
  * head_dim == 96 only (BETR; DINOv2's head_dim-64 sequences are per image and never ragged) and tokens_per_view % 128 == 0, so that every
  * sample is whole 64-key tiles and whole query blocks and no tail is masked (BETR: 256): BD_ERR_SHAPE otherwise.  The 2 GiB rule of
  * bd_attention applies per sample, to max_views * tokens_per_view rows.  Every `prec` bd_attention takes.
- * ONE launch: the work list (sample, head, query block) is implicit in the offsets -- the grid is exactly the batch's query blocks,
- * n_views * (tokens_per_view / 256 or 128) * heads (q_view: batch * ...), never sized by the longest sample; a workgroup finds its sample
- * with one ballot over the offsets.  The same kernels as bd_attention (ping-pong for the single-plane classes at tokens_per_view % 256 == 0,
- * else the 4-wave kernel), taking their base row and key count per sample: a row's bits equal bd_attention[_q] run on that sample alone
- * (batch = 1, seq = its rows).  Launch trace: one kind-1 record, N = max_views * tokens_per_view. */
+ * ONE launch: the work list (sample, head, query block) is implicit in the offsets -- the grid is exactly the batch's query blocks
+ * (q_view: the batch's query views' blocks), never sized by the longest sample; a workgroup finds its sample with one ballot over the
+ * offsets.  The same kernels as bd_attention, as their VL instances (which one, and the grid: bd_attention_plan), taking their base row
+ * and key count per sample: a row's bits equal bd_attention[_q] run on that sample alone (batch = 1, seq = its rows).
+ * Launch trace: one kind-1 record, N = max_views * tokens_per_view. */
 int bd_attention_varlen(const void* qkv, int64_t qkv_plane, void* out, int64_t out_plane, const int32_t* view_start, int batch,
                         int n_views, int max_views, int tokens_per_view, int heads, int head_dim, float scale,
                         const int32_t* q_view, int prec, void* stream);
+
+/* Which kernel instance an attention call launches, decided on the host (no GPU needed, nothing is launched or dereferenced; for tests
+ * and tools -- nothing on the product path calls these).  The four entry points plan with the same function and then launch the plan.
+ * A call is described by bd_attn_call: the entry point and its integer arguments (fields an entry point does not take are ignored),
+ * whether q_view is given, and latency_forms -- the opt-in forms of bd_*_weights.latency_mode, which no public entry point can ask for
+ * (they pass 0).  A launch names one row of its kernel family's instance table; `key` holds the template arguments as integers:
+ *   BD_ATTN_FAMILY_TILED  attn_kernel     T (0 bf16, 1 f16), NS, HD, NW, OUTMODE, VL
+ *   BD_ATTN_FAMILY_PP     attn_kernel_pp  T, HD, OUTMODE, VL
+ * (NS: operand planes; HD: head_dim; NW: waves = 32-query blocks per workgroup, the ping-pong kernel has 8; OUTMODE: 0 operand class,
+ * 1 split-bf16, 2 e4m3, 3 F16C8, 4 split-f16; VL: the ragged instance.)  q_len / q_off / out_rows: queries are the rows [q_off, q_off +
+ * q_len) of a sample (of its query view with q_view), written to a sample's out_rows result rows from q_off. */
+#define BD_ATTN_ENTRY_PLAIN 0                      /* bd_attention */
+#define BD_ATTN_ENTRY_Q 1                          /* bd_attention_q */
+#define BD_ATTN_ENTRY_PREFIX 2                     /* bd_attention_prefix */
+#define BD_ATTN_ENTRY_VARLEN 3                     /* bd_attention_varlen */
+#define BD_ATTN_FAMILY_TILED 1
+#define BD_ATTN_FAMILY_PP 2
+#define BD_ATTN_KEY_LEN 6
+typedef struct bd_attn_call {
+    int entry;
+    int batch, seq, heads, head_dim;
+    int has_q_view, q_len;                         /* bd_attention_q, bd_attention_varlen (has_q_view only) */
+    int n_prefix, prefix_queries;                  /* bd_attention_prefix */
+    int n_views, max_views, tokens_per_view;       /* bd_attention_varlen (which takes no seq) */
+    int prec;
+    int latency_forms;
+} bd_attn_call;
+typedef struct bd_attn_launch {
+    int family, row;                               /* row: index into the family's table (bd_attention_instance) */
+    int key[BD_ATTN_KEY_LEN];
+    int grid, block;                               /* workgroups, threads per workgroup */
+    int q_len, q_off, out_rows;
+} bd_attn_launch;
+typedef struct bd_attn_plan_t { int n_launches; bd_attn_launch launch[1]; } bd_attn_plan_t;
+/* Writes the plan of `call` made with these pointers (device addresses, compared with NULL and checked for alignment only; view_start:
+ * bd_attention_varlen).  Returns BD_OK, or the BD_ERR_* code with which the entry point refuses the call (out->n_launches = 0 then). */
+int bd_attention_plan(const bd_attn_call* call /*[host]*/, const void* qkv, const void* out, const void* view_start,
+                      bd_attn_plan_t* plan /*[host]*/);
+/* Row `index` of a family's instance table: writes its key (BD_ATTN_KEY_LEN ints) and returns 1; returns 0 past the end of the
+ * table or for an unknown family.  The tables hold every instantiated attention kernel. */
+int bd_attention_instance(int family, int index, int* key /*[host]*/);
 
 /* (x - mean_c) / std_c, then 14x14 patches -> A operand rows [n*grid*grid, kpad], k = c*p*p + py*p + px,
  * zero-padded to kpad.  Replaces encoder/dinov2.py:45-46,56 + the unfold inside the patch-embed conv. */

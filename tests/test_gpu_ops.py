@@ -548,6 +548,14 @@ def test_attention_prefix_split(hip, variant, batch, seq, heads, npre):
         return (o[0].float() + o[1].float()).cpu().reshape(batch, seq, heads, hd)
 
     plane = lambda o: 0 if kind in ("native", "fp8") else o[0].numel()
+    # the forms, through the plan: prefix_queries = 1 is bd_attention's one launch; without them the same attn_kernel class on the seq - npre
+    # patch queries, written behind the prefix rows (head_dim 64: never the ping-pong kernel)
+    call = dict(prec=pid, batch=batch, seq=seq, heads=heads, head_dim=hd)
+    p1, p2, p3 = (hip_ops.attention_plan("plain", **call), hip_ops.attention_plan("prefix", n_prefix=npre, prefix_queries=1, **call),
+                  hip_ops.attention_plan("prefix", n_prefix=npre, prefix_queries=0, **call))
+    assert p2 == p1 and p1["kernel"] == "tiled" and (p1["q_len"], p1["q_off"], p1["out_rows"]) == (seq, 0, seq)
+    assert (p3["q_len"], p3["q_off"], p3["out_rows"]) == (seq - npre, npre, seq) and p3["grid"] == -(-(seq - npre) // (32 * p3["waves"])) * heads * batch
+    assert [p3[k] for k in ("kernel", "planes", "head_dim", "out_mode", "vl")] == [p1[k] for k in ("kernel", "planes", "head_dim", "out_mode", "vl")]
     one = alloc()
     _lib.check(lib.bd_attention(_lib.ptr(t), qkv_plane, _lib.ptr(one), plane(one), batch, seq, heads, hd, hd ** -0.5, pid, _lib.stream()),
                "bd_attention")

@@ -65,17 +65,36 @@ def _same(a, b):
     return all(torch.equal(x, y) for x, y in zip(a, b))
 
 
+VARLEN_BATCHES = (((2, 6, 3, 17, 2), (1, 0, 2, 9, 0)), ((4, 4, 4), (3, 0, 2)))       # (view counts, query view per sample)
+
+
+def varlen_plans(variant, counts):
+    """The plans of the two ragged launches of test_attention_varlen_bit_identical_to_each_sample_alone (every row a query; query views
+    only), held against the forms the test is about: at 256 tokens per view the ragged ping-pong instance for the one-plane classes and
+    the ragged 4-wave instance of attn_kernel for the split-bf16 ones, on exactly the batch's query blocks."""
+    in_prec, code, _ = VARIANTS[variant]
+    call = dict(prec=getattr(_lib, code), batch=len(counts), n_views=sum(counts), max_views=max(counts), tokens_per_view=TPV, heads=HEADS, head_dim=HD)
+    plans = [hip_ops.attention_plan("varlen", **call), hip_ops.attention_plan("varlen", q_view=True, **call)]
+    kernel, waves = ("tiled", 4) if in_prec == "bf16x3" else ("pp", 8)
+    for p, units in zip(plans, (sum(counts), len(counts))):
+        assert (p["kernel"], p["waves"], p["vl"], p["head_dim"]) == (kernel, waves, True, HD), p
+        assert p["grid"] == units * (TPV // (32 * waves)) * HEADS and (p["q_len"], p["q_off"], p["out_rows"]) == (TPV, 0, TPV), p
+    return plans
+
+
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 def test_attention_varlen_bit_identical_to_each_sample_alone(hip, variant):
     """bd_attention_varlen on a packed batch with view counts (2, 6, 3, 17, 2) == bd_attention / bd_attention_q on every sample alone
-    (batch = 1, seq = T_b * 256), bit for bit, in both query forms; with equal counts == the uniform bd_attention call."""
+    (batch = 1, seq = T_b * 256), bit for bit, in both query forms; with equal counts == the uniform bd_attention call.  The ragged
+    launches run the VL instance of the kernel the samples alone run (varlen_plans)."""
     lib = _lib.load()
     in_prec, code, kind = VARIANTS[variant]
     pid = getattr(_lib, code)
     split = in_prec == "bf16x3"
     scale = HD ** -0.5
-    for counts, qv in (((2, 6, 3, 17, 2), (1, 0, 2, 9, 0)), ((4, 4, 4), (3, 0, 2))):
+    for counts, qv in VARLEN_BATCHES:
         B, n_views, starts = len(counts), sum(counts), _lib.view_starts(counts)
+        varlen_plans(variant, counts)
         t = hip_ops.to_operand(_qkv(counts, 11 + n_views).cuda(), in_prec)
         qplane = t[0].numel() if split else 0
         vs = torch.tensor(starts, dtype=torch.int32).cuda()

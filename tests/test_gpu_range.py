@@ -772,7 +772,31 @@ ONE_HOT = float.fromhex("0x1.62e43p+99")
 assert np.float32(np.float32(ONE_HOT) * np.float32(1.4426950408889634)) == np.float32(2.0 ** 100)
 
 
-@pytest.mark.parametrize("seq,hd", [(70, 64), (70, 96), (261, 64), (261, 96), (256, 64), (256, 96)])
+V_ROW_SHAPES = [(70, 64), (70, 96), (261, 64), (261, 96), (256, 64), (256, 96)]
+V_ROW_BATCH, V_ROW_HEADS, V_ROW_NPRE = 2, 2, 5
+V_ROW_Q_LEN = {70: 35, 261: 87, 256: 128}
+# seq -> waves of attn_kernel for bd_attention, bd_attention_q (V_ROW_Q_LEN queries) and bd_attention_prefix (seq - 5 patch queries)
+V_ROW_WAVES = {70: (3, 3, 3), 261: (3, 3, 4), 256: (4, 4, 4)}
+
+
+def v_row_plans(variant, seq, hd):
+    """The plans of the three launches of test_attention_stores_the_v_row, held against the forms the test is about: attn_kernel on
+    V_ROW_WAVES, but the ping-pong kernel for bd_attention on 256 rows at head_dim 96 in the one-plane classes (the prefix call's 256
+    queries of 261 rows stay on attn_kernel: 261 keys are no whole key tiles)."""
+    in_prec, code, _ = _PREFIX_VARIANTS[variant]
+    call = dict(prec=getattr(_lib, code), batch=V_ROW_BATCH, seq=seq, heads=V_ROW_HEADS, head_dim=hd)
+    plans = [hip_ops.attention_plan("plain", **call), hip_ops.attention_plan("q", q_view=True, q_len=V_ROW_Q_LEN[seq], **call),
+             hip_ops.attention_plan("prefix", n_prefix=V_ROW_NPRE, prefix_queries=0, **call)]
+    want = [("tiled", w) for w in V_ROW_WAVES[seq]]
+    if seq == 256 and hd == 96 and _lib.planes(in_prec) == 1:
+        want[0] = ("pp", 8)
+    assert [(p["kernel"], p["waves"]) for p in plans] == want and all(p["head_dim"] == hd and not p["vl"] for p in plans), plans
+    q_len = V_ROW_Q_LEN[seq]
+    assert [(p["q_len"], p["q_off"], p["out_rows"]) for p in plans] == [(seq, 0, seq), (q_len, 0, q_len), (seq - V_ROW_NPRE, V_ROW_NPRE, seq)]
+    return plans
+
+
+@pytest.mark.parametrize("seq,hd", V_ROW_SHAPES)
 @pytest.mark.parametrize("variant", sorted(_PREFIX_VARIANTS))
 def test_attention_stores_the_v_row(hip, variant, seq, hd):
     """Within a (sample, head) every key has the same V row, taken from the steered table of the INPUT class; Q and K are random.  The
@@ -783,11 +807,13 @@ def test_attention_stores_the_v_row(hip, variant, seq, hd):
     the accumulator exactly V -- also for the largest bf16 values, which an accumulation over several keys with non-zero P overflows
     (|v| l > fp32's range: a limit of the un-normalised accumulation, not of the store).  The stored planes are the packing of the V row
     in the OUTPUT class, bit for bit: rounded where the output class is narrower (bf16 -> e4m3, split-bf16 -> F16C8 / split-f16), saturated at its
-    MAX where the input exceeds its range.  attn_kernel (3 / 4 waves: seq 70, 261, and 256 at head_dim 64 or two planes; attention.hip:870-871)
-    and attn_kernel_pp (seq 256, head_dim 96, one-plane inputs; attention.hip:868) through bd_attention, bd_attention_q (one third / half
-    of the rows as queries, compact output) and bd_attention_prefix without the prefix queries, whose rows keep their fill."""
-    batch, heads, npre = 2, 2, 5
+    MAX where the input exceeds its range.  attn_kernel (3 / 4 waves: seq 70, 261, and 256 at head_dim 64 or two planes) and
+    attn_kernel_pp (seq 256, head_dim 96, one-plane inputs) through bd_attention, bd_attention_q (one third / half of the rows as
+    queries, compact output) and bd_attention_prefix without the prefix queries, whose rows keep their fill: v_row_plans asserts the
+    form of each launch."""
+    batch, heads, npre = V_ROW_BATCH, V_ROW_HEADS, V_ROW_NPRE
     in_prec, code, kind = _PREFIX_VARIANTS[variant]
+    v_row_plans(variant, seq, hd)
     out_cls = in_prec if kind == "native" else _ATTN_OUT_CLS[kind]
     pid = getattr(_lib, code)
     lib = _lib.load()
@@ -822,7 +848,7 @@ def test_attention_stores_the_v_row(hip, variant, seq, hd):
     torch.cuda.synchronize()
     same(full, vrow, "bd_attention")
     # queries = one view of the sequence, compact output
-    q_len = {70: 35, 261: 87, 256: 128}[seq]
+    q_len = V_ROW_Q_LEN[seq]
     q_view = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
     part = alloc(batch * q_len)
     _lib.check(lib.bd_attention_q(_lib.ptr(t), qkv_plane, _lib.ptr(part), plane(part), batch, seq, heads, hd, ONE_HOT, _lib.ptr(q_view), q_len, pid,
@@ -887,6 +913,8 @@ def test_attention_normalisation_rounds_once_before_the_split(hip, variant, seq,
     pre = torch.from_numpy((acc * inv).astype(np.float32)) + 0.0          # fp32 product, as the kernel forms it
     assert np.float32(np.float64(acc[0, 12]) * np.float64(inv)) == pre[0, 12].item() and float(np.float64(acc[0, 12]) * np.float64(inv)) != pre[0, 12].item()
     out = operand.empty(out_cls, batch * seq, heads * hd, "cuda", zero=True)
+    plan = hip_ops.attention_plan("plain", prec=getattr(_lib, code), batch=batch, seq=seq, heads=heads, head_dim=hd)
+    assert (plan["kernel"], plan["planes"], plan["waves"], plan["head_dim"]) == ("tiled", 2, 3, hd), plan      # the split-bf16 epilogues of attn_kernel
     _lib.check(lib.bd_attention(_lib.ptr(t), t[0].numel(), _lib.ptr(out), out[0].numel(), batch, seq, heads, hd, ONE_HOT, getattr(_lib, code),
                                 _lib.stream()), "bd_attention")
     torch.cuda.synchronize()

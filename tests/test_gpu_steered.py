@@ -414,11 +414,17 @@ def _steered_case(batch, seq, hd, in_prec):
 def _attn_out(kind, in_prec, rows, cols):
     if kind == "native":
         return torch.full((rows, cols), 7.0, dtype=_lib.op_dtype(in_prec), device="cuda")
+    if kind == "fp8":
+        return torch.full((rows, cols), 7.0, device="cuda").to(torch.float8_e4m3fn)
     return torch.full((2, rows, cols), 7.0, dtype=torch.bfloat16 if kind == "planes" else torch.float16, device="cuda")
 
 
+def _attn_out_plane(o, kind):
+    return 0 if kind in ("native", "fp8") else o[0].numel()
+
+
 def _attn_read(o, kind):
-    if kind == "native":
+    if kind in ("native", "fp8"):
         return o.float().cpu()
     if kind == "f16c8":
         hi, lo, _ = hip_ops.f16c8_decode(o)
@@ -426,40 +432,88 @@ def _attn_read(o, kind):
     return (o[0].float() + o[1].float()).cpu()
 
 
-def _attn_assert(got, ref, eps, what):
-    err = (got - ref).abs().max().item()
-    assert err < 6 * eps * max(1.0, ref.abs().max().item()) + 2e-5, (what, err)
+def _attn_assert(got, ref, eps, what, kind="native"):
+    err = (got - ref).abs()
+    tol = 6 * eps * max(1.0, ref.abs().max().item()) + 2e-5
+    if kind == "fp8":       # on top of the pass's bound the e4m3 rounding of the result: 2^-4 relative (3 mantissa bits), 2^-10 below 2^-6
+        assert (err < tol + ref.abs() * 2.0 ** -4 + 2.0 ** -10).all(), (what, err.max().item())
+        return
+    assert err.max().item() < tol, (what, err.max().item())
 
 
-# (seq, head_dim) -> the kernel form bd_attention dispatches it to
-_FORMS = [
-    (261, 64),     # attn_kernel, 3 waves (96-query blocks), ragged tail of 5 keys (the peeled small-tail tile)
-    (257, 64),     # 3 waves, a tail tile with ONE live key
-    (250, 64),     # attn_kernel, 4 waves, ragged tail of 58 keys
-    (300, 96),     # attn_kernel hd 96, ragged tail of 44 keys
-    (321, 96),     # hd 96, a tail tile with one live key
-    (1000, 96),    # hd 96, 16 key tiles, ragged
-    (512, 96),     # attn_kernel_pp for single-pass classes (256-query blocks, whole tiles); split-bf16: attn_kernel NS = 2
-    (1536, 96),    # attn_kernel_pp, 24 key tiles (BETR's sequence at T = 6)
-]
+# (seq, head_dim) -> the kernel form bd_attention runs it on: (kernel, waves) of hip_ops.attention_plan, asserted before the launch.  The
+# split-bf16 classes have no ping-pong instance: where the one-plane classes take it they run attn_kernel on 4 waves.
+_FORMS = {
+    (261, 64): ("tiled", 3),     # attn_kernel, 3 waves (96-query blocks), ragged tail of 5 keys (the peeled small-tail tile)
+    (257, 64): ("tiled", 3),     # 3 waves, a tail tile with ONE live key
+    (250, 64): ("tiled", 4),     # attn_kernel, 4 waves, ragged tail of 58 keys
+    (300, 96): ("tiled", 4),     # attn_kernel hd 96, ragged tail of 44 keys
+    (321, 96): ("tiled", 4),     # hd 96, a tail tile with one live key
+    (1000, 96): ("tiled", 4),    # hd 96, 16 key tiles, ragged
+    (512, 96): ("pp", 8),        # attn_kernel_pp for single-pass classes (256-query blocks, whole tiles); split-bf16: attn_kernel NS = 2
+    (1536, 96): ("pp", 8),       # attn_kernel_pp, 24 key tiles (BETR's sequence at T = 6)
+}
+# The table rows (bd_attention_instance) that no other GPU test launches, one case each (tests/test_attention_plan_host.py counts them):
+# the ragged instance of attn_kernel for the one-plane classes -- bd_attention_varlen takes it where tokens_per_view is no multiple of
+# 256 -- on a packed batch of 1 and 2 views of 128 tokens.  Three of those classes have no entry in _VARIANTS; their result classes are
+# no less exact than their f16 / bf16 pass (split planes: ~2^-16 and ~2^-22), except e4m3 (_attn_assert).
+RAGGED = "ragged"
+_ROW_VARIANTS = {
+    **_VARIANTS,
+    "f16_out_bf16x3": ("fp16", "PREC_F16_OUT_BF16X3", "planes", 2.0 ** -11),
+    "f16_out_f16x3": ("fp16", "PREC_F16_OUT_F16X3", "planes_f16", 2.0 ** -11),
+    "bf16_out_fp8": ("bf16", "PREC_BF16_OUT_FP8", "fp8", 2.0 ** -8),
+}
+_ROW_CASES = [(v, RAGGED, 96) for v in ("bf16", "fp16", "f16_out_f16c8", "f16_out_bf16x3", "f16_out_f16x3", "bf16_out_fp8")]
+RAGGED_TPV, RAGGED_COUNTS = 128, (1, 2)
+_STEERED = [(v, seq, hd) for seq, hd in _FORMS for v in sorted(_VARIANTS)] + _ROW_CASES
 
 
-@pytest.mark.parametrize("variant", sorted(_VARIANTS))
-@pytest.mark.parametrize("seq,hd", _FORMS)
+def steered_plan(variant, seq, hd):
+    """The plan of a case of test_attention_online_softmax_steered, held against the form the case is about."""
+    in_prec, code, _, _ = _ROW_VARIANTS[variant]
+    heads, pid = len(PATTERNS), getattr(_lib, code)
+    if seq == RAGGED:
+        plan = hip_ops.attention_plan("varlen", prec=pid, batch=len(RAGGED_COUNTS), n_views=sum(RAGGED_COUNTS), max_views=max(RAGGED_COUNTS),
+                                      tokens_per_view=RAGGED_TPV, heads=heads, head_dim=hd)
+        assert (plan["kernel"], plan["waves"], plan["vl"], plan["planes"]) == ("tiled", 4, True, 1), plan
+        return plan
+    plan = hip_ops.attention_plan("plain", prec=pid, batch=1, seq=seq, heads=heads, head_dim=hd)
+    want = ("tiled", 4) if in_prec == "bf16x3" and _FORMS[seq, hd][0] == "pp" else _FORMS[seq, hd]
+    assert (plan["kernel"], plan["waves"], plan["head_dim"], plan["vl"]) == (*want, hd, False), plan
+    return plan
+
+
+@pytest.mark.parametrize("variant,seq,hd", _STEERED, ids=[f"{seq}-{hd}-{v}" for v, seq, hd in _STEERED])
 def test_attention_online_softmax_steered(hip, variant, seq, hd):
     """Online softmax under steered logits (one pattern per head, _steer): the rescale branch taken in every tile, never taken, taken on
-    the last key of a ragged tail, an alpha that underflows to 0, equal maxima, all-zero logits -- against fp64 torch."""
-    in_prec, code, kind, eps = _VARIANTS[variant]
-    batch, heads = 1, len(PATTERNS)
-    t, ref = _steered_case(batch, seq, hd, in_prec)
-    out = _attn_out(kind, in_prec, batch * seq, heads * hd)
+    the last key of a ragged tail, an alpha that underflows to 0, equal maxima, all-zero logits -- against fp64 torch.  Every case
+    asserts through the plan that it runs the kernel form it is about (_FORMS, _ROW_CASES)."""
+    in_prec, code, kind, eps = _ROW_VARIANTS[variant]
+    heads = len(PATTERNS)
+    steered_plan(variant, seq, hd)
     lib = _lib.load()
-    _lib.check(lib.bd_attention(_lib.ptr(t), t[0].numel() if in_prec == "bf16x3" else 0, _lib.ptr(out), 0 if kind == "native" else out[0].numel(),
-                                batch, seq, heads, hd, hd ** -0.5, getattr(_lib, code), _lib.stream()), "bd_attention")
+    split = in_prec == "bf16x3"
+    if seq == RAGGED:                                    # every sample its own steered sequence, packed back to back
+        parts = [_steered_case(1, c * RAGGED_TPV, hd, in_prec) for c in RAGGED_COUNTS]
+        t = torch.cat([p[0] for p in parts], 1 if split else 0).contiguous()
+        ref = torch.cat([p[1] for p in parts], 1)
+        rows = ref.shape[1]
+        out = _attn_out(kind, in_prec, rows, heads * hd)
+        vs = torch.tensor(_lib.view_starts(RAGGED_COUNTS), dtype=torch.int32).cuda()
+        _lib.check(lib.bd_attention_varlen(_lib.ptr(t), t[0].numel() if split else 0, _lib.ptr(out), _attn_out_plane(out, kind), _lib.ptr(vs),
+                                           len(RAGGED_COUNTS), sum(RAGGED_COUNTS), max(RAGGED_COUNTS), RAGGED_TPV, heads, hd, hd ** -0.5, None,
+                                           getattr(_lib, code), _lib.stream()), "bd_attention_varlen")
+    else:
+        t, ref = _steered_case(1, seq, hd, in_prec)
+        rows = seq
+        out = _attn_out(kind, in_prec, rows, heads * hd)
+        _lib.check(lib.bd_attention(_lib.ptr(t), t[0].numel() if split else 0, _lib.ptr(out), _attn_out_plane(out, kind),
+                                    1, seq, heads, hd, hd ** -0.5, getattr(_lib, code), _lib.stream()), "bd_attention")
     torch.cuda.synchronize()
-    got = _attn_read(out, kind).reshape(batch, seq, heads, hd)
+    got = _attn_read(out, kind).reshape(1, rows, heads, hd)
     for h, pat in enumerate(PATTERNS):
-        _attn_assert(got[:, :, h], ref[:, :, h], eps, (variant, seq, hd, pat))
+        _attn_assert(got[:, :, h], ref[:, :, h], eps, (variant, seq, hd, pat), kind)
 
 
 @pytest.mark.parametrize("variant", sorted(_VARIANTS))

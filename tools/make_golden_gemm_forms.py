@@ -29,13 +29,11 @@ from __future__ import annotations
 import itertools
 import json
 import os
-import re
-import subprocess
 import sys
 import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = "boxdreamer_amd/csrc"
+from golden_forms import ROOT, build_host_only, extract, kernel_names, sh, template_args
+
 FILES = ["gemm.hip", "gemm_f16c8.hip", "gemm_common.h", "bd_common.h"]
 
 # bd_gemm_args, in declaration order: (name, kind) with kind p = pointer, l = int64, i = int, f = float (not varied: never read by a dispatcher)
@@ -137,69 +135,28 @@ int main() {
 """
 
 
-def sh(cmd, **kw):
-    r = subprocess.run(cmd, capture_output=True, text=True, **kw)
-    if r.returncode != 0:
-        raise SystemExit(f"{' '.join(cmd)}\n{r.stderr}")
-    return r.stdout
-
-
 def build_recorder(rev: str, tmp: str) -> str:
-    csrc = os.path.join(tmp, *CSRC.split("/"))                  # the repository's layout: bd_common.h includes ../../include/
-    os.makedirs(csrc)
-    os.makedirs(os.path.join(tmp, "include"))
-    for f in FILES:
-        src = sh(["git", "-C", ROOT, "show", f"{rev}:{CSRC}/{f}"])
-        if f == "gemm_common.h":
-            assert src.count("inline int cu_count() {") == 1
-            src = src.replace("inline int cu_count() {", "inline int cu_count() { return ::g_cus; }\ninline int cu_count_of_device() {")
-        open(os.path.join(csrc, f), "w").write(src)
-    open(os.path.join(tmp, "include", "boxdreamer_hip.h"), "w").write(sh(["git", "-C", ROOT, "show", f"{rev}:include/boxdreamer_hip.h"]))
-    open(os.path.join(tmp, "prelude.h"), "w").write(PRELUDE)
+    def edit(f, src):
+        if f != "gemm_common.h":
+            return src
+        assert src.count("inline int cu_count() {") == 1
+        return src.replace("inline int cu_count() {", "inline int cu_count() { return ::g_cus; }\ninline int cu_count_of_device() {")
+
+    csrc = extract(rev, tmp, FILES, edit)
     cast = {"p": "(decltype(a.%s))(uintptr_t)", "l": "(int64_t)", "i": "(int)"}
     reads = "\n".join(f"        a.{n} = {cast[t] % n if t == 'p' else cast[t]}v[k++];" for n, t in FIELDS)
-    open(os.path.join(tmp, "driver.cpp"), "w").write(DRIVER % reads)
-    hipcc = os.environ.get("HIPCC", "hipcc")
-    exe = os.path.join(tmp, "recorder")
-    objs = []
-    for src in (os.path.join(csrc, "gemm.hip"), os.path.join(csrc, "gemm_f16c8.hip"), os.path.join(tmp, "driver.cpp")):
-        objs.append(src + ".o")
-        sh([hipcc, "--cuda-host-only", "-O1", "-std=c++17", "-I", os.path.join(tmp, "include"), "-include", os.path.join(tmp, "prelude.h"),
-            "-x", "hip", "-c", src, "-o", objs[-1]])
-    # a host-only object still refers to the device code bundle it would register: give each an empty one (nothing is ever launched)
-    fatbins = sorted({ln.split()[-1] for o in objs for ln in sh(["nm", "-u", o]).splitlines() if "__hip_fatbin_" in ln})
-    open(os.path.join(tmp, "fatbins.c"), "w").write("".join(f"const char {n}[64] = {{0}};\n" for n in fatbins))
-    sh([hipcc, "-no-pie", *objs, os.path.join(tmp, "fatbins.c"), "-o", exe])
-    return exe
-
-
-def kernel_names(exe: str) -> dict:
-    """address (hex, as the recorder prints it) -> mangled name of every gemm kernel symbol of the recorder (not position-independent)."""
-    names = {}
-    for line in sh(["nm", exe]).splitlines():
-        addr, _, name = line.partition(" ")[0], None, line.split(" ")[-1]
-        if "gemm_kernel_" in name and addr:
-            names.setdefault(format(int(addr, 16), "x"), name)
-    return names
+    return build_host_only(tmp, [os.path.join(csrc, "gemm.hip"), os.path.join(csrc, "gemm_f16c8.hip")], PRELUDE, DRIVER % reads)
 
 
 FAMILIES = {"gemm_kernel_pc": 1, "gemm_kernel_glds": 2, "gemm_kernel_pc_f16c8": 3}
 KEY_LEN = 13
-# Itanium mangling of the template arguments these kernels take: __bf16, _Float16, fp8e4 (global), int, bool
-TOKEN = re.compile(r"(DF16b)|(DF16_)|(5fp8e4)|Li(n?\d+)E|Lb([01])E")
 
 
 def parse_kernel(mangled: str):
-    """`_ZN12_GLOBAL__N_1..14gemm_kernel_pcIDF16bLi1ELi64E...EEv12bd_gemm_args` -> (family, template arguments as integers, zero-padded)."""
-    m = re.search(r"\d+(gemm_kernel_[a-z0-9_]+?)I((?:DF16b|DF16_|5fp8e4|Lin?\d+E|Lb[01]E)+)E", mangled)
-    if not m:
-        raise SystemExit(f"cannot parse kernel name: {mangled}")
-    key = []
-    for t in TOKEN.finditer(m.group(2)):
-        bf, f16, f8, i, b = t.groups()
-        key.append(0 if bf else 1 if f16 else 2 if f8 else int(b) if b is not None else int(i.replace("n", "-")))
+    """A mangled instance name -> (family, template arguments as integers, zero-padded)."""
+    name, key = template_args(mangled, r"gemm_kernel_[a-z0-9_]+?")
     assert len(key) <= KEY_LEN
-    return FAMILIES[m.group(1)], key + [0] * (KEY_LEN - len(key))
+    return FAMILIES[name], key + [0] * (KEY_LEN - len(key))
 
 
 def case_fields(variant: dict, N: int, K: int, M: int) -> dict:
@@ -225,7 +182,7 @@ def main():
     with tempfile.TemporaryDirectory() as tmp:
         exe = build_recorder(rev, tmp)
         res = sh([exe], input="\n".join(lines) + "\n").splitlines()
-        names = kernel_names(exe)
+        names = kernel_names(exe, "gemm_kernel_")
     assert len(res) == len(lines), (len(res), len(lines))
     kernels, outcomes, entries, groups = {}, {}, {}, []
     it = iter(res)
