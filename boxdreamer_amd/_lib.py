@@ -164,10 +164,11 @@ EXPORTS = [
     "bd_decoder_forward_entry_ragged", "bd_solve_pnp_wave",
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
     "bd_round_sources", "bd_pose_select_rows",
-    "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host",
+    "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host", "bd_stream_select_rows",
     "bd_gemm_plan", "bd_gemm_instance", "bd_attention_plan", "bd_attention_instance",
 ]
 STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
+STREAM_SELECT_DINO, STREAM_SELECT_TRACK = 0, 1         # BD_STREAM_SELECT_*: bd_stream_select_rows' rule
 
 _lib = None
 
@@ -268,6 +269,7 @@ def load() -> C.CDLL:
     lib.bd_stream_windows_host.argtypes = [vp, vp, C.c_double, i, vp, vp, i]
     lib.bd_stream_results.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, vp]
     lib.bd_stream_results_host.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i]
+    lib.bd_stream_select_rows.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, vp]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:

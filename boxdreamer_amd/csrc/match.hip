@@ -11,11 +11,11 @@
 // second time from L2) plus a dot product per pair, instead of B*N bmm's of (L x D) x (D x L).
 // Foreground = luminance(0.299 R + 0.587 G + 0.114 B) > threshold at the nearest-resized pixel of the patch grid
 // (F.interpolate(mode="nearest"): source index floor(i * H / g)).
-#include "bd_common.h"
+#include "select_common.h"
 
 namespace {
 
-constexpr int MAXL = 1024;
+constexpr int MAXL = SEL_MAXN;
 constexpr float BACKGROUND = -1.0f;      // inv[] entry of a background patch (a foreground patch's inverse norm lies in [0, 1e12])
 
 // Every product and sum rounded on its own, as the reference's fp32 tensor expression rounds them.  Contracted into v_fmac_f32
@@ -69,26 +69,6 @@ __global__ __launch_bounds__(256) void match_sums_kernel(const float* __restrict
     if (tid == 0) counts[v] = (float)cnt;
 }
 
-// The score of one (query, reference) pair from the two views' summaries, by ONE wave; every kernel that scores a pair calls these two,
-// so a pair's score has the same bits whichever entry produced it (bd_dino_match_scores, bd_match_select_rows).
-__device__ __forceinline__ float pair_dot(const float* __restrict__ sq, const float* __restrict__ sr, int D, int lane) {
-    float dot = 0.f;
-    for (int d = lane; d < D; d += 64) dot = fmaf(sq[d], sr[d], dot);
-    return wave_sum(dot);
-}
-
-__device__ __forceinline__ float pair_score(float dot, float cq, float cr, int L) {
-    const float ll = (float)L * (float)L;
-    const float pairs = cq * cr;
-    // a view without foreground: the reference fills EVERY pair with -1e4, so non-finite features of the other view (NaN * 0
-    // in the dot product) do not reach the score
-    if (pairs == 0.f) dot = 0.f;
-    const float invalid = ll - pairs;
-    float m = (dot - 1e4f * invalid) / ll;
-    if (!(m == m) || fabsf(m) == INFINITY) m = 0.f;            // nan_to_num(0, 0, 0)
-    return m;
-}
-
 // one wave per (sample, reference): references are the views != query_view[b], in view order
 __global__ __launch_bounds__(64) void match_scores_kernel(const float* __restrict__ sums, const float* __restrict__ counts,
                                                            const int32_t* __restrict__ query_view, int T, int L, int D,
@@ -109,34 +89,19 @@ __global__ __launch_bounds__(256) void topk_mask_kernel(const float* __restrict_
     __shared__ float val[MAXL];
     __shared__ float wv[4];
     __shared__ int wi[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x, tid = threadIdx.x;
     for (int i = tid; i < N; i += 256) { val[i] = scores[(int64_t)b * N + i]; mask[(int64_t)b * N + i] = 0; }
     __syncthreads();
     float pv = INFINITY;
     int pi = -1;
     for (int round = 0; round < k; ++round) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < N; i += 256) {
-            const float v = val[i];
-            const bool after = v < pv || (v == pv && i > pi);
-            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { wv[wid] = bv; wi[wid] = bi; }
-        __syncthreads();
-        bv = wv[0]; bi = wi[0];
-        for (int w = 1; w < 4; ++w) if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
+        float bv; int bi;
+        topk_round(val, N, pv, pi, wv, wi, bv, bi);
         if (tid == 0 && bi < N) mask[(int64_t)b * N + bi] = 1;
         pv = bv; pi = bi;
         __syncthreads();                    // wv / wi are rewritten in the next round
     }
 }
-
-constexpr int32_t NO_VIEW = 0x7fffffff;  // a `src` entry bd_gather_view_rows skips (outside every bank): its view keeps its bytes
 
 // Dense-reference mode over a bank of view summaries: score, select and compact in ONE launch, one workgroup (4 waves) per sample.
 // Sample b's references are the bank rows rows[b][0 .. n_refs[b]); its query is fresh view b (q_sums / q_counts).
@@ -155,61 +120,14 @@ __global__ __launch_bounds__(256) void match_select_rows_kernel(const float* __r
     __shared__ int pick[MAXL];
     __shared__ float wv[4];
     __shared__ int wi[4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int b = blockIdx.x;
     int N = n_refs[b];
     N = N < 0 ? 0 : (N > N_max ? N_max : N);
     const int32_t* row = rows + (int64_t)b * N_max;
-    const float* sq = q_sums + (int64_t)b * D;
-    const float cq = q_counts[b];
-    for (int i = wid; i < N_max; i += 4) {
-        float m = -INFINITY;
-        const int r = i < N ? row[i] : -1;                  // (wave-uniform)
-        if (r >= 0 && r < R) m = pair_score(pair_dot(sq, bank_sums + (int64_t)r * D, D, lane), cq, bank_counts[r], L);
-        if (lane == 0) { val[i] = m; scores[(int64_t)b * N_max + i] = m; }
-    }
+    score_slots(bank_sums, bank_counts, R, q_sums + (int64_t)b * D, q_counts[b], row, N, N_max, L, D, val, scores + (int64_t)b * N_max);
     __syncthreads();
-    float pv = INFINITY;
-    int pi = -1, n_picked = 0;
-    for (int round = 0; round < k; ++round) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int i = tid; i < N; i += 256) {
-            const float v = val[i];
-            const bool after = v < pv || (v == pv && i > pi);
-            if (after && (v > bv || (v == bv && i < bi))) { bv = v; bi = i; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { wv[wid] = bv; wi[wid] = bi; }
-        __syncthreads();
-        bv = wv[0]; bi = wi[0];
-        for (int w = 1; w < 4; ++w) if (wv[w] > bv || (wv[w] == bv && wi[w] < bi)) { bv = wv[w]; bi = wi[w]; }
-        if (bi >= N) break;                                 // (block-uniform) fewer than k slots: nothing is left to pick
-        if (tid == 0) pick[round] = bi;
-        n_picked = round + 1;
-        pv = bv; pi = bi;
-        __syncthreads();                    // wv / wi are rewritten in the next round
-    }
-    __syncthreads();
-    // the picks are distinct slots: a pick's place in ascending order is the number of smaller picks
-    int32_t* out_sel = sel + (int64_t)b * k;
-    int32_t* out_src = src + (int64_t)b * (k + 1);
-    for (int j = tid; j < k; j += 256) {
-        if (j < n_picked) {
-            const int p = pick[j];
-            int rank = 0;
-            for (int m = 0; m < n_picked; ++m) rank += pick[m] < p;
-            const int r = row[p];
-            out_sel[rank] = p;
-            out_src[rank] = r >= 0 && r < R ? r : NO_VIEW;
-        } else {
-            out_sel[j] = -1;
-            out_src[j] = NO_VIEW;
-        }
-    }
-    if (tid == 0) out_src[k] = -(b + 1);
+    const int n_picked = topk_picks(val, N, k, pick, wv, wi);
+    compact_picks(pick, n_picked, k, row, R, b, sel + (int64_t)b * k, src + (int64_t)b * (k + 1));
 }
 
 }  // namespace

@@ -9,20 +9,11 @@
 // Both follow bd_match_select_rows' conventions (match.hip): one workgroup per sample, no atomics, every sum in index order (a
 // sample's bits do not depend on the batch), arguments checked before any launch, inconsistent device data reads and writes nothing
 // out of bounds.
-#include "bd_common.h"
+#include "select_common.h"
 
 namespace {
 
-constexpr int MAXK = 1024;
-constexpr int32_t NO_VIEW = 0x7fffffff;  // a `src` entry bd_gather_view_rows / bd_assemble_entry_tokens skip (match.hip)
-
-// The bank row of candidate position c of one sample: rows[cand[c]], NO_VIEW when the slot or the row is out of range.
-__device__ __forceinline__ int32_t candidate_row(const int32_t* __restrict__ row, const int32_t* __restrict__ cand, int c, int N_max, int R) {
-    const int slot = cand[c];
-    if (slot < 0 || slot >= N_max) return NO_VIEW;
-    const int r = row[slot];
-    return r >= 0 && r < R ? r : NO_VIEW;
-}
+constexpr int MAXK = SEL_MAXN;
 
 // one workgroup (4 waves) per sample; the sample's k resolved rows go through LDS once, every round reads them from there
 __global__ __launch_bounds__(256) void round_sources_kernel(const int32_t* __restrict__ rows, const int32_t* __restrict__ cand, int R,
@@ -53,35 +44,8 @@ __global__ __launch_bounds__(256) void round_sources_kernel(const int32_t* __res
     }
 }
 
-// The order bd_pose_select_rows ranks by, on the stored fp32 distance: numbers before NaNs, smaller before larger (+inf an ordinary
-// value), equal ones -- and NaNs among themselves -- by position.
-__device__ __forceinline__ bool ranks_before(float va, int pa, float vb, int pb) {
-    const bool na = va != va, nb = vb != vb;
-    if (na != nb) return nb;
-    if (na || va == vb) return pa < pb;
-    return va < vb;
-}
-
-// The distance in fp64 from the fp32 inputs, every product and sum rounded on its own in the order the header states (the nine
-// products of the trace are exact in fp64; the squares of the translation are not, so nothing here may be contracted).
-__device__ __forceinline__ double pose_distance(const float* __restrict__ p, const float* __restrict__ g) {
-#pragma clang fp contract(off)
-    double tr = 0.0;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) tr = tr + (double)p[i * 4 + j] * (double)g[i * 4 + j];
-    double x = (tr - 1.0) / 2.0;
-    x = x < -1.0 ? -1.0 : (x > 1.0 ? 1.0 : x);          // (comparisons, not fmin / fmax: a NaN stays a NaN, as in torch.clamp)
-    double ss = 0.0;
-    for (int i = 0; i < 3; ++i) {
-        const double d = (double)p[i * 4 + 3] - (double)g[i * 4 + 3];
-        ss = ss + d * d;
-    }
-    return acos(x) + sqrt(ss);
-}
-
-// one workgroup (4 waves) per sample.  A candidate's rank is the number of valid candidates that rank before it: k reads of the LDS
-// table per candidate (every lane reads the same word: a broadcast), no reduction and no barrier inside a loop; at k = 1024 that is
-// 4096 compares per thread, at the k of a real database (20 .. 64) a few dozen.
+// one workgroup (4 waves) per sample: distances, rank by counting, compaction (select_common.h: candidate_distance, choose_nearest,
+// compact_chosen)
 __global__ __launch_bounds__(256) void pose_select_rows_kernel(const float* __restrict__ bank_poses, int R, const float* __restrict__ pred,
                                                                 const int32_t* __restrict__ rows, const int32_t* __restrict__ cand,
                                                                 int N_max, int k, int fk, float* __restrict__ dist,
@@ -95,31 +59,15 @@ __global__ __launch_bounds__(256) void pose_select_rows_kernel(const float* __re
     const float* p = pred + (int64_t)b * 16;
     for (int c = tid; c < k; c += 256) {
         const int32_t r = candidate_row(row, cd, c, N_max, R);
-        const float d = r == NO_VIEW ? INFINITY : (float)pose_distance(p, bank_poses + (int64_t)r * 16);
+        const float d = candidate_distance(p, bank_poses, r);
         tab[c] = r;
         val[c] = d;
         dist[(int64_t)b * k + c] = d;
     }
     __syncthreads();
-    for (int c = tid; c < k; c += 256) {
-        int rank = 0;
-        const float v = val[c];
-        for (int m = 0; m < k; ++m) rank += tab[m] != NO_VIEW && ranks_before(val[m], m, v, c);
-        chosen[c] = tab[c] != NO_VIEW && rank < fk;
-    }
+    choose_nearest(val, tab, k, fk, chosen);
     __syncthreads();
-    // output j is the j-th chosen position in ascending order: each output finds its own (no two threads write one word)
-    int32_t* out_pos = fine_pos + (int64_t)b * fk;
-    int32_t* out_src = src + (int64_t)b * (fk + 1);
-    for (int j = tid; j < fk; j += 256) {
-        int seen = 0, at = -1;
-        for (int c = 0; c < k && at < 0; ++c) {
-            if (chosen[c]) { if (seen == j) at = c; ++seen; }
-        }
-        out_pos[j] = at;
-        out_src[j] = at >= 0 ? tab[at] : NO_VIEW;
-    }
-    if (tid == 0) out_src[fk] = -(b + 1);
+    compact_chosen(chosen, tab, k, fk, b, fine_pos + (int64_t)b * fk, src + (int64_t)b * (fk + 1));
 }
 
 }  // namespace

@@ -10,7 +10,11 @@
 // arithmetic is written once (__host__ __device__) and runs on the host as bd_stream_*_host, the twin the tests compare the
 // kernels against.  Floating-point contraction is OFF in it: hipcc -O3 would turn a * b - c * d into an FMA, which rounds once
 // where torch's separate fp64 kernels round twice.
-#include "bd_common.h"
+//   * bd_stream_select_rows: between the encoder and the decoder of a step whose session owns a reference DATABASE per object
+//     (PoseStream(select_k=...)): which k views the decoder reads this frame, decided on the device and written as the decoder's
+//     source table, so the captured graph replays unchanged while the references change.  One workgroup per object; the arithmetic
+//     and the rankings are bd_match_select_rows' and bd_pose_select_rows' own (select_common.h).
+#include "select_common.h"
 #include <cmath>
 
 namespace {
@@ -132,6 +136,58 @@ __global__ __launch_bounds__(SW_LANES) void stream_results_kernel(const float* _
                   bbox_3d + (int64_t)i * 24, out_size, rows + (int64_t)i * BD_STREAM_ROW_FLOATS);
 }
 
+// One workgroup (4 waves) per tracked object: both value arrays, the rule, then the ranking of the rule that applies.
+//   scores   bd_match_select_rows' (score_slots): the appearance of every database slot against this frame's query
+//   dist     bd_pose_select_rows' with cand = the identity over [0, n_refs[b]): the distance of every slot's pose to the last pose
+//   rule     pose when rule == TRACK, force[b] == 0, the last row's ok == 1 and its rms <= max_rms_px (a comparison: a NaN rms
+//            fails it); appearance otherwise.  Every thread reads the same four words: the decision is block-uniform.
+//   ranking  topk_picks + compact_picks (appearance) or choose_nearest + compact_chosen with k = N_max, fk = k (pose)
+// n_refs[b] is clamped into [0, N_max] and `rows` is not read past it; a row outside [0, R) is no view under either rule.
+__global__ __launch_bounds__(256) void stream_select_rows_kernel(const float* __restrict__ sums, const float* __restrict__ counts,
+                                                                  const float* __restrict__ poses, int R, const float* __restrict__ q_sums,
+                                                                  const float* __restrict__ q_counts, const float* __restrict__ prev_rows,
+                                                                  const int32_t* __restrict__ rows, const int32_t* __restrict__ n_refs,
+                                                                  const int32_t* __restrict__ force, int N_max, int L, int D, int k, int rule,
+                                                                  float max_rms_px, float* __restrict__ scores, float* __restrict__ dist,
+                                                                  int32_t* __restrict__ used, int32_t* __restrict__ sel,
+                                                                  int32_t* __restrict__ src) {
+    __shared__ float val[SEL_MAXN];             // scores
+    __shared__ float dval[SEL_MAXN];            // distances
+    __shared__ int32_t tab[SEL_MAXN];           // the slot's private row, NO_VIEW: no view
+    __shared__ int pick[SEL_MAXN];
+    __shared__ unsigned char chosen[SEL_MAXN];
+    __shared__ float wv[4];
+    __shared__ int wi[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int N = n_refs[b];
+    N = N < 0 ? 0 : (N > N_max ? N_max : N);
+    const int32_t* row = rows + (int64_t)b * N_max;
+    const float* prev = prev_rows + (int64_t)b * BD_STREAM_ROW_FLOATS;
+    const bool by_pose = rule == BD_STREAM_SELECT_TRACK && force[b] == 0 && prev[17] == 1.0f && prev[16] <= max_rms_px;
+    score_slots(sums, counts, R, q_sums + (int64_t)b * D, q_counts[b], row, N, N_max, L, D, val, scores + (int64_t)b * N_max);
+    if (poses) {
+        for (int c = tid; c < N_max; c += 256) {
+            const int32_t r = c < N ? slot_row(row, c, N_max, R) : NO_VIEW;
+            const float d = candidate_distance(prev, poses, r);
+            tab[c] = r;
+            dval[c] = d;
+            dist[(int64_t)b * N_max + c] = d;
+        }
+    }
+    if (tid == 0) used[b] = by_pose ? 1 : 0;
+    __syncthreads();
+    int32_t* out_sel = sel + (int64_t)b * k;
+    int32_t* out_src = src + (int64_t)b * (k + 1);
+    if (by_pose) {                                          // (block-uniform; poses != NULL: checked before the launch)
+        choose_nearest(dval, tab, N_max, k, chosen);
+        __syncthreads();
+        compact_chosen(chosen, tab, N_max, k, b, out_sel, out_src);
+    } else {
+        const int n_picked = topk_picks(val, N, k, pick, wv, wi);
+        compact_picks(pick, n_picked, k, row, R, b, out_sel, out_src);
+    }
+}
+
 int windows_args(const void* a, const void* b, const void* c, const void* d, int out_size, int n) {
     if (!a || !b || !c || !d) return BD_ERR_NULL;
     if (n < 0 || n > SW_MAX_N || out_size < 1) return BD_ERR_SHAPE;
@@ -182,5 +238,20 @@ extern "C" int bd_stream_results_host(const float* poses, const float* rms_px, c
     for (int i = 0; i < n; ++i)
         stream_result(poses + (int64_t)i * 16, rms_px[i], kp_px + (int64_t)i * 16, windows + (int64_t)i * 4, K + (int64_t)i * 9,
                       bbox_3d + (int64_t)i * 24, out_size, rows + (int64_t)i * BD_STREAM_ROW_FLOATS);
+    return BD_OK;
+}
+
+extern "C" int bd_stream_select_rows(const float* sums, const float* counts, const float* poses, int R, const float* q_sums,
+                                     const float* q_counts, const float* prev_rows, const int32_t* rows, const int32_t* n_refs,
+                                     const int32_t* force, int B, int N_max, int L, int D, int k, int rule, float max_rms_px,
+                                     float* scores, float* dist, int32_t* used, int32_t* sel, int32_t* src, void* stream) {
+    if (!sums || !counts || !q_sums || !q_counts || !prev_rows || !rows || !n_refs || !force || !scores || !used || !sel || !src) return BD_ERR_NULL;
+    if (rule != BD_STREAM_SELECT_DINO && rule != BD_STREAM_SELECT_TRACK) return BD_ERR_SHAPE;
+    if (!poses && rule != BD_STREAM_SELECT_DINO) return BD_ERR_NULL;
+    if (poses && !dist) return BD_ERR_NULL;
+    if (B <= 0 || R < 0 || N_max <= 0 || N_max > SEL_MAXN || k <= 0 || k > N_max || L <= 0 || D <= 0) return BD_ERR_SHAPE;
+    hipLaunchKernelGGL(stream_select_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, sums, counts, poses, R, q_sums, q_counts,
+                       prev_rows, rows, n_refs, force, N_max, L, D, k, rule, max_rms_px, scores, dist, used, sel, src);
+    BD_CHECK_LAUNCH();
     return BD_OK;
 }

@@ -506,6 +506,49 @@ def stream_results(poses, rms_px, kp_px, windows, K, bbox_3d, out_size=224, rows
     return rows
 
 
+def stream_select_rows(sums, counts, poses, n_rows, q_sums, q_counts, prev_rows, rows, n_refs, force, L, k, rule, max_rms_px=float("inf"),
+                       scores=None, dist=None, used=None, sel=None, src=None):
+    """bd_stream_select_rows: one launch -> (scores fp32 (B, N_max), dist fp32 (B, N_max) or None, used int32 (B,), sel int32 (B, k),
+    src int32 (B * (k + 1),)).  sums fp32 (>= n_rows, D) / counts fp32 (>= n_rows,) / poses fp32 (>= n_rows, 4, 4) or None (rule
+    _lib.STREAM_SELECT_DINO only; dist is then None): the database views' match summaries and poses, n_rows of them in use; q_sums (B, D)
+    / q_counts (B,): match_view_sums of the query crops; prev_rows fp32 (B, 66): the previous step's result rows; rows int32
+    (B, N_max) / n_refs int32 (B,) / force int32 (B,): device tables.  The outputs are written into the given tensors, allocated when
+    None."""
+    lib = _lib.load()
+    B, N_max = (int(x) for x in rows.shape) if isinstance(rows, torch.Tensor) and rows.dim() == 2 else (-1, -1)
+    k, n_rows = int(k), int(n_rows)
+    D = int(q_sums.shape[1]) if isinstance(q_sums, torch.Tensor) and q_sums.dim() == 2 else -1
+    _stream_dev(rows, (B, N_max), torch.int32, "rows")
+    _stream_dev(n_refs, (B,), torch.int32, "n_refs")
+    _stream_dev(force, (B,), torch.int32, "force")
+    _stream_dev(q_sums, (B, D), torch.float32, "q_sums")
+    _stream_dev(q_counts, (B,), torch.float32, "q_counts")
+    _stream_dev(prev_rows, (B, _lib.STREAM_ROW_FLOATS), torch.float32, "prev_rows")
+    for t, tail, name in ((sums, (D,), "sums"), (counts, (), "counts"), (poses, (4, 4), "poses")):
+        if t is None and name == "poses":
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape[1:]) != tail
+                or t.shape[0] < n_rows):
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of shape (>= {n_rows},) + {tail}, got "
+                             f"{(tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    dev = rows.device
+    kk = max(k, 0)
+    outs = []
+    for t, shape, dtype, name in ((scores, (B, N_max), torch.float32, "scores"), (dist, (B, N_max), torch.float32, "dist"),
+                                  (used, (B,), torch.int32, "used"), (sel, (B, kk), torch.int32, "sel"),
+                                  (src, (B * (kk + 1),), torch.int32, "src")):
+        if name == "dist" and poses is None:
+            outs.append(None)
+        else:
+            outs.append(torch.empty(shape, dtype=dtype, device=dev) if t is None else _stream_dev(t, shape, dtype, name))
+    scores, dist, used, sel, src = outs
+    _lib.same_device(sums, counts, poses, q_sums, q_counts, prev_rows, rows, n_refs, force, scores, dist, used, sel, src)
+    check(lib.bd_stream_select_rows(ptr(sums), ptr(counts), ptr(poses), n_rows, ptr(q_sums), ptr(q_counts), ptr(prev_rows), ptr(rows),
+                                    ptr(n_refs), ptr(force), B, N_max, int(L), D, k, int(rule), float(max_rms_px), ptr(scores), ptr(dist),
+                                    ptr(used), ptr(sel), ptr(src), stream()), "bd_stream_select_rows")
+    return scores, dist, used, sel, src
+
+
 def _host32(a, shape, dtype):
     import numpy as np
     a = np.ascontiguousarray(a.numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)

@@ -17,11 +17,31 @@ session -- B tracked objects, each with its T - 1 banked references, a fixed fra
 `step()` copies the frame, the detector boxes and K into static buffers, replays the graph, enqueues ONE D2H of the result rows into
 a pinned buffer and waits for that copy's event.  Nothing is carried from frame to frame.
 
+With `select_k=k` each object's `ref_rows` is its whole DATABASE of banked views (up to 1024, lengths may differ) and the k views the
+decoder reads are chosen on the device every frame, inside the same captured graph (T = k + 1):
+
+    bank = RefFeatureBank(model.rgb_encoder, decoder=model.decoder, match_threshold=0.05, keep_poses=True)
+    rows = bank.add(db_images, bbox_feat=db_heatmaps, poses=db_poses)
+    s = PoseStream(model, bank, [rows.tolist()], bbox_3d, frame_shape=(480, 640), select_k=5, select="track", max_rms_px=4.0)
+
+    ... encoder -> bd_match_view_sums (the B query crops) -> bd_stream_select_rows (writes the decoder's source table) ->
+    BETR.forward_entry -> ...
+
+`select="dino"` chooses by appearance, the dense-reference mode's DINO filter (bd_match_select_rows' scores and ranking); nothing is
+carried from frame to frame there either.  `select="track"` chooses the k views nearest to the LAST frame's pose
+(bd_pose_select_rows' distance and ranking, the dense mode's fine level with the last pose standing in for the coarse pose) while
+that pose is trustworthy -- the last row's ok == 1 and its rms_px <= max_rms_px -- and by appearance otherwise: on the first step,
+after `reset()`, after a failed or poor solve, and for the objects `step(..., relocalise=...)` names.  A "track" step therefore
+DEPENDS on the previous step's result rows: that is the one thing such a session carries from frame to frame.
+
 Limits: an entry-token bank only; the same T for every sample; a fixed frame shape and frame count; the encoder and the decoder are
 frozen while the session lives (a larger eager batch, .to() or a checkpoint load raises; `del` the session first).
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 from . import _lib, calibrate, hip_ops
@@ -58,6 +78,92 @@ def _ref_rows(ref_rows, bank_len: int):
     return rows, B, R + 1
 
 
+SELECT_RULES = {"dino": _lib.STREAM_SELECT_DINO, "track": _lib.STREAM_SELECT_TRACK}
+MAX_DATABASE = 1024         # slots one bd_stream_select_rows workgroup ranks
+
+
+def _ref_database(ref_rows, bank_len: int, k):
+    """`ref_rows` of a session that selects (host ints: B lists of bank rows, lengths may differ) -> (B lists, n_refs, N_max), validated
+    against the bank's length and `select_k`."""
+    if isinstance(ref_rows, torch.Tensor):
+        if ref_rows.device.type != "cpu" or ref_rows.dtype.is_floating_point or ref_rows.dtype == torch.bool or ref_rows.dim() != 2:
+            raise ValueError("ref_rows must be host integers: one list of bank rows (its database) per tracked object")
+        ref_rows = ref_rows.tolist()
+    try:
+        rows = [list(r) for r in ref_rows]
+    except TypeError:
+        raise ValueError("ref_rows must be host integers: one list of bank rows (its database) per tracked object") from None
+    if len(rows) < 1:
+        raise ValueError("ref_rows names no sample: a pose stream tracks B >= 1 objects")
+    if any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) for row in rows for r in row):
+        raise ValueError("ref_rows must be integers: every entry of a database is a row of the bank")
+    rows = [[int(r) for r in row] for row in rows]
+    for b, row in enumerate(rows):
+        for t, r in enumerate(row):
+            if not 0 <= r < bank_len:
+                raise ValueError(f"ref_rows[{b}][{t}] = {r} is not a row of the bank (it holds {bank_len}): every entry of a database is")
+    n_refs = [len(r) for r in rows]
+    if max(n_refs) > MAX_DATABASE:
+        raise ValueError(f"a database of {max(n_refs)} views: one bd_stream_select_rows launch ranks at most {MAX_DATABASE} per object")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError(f"select_k must be a positive integer, got {k!r}")
+    if k > min(n_refs):
+        raise ValueError(f"select_k = {k} exceeds the smallest database ({min(n_refs)} views, object {n_refs.index(min(n_refs))}): every "
+                         "frame decodes against k views of the object's own")
+    return rows, n_refs, max(n_refs)
+
+
+def _relocalise(relocalise, B: int) -> torch.Tensor:
+    """step()'s `relocalise` -> an integer or bool tensor of shape (B,) (host or device), validated without reading it."""
+    t = relocalise if isinstance(relocalise, torch.Tensor) else torch.as_tensor(relocalise)
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise ValueError(f"relocalise must be integers or bools, got {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"relocalise must be ({B},) for this session of B = {B}: one flag per tracked object, got {tuple(t.shape)}")
+    return t
+
+
+def _rank_key(v: float, slot: int):
+    """bd_pose_select_rows' order on a stored fp32 distance: numbers before NaNs, smaller first (+inf ordinary), then the position."""
+    nan = v != v
+    return (nan, 0.0 if nan else v, slot)
+
+
+def select_rows_host(scores, dist, prev_rows, force, n_refs, k, rule, max_rms_px=float("inf")):
+    """bd_stream_select_rows' decision and rankings on the host, from the two value arrays the kernel writes: scores (B, N_max), dist
+    (B, N_max) or None (rule "dino"), prev_rows (B, 66), force (B,), n_refs (B,), rule "dino" / "track" (or _lib.STREAM_SELECT_*) ->
+    (used int32 (B,), sel int32 (B, k)), numpy.  Plain sorts, not the kernels' rounds:
+      rule        pose when rule is "track", force[b] == 0, prev ok == 1 and prev rms_px <= max_rms_px (a NaN rms fails it)
+      appearance  the slots [0, n_refs[b]) by (score descending, slot ascending), -inf an ordinary value, a NaN never picked
+      pose        the VALID slots by (number before NaN, distance ascending, slot ascending), +inf an ordinary value; a slot whose
+                  row lies outside the private store is no candidate -- it is the one whose score is -inf (a pair's score is finite)
+    The first k of either order, ascending; -1 where fewer exist."""
+    rule = SELECT_RULES.get(rule, rule)
+    if rule not in SELECT_RULES.values():
+        raise ValueError(f"unknown rule {rule!r}: choose from {sorted(SELECT_RULES)}")
+    sc = np.asarray(torch.as_tensor(scores).cpu(), dtype=np.float32)
+    B, n_max = sc.shape
+    ds = None if dist is None else np.asarray(torch.as_tensor(dist).cpu(), dtype=np.float32)
+    prev = np.asarray(torch.as_tensor(prev_rows).cpu(), dtype=np.float32).reshape(B, _lib.STREAM_ROW_FLOATS)
+    force = np.asarray(torch.as_tensor(force).cpu()).reshape(B)
+    n_refs = np.asarray(torch.as_tensor(n_refs).cpu()).reshape(B)
+    k, max_rms = int(k), np.float32(max_rms_px)
+    used, sel = np.zeros((B,), np.int32), np.full((B, k), -1, np.int32)
+    for b in range(B):
+        n = min(max(int(n_refs[b]), 0), n_max)
+        by_pose = bool(rule == _lib.STREAM_SELECT_TRACK and force[b] == 0 and prev[b, ROW_OK] == 1.0 and prev[b, ROW_RMS] <= max_rms)
+        if by_pose:
+            if ds is None:
+                raise ValueError("the pose rule applies and no distances were given")
+            order = sorted((i for i in range(n) if sc[b, i] != -math.inf), key=lambda i: _rank_key(float(ds[b, i]), i))
+        else:
+            order = sorted((i for i in range(n) if sc[b, i] == sc[b, i]), key=lambda i: (-float(sc[b, i]), i))
+        chosen = sorted(order[:k])
+        used[b] = int(by_pose)
+        sel[b, :len(chosen)] = chosen
+    return used, sel
+
+
 class PoseStream:
     """One streaming session over an entry-token bank, its step captured as one HIP graph (the module docstring has the sequence).
 
@@ -69,10 +175,21 @@ class PoseStream:
 
     The referenced entry rows are COPIED into a private store at construction: afterwards the bank may grow, be cleared or be
     refreshed without affecting the session.  After a step, `heat`, `corners_px`, `poses`, `rms_px`, `windows`, `K_crop` and `rows`
-    are the static device tensors of that step (the next step overwrites them)."""
+    are the static device tensors of that step (the next step overwrites them).
+
+    select_k (None: the fixed references above, today's session launch for launch and buffer for buffer): `ref_rows` is then a list
+    of B lists of bank rows, each object's DATABASE -- lengths may differ, at most 1024, objects may share rows -- and every step
+    decodes against the select_k <= min(length) views bd_stream_select_rows chooses (T = select_k + 1).  select: "dino" (by
+    appearance; the bank keeps match summaries: match_threshold=0.05) or "track" (by distance to the last frame's pose while its
+    ok == 1 and its rms_px <= max_rms_px, by appearance otherwise; the bank also keeps poses: keep_poses=True).  The distinct
+    database rows' entry tokens, match summaries and poses are copied like the entry rows above.  After a step `sel` (B, select_k)
+    database slots, ascending, `used` (B,) 1 = the pose rule chose, `scores` (B, N_max) and `dist` (B, N_max; None with "dino") are
+    that step's device tensors as well; `ref_rows_of(sel)` names the bank rows.  With "track" a step depends on the previous step's
+    result rows (`rows`): the first step after construction and after `reset()` re-localises by appearance."""
 
     def __init__(self, model, bank, ref_rows, bbox_3d, frame_shape, n_frames: int = 1, padding: float = 0.1,
-                 crop_dtype: torch.dtype = torch.float32, use_keep_boxes: bool = False, capture_error_mode: str = "global"):
+                 crop_dtype: torch.dtype = torch.float32, use_keep_boxes: bool = False, capture_error_mode: str = "global",
+                 select_k=None, select: str = "dino", max_rms_px: float = float("inf")):
         # ---- host-side refusals, before a device is needed
         if getattr(model, "training", False):
             raise ValueError("PoseStream needs the model in eval mode (model.eval()): the captured step is the evaluation path")
@@ -86,7 +203,24 @@ class PoseStream:
             raise ValueError("the reference bank was built on another encoder than this model's rgb_encoder")
         if bank.decoder is not decoder:
             raise ValueError("the reference bank keeps the entry tokens of another decoder than this model's")
-        rows, B, T = _ref_rows(ref_rows, len(bank))
+        if select not in SELECT_RULES:
+            raise ValueError(f"unknown select {select!r}: choose from {sorted(SELECT_RULES)}")
+        if select_k is None:
+            rows, B, T = _ref_rows(ref_rows, len(bank))
+            n_refs = n_max = None
+        else:
+            if not getattr(bank, "has_match_summaries", False):
+                raise ValueError("a selecting PoseStream scores the database by appearance and the reference bank keeps no match "
+                                 "summaries: build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05)")
+            if select == "track" and not getattr(bank, "has_poses", False):
+                raise ValueError('select="track" ranks the database by distance to the last pose and the reference bank keeps no poses: '
+                                 "build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05, keep_poses=True) "
+                                 "and add(images, bbox_feat=..., poses=...)")
+            max_rms_px = float(max_rms_px)
+            if max_rms_px != max_rms_px:
+                raise ValueError("max_rms_px is NaN: no solve would ever be trusted; give a number or inf")
+            rows, n_refs, n_max = _ref_database(ref_rows, len(bank), select_k)
+            B, T = len(rows), int(select_k) + 1
         if not isinstance(bbox_3d, torch.Tensor) or tuple(bbox_3d.shape) != (B, 8, 3):
             raise ValueError(f"bbox_3d must be a tensor of shape {(B, 8, 3)}, got {tuple(getattr(bbox_3d, 'shape', ()))}")
         H, W = (int(x) for x in frame_shape)
@@ -103,6 +237,7 @@ class PoseStream:
         self.model, self.encoder, self.decoder = model, encoder, decoder
         self.B, self.T, self.H, self.W, self.n_frames = B, T, H, W, n_frames
         self.padding, self.out_size, self.use_keep_boxes = float(padding), int(decoder.img_size), bool(use_keep_boxes)
+        self.select_k, self.select, self.max_rms_px = (None if select_k is None else int(select_k)), select, max_rms_px
 
         # ---- the private entry store and its source table: sample b's references, then -(b + 1): its query, in the last slot
         bank.ensure_fresh()
@@ -110,9 +245,31 @@ class PoseStream:
         dev = store.device
         distinct = sorted({r for row in rows for r in row})
         place = {r: i for i, r in enumerate(distinct)}
-        self._entry = store.index_select(0, torch.tensor(distinct, dtype=torch.int64).to(dev)).contiguous()
-        src = [x for b, row in enumerate(rows) for x in [place[r] for r in row] + [-(b + 1)]]
-        self._src = torch.tensor(src, dtype=torch.int32).to(dev)
+        take = torch.tensor(distinct, dtype=torch.int64).to(dev)
+        self._entry = store.index_select(0, take).contiguous()
+        self.sel = self.used = self.scores = self.dist = self.force = None
+        if select_k is None:
+            src = [x for b, row in enumerate(rows) for x in [place[r] for r in row] + [-(b + 1)]]
+            self._src = torch.tensor(src, dtype=torch.int32).to(dev)
+        else:
+            # the database in private row space: one `place` map serves the entry tokens, the match summaries and the poses
+            k = self.select_k
+            self._database = rows
+            self._msums, self._mcounts = bank._msums.index_select(0, take).contiguous(), bank._mcounts.index_select(0, take).contiguous()
+            self._poses = bank.poses.index_select(0, take).contiguous() if select == "track" else None
+            self._match = (float(bank.match_threshold), int(bank.tokens_per_view))
+            self._db_rows = torch.tensor([[place[r] for r in row] + [-1] * (n_max - len(row)) for row in rows], dtype=torch.int32).to(dev)
+            self._n_refs = torch.tensor(n_refs, dtype=torch.int32).to(dev)
+            self._q_sums = torch.zeros((B, int(bank.feature_dim)), dtype=torch.float32, device=dev)
+            self._q_counts = torch.zeros((B,), dtype=torch.float32, device=dev)
+            self.scores = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
+            self.dist = torch.zeros((B, n_max), dtype=torch.float32, device=dev) if select == "track" else None
+            self.used = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self.sel = torch.zeros((B, k), dtype=torch.int32, device=dev)
+            self.force = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self._src = torch.tensor([x for b, row in enumerate(rows) for x in [place[r] for r in row[:k]] + [-(b + 1)]], dtype=torch.int32).to(dev)
+            self._pin_force = torch.zeros((B,), dtype=torch.int32).pin_memory()
+            self._pin_reset, self._reset_done, self._forced = None, None, False
         self._mask = torch.zeros((B, T), dtype=torch.bool, device=dev)
         self._mask[:, T - 1] = True
 
@@ -161,12 +318,22 @@ class PoseStream:
         self._pinned = [enc_model._ws, decoder._ws, list(enc_model._packed.values()), list(decoder._packed.values())]
         enc_model._frozen_by.add(self)
         decoder._frozen_by.add(self)
+        if select_k is not None:        # (the warm-up left its own result rows: the first step re-localises by appearance)
+            self.rows.zero_()
 
     def _run(self):
         S = self.out_size
         hip_ops.stream_windows(self.det_boxes, self.K, self.padding, S, self.windows, self.K_crop)
         crop_resize_frames(self.frames, self.windows, frame_idx=self.frame_idx, keep_boxes=self.keep_boxes, out_size=S, out=self.crops)
         fresh = self.encoder.predict(self.crops)
+        if self.select_k is not None:
+            # which k database views the decoder reads this frame: the query's summary, then ONE launch that reads the last step's
+            # result rows and writes the source table forward_entry reads from device memory
+            (threshold, L), R = self._match, self._entry.shape[0]
+            hip_ops.match_view_sums(fresh, self.crops, threshold, self._q_sums, self._q_counts)
+            hip_ops.stream_select_rows(self._msums, self._mcounts, self._poses, R, self._q_sums, self._q_counts, self.rows, self._db_rows,
+                                       self._n_refs, self.force, L, self.select_k, SELECT_RULES[self.select], self.max_rms_px,
+                                       scores=self.scores, dist=self.dist, used=self.used, sel=self.sel, src=self._src)
         heat = self.decoder.forward_entry(self._entry, self._entry.shape[0], self._src, fresh, self._mask, S)
         kp_px = hip_ops.decode_topk(heat, want_idx=False)[0]
         poses, rms_px = solve_poses_device(kp_px, self.bbox_3d, self.K_crop, form="wave", want_rms=True)
@@ -190,12 +357,13 @@ class PoseStream:
             raise ValueError(f"{name} must be {tuple(shape)} for this session of B = {self.B}, got {tuple(t.shape)}")
         return t
 
-    def step(self, frames, det_boxes, K, frame_idx=None, keep_boxes=None, wait: bool = True) -> torch.Tensor:
+    def step(self, frames, det_boxes, K, frame_idx=None, keep_boxes=None, wait: bool = True, relocalise=None) -> torch.Tensor:
         """One frame: frames uint8 (n_frames, H, W, 3) (or (H, W, 3) when n_frames == 1; a pinned host tensor is copied
         asynchronously, a device tensor on the device), det_boxes float (B, 4) x0 y0 x1 y1, K float (B, 3, 3) full-frame intrinsics
         (host or device), frame_idx integers (B,): the frame each sample reads (None: as in the last step; initially b % n_frames),
         keep_boxes integers (B, 4) when the session was built with use_keep_boxes (None: as in the last step; initially the whole
-        frame).  Returns the pinned (B, 66) fp32 rows (the layout: include/boxdreamer_hip.h, bd_stream_results; ROW_* here) --
+        frame), relocalise integers or bools (B,) for a session built with select_k: nonzero = choose this object's references by
+        appearance on THIS step, whatever its last pose (None: nobody).  Returns the pinned (B, 66) fp32 rows (the layout: include/boxdreamer_hip.h, bd_stream_results; ROW_* here) --
         valid once the copy's event has completed: wait=True (the default) waits for it, wait=False leaves that to `wait()`."""
         B = self.B
         frames = self._check_frames(frames)
@@ -207,6 +375,10 @@ class PoseStream:
             if not self.use_keep_boxes:
                 raise ValueError("keep_boxes given to a session built with use_keep_boxes=False")
             self._check(keep_boxes, (B, 4), False, "keep_boxes")
+        if relocalise is not None:
+            if self.select_k is None:
+                raise ValueError("relocalise given to a session built without select_k: its references are fixed")
+            relocalise = _relocalise(relocalise, B)
         if self._pending:               # (an un-waited step: its copies still read the pinned staging buffers)
             self._done.synchronize()
             self._pending = False
@@ -226,6 +398,16 @@ class PoseStream:
             else:
                 pin.copy_(given)
                 static.copy_(pin, non_blocking=True)
+        if relocalise is not None:
+            if relocalise.is_cuda:
+                self.force.copy_(relocalise != 0, non_blocking=True)
+            else:
+                self._pin_force.copy_(relocalise != 0)
+                self.force.copy_(self._pin_force, non_blocking=True)
+            self._forced = True
+        elif self.select_k is not None and self._forced:        # (the flags hold for one step)
+            self.force.zero_()
+            self._forced = False
         self.graph.replay()
         self.rows_host.copy_(self.rows, non_blocking=True)
         self._done.record()
@@ -241,3 +423,38 @@ class PoseStream:
             self._done.synchronize()
             self._pending = False
         return self.rows_host
+
+    # -- a session that selects (select_k)
+    def reset(self, poses=None) -> None:
+        """Forget the last poses (enqueued on the current stream, nothing waits).  None: the result rows become zero, so the next step
+        re-localises by appearance.  poses float (B, 4, 4), host or device: they become the last poses with ok = 1 and rms_px = 0 -- a
+        session resumed from a known pose, whose next "track" step ranks by distance to them."""
+        if self.select_k is None:
+            raise ValueError("reset() on a session built without select_k: nothing is carried from frame to frame there")
+        if poses is None:
+            self.rows.zero_()
+            return
+        self._check(poses, (self.B, 4, 4), True, "poses")
+        if poses.is_cuda:
+            self.rows.zero_()
+            self.rows[:, ROW_POSE].copy_(poses.reshape(self.B, 16), non_blocking=True)
+            self.rows[:, ROW_OK].fill_(1.0)
+            return
+        if self._pin_reset is None:
+            self._pin_reset, self._reset_done = torch.zeros_like(self.rows_host).pin_memory(), torch.cuda.Event()
+        else:
+            self._reset_done.synchronize()          # (the last reset's copy still reads the staging buffer)
+        self._pin_reset.zero_()
+        self._pin_reset[:, ROW_POSE].copy_(poses.reshape(self.B, 16))
+        self._pin_reset[:, ROW_OK] = 1.0
+        self.rows.copy_(self._pin_reset, non_blocking=True)
+        self._reset_done.record()
+
+    def ref_rows_of(self, sel) -> list:
+        """Database slots (B, k) -- `sel`, read back -- -> the bank rows they name, B lists; -1 stays -1."""
+        if self.select_k is None:
+            raise ValueError("ref_rows_of() on a session built without select_k: its references are ref_rows")
+        slots = torch.as_tensor(sel).cpu().tolist()
+        if len(slots) != self.B:
+            raise ValueError(f"sel must have one row per tracked object (B = {self.B}), got {len(slots)}")
+        return [[self._database[b][int(i)] if int(i) >= 0 else -1 for i in row] for b, row in enumerate(slots)]

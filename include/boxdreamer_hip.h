@@ -641,6 +641,38 @@ int bd_stream_results(const float* poses, const float* rms_px, const float* kp_p
 int bd_stream_results_host(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
                            const float* bbox_3d, int out_size, float* rows, int n);
 
+/* bd_stream_select_rows: a streaming step's choice of references, on the device (stream.PoseStream(select_k=...)): each of the B
+ * tracked objects owns a database of views, and every frame k of them are named in the decoder's source table by ONE launch, one
+ * workgroup (4 waves) per object -- so a captured step replays unchanged while its references change.  Like bd_match_select_rows and
+ * bd_pose_select_rows: no atomics on floating-point data, every sum in index order (an object's bits do not depend on the batch),
+ * inconsistent device data reads and writes nothing out of bounds (n_refs[b] is clamped into [0, N_max], `rows` is not read past it).
+ * sums fp32 [R, D], counts fp32 [R], poses fp32 [R, 4, 4]: the session's private copies of the database views' match summaries
+ * (bd_match_view_sums) and poses; poses may be NULL when rule == BD_STREAM_SELECT_DINO (dist may then be NULL too and is not
+ * written).  q_sums fp32 [B, D], q_counts fp32 [B]: bd_match_view_sums of this frame's query crops.  prev_rows fp32
+ * [B, BD_STREAM_ROW_FLOATS]: the previous step's result rows (bd_stream_results: the pose at [0, 16), rms_px at [16], ok at [17]).
+ * rows int32 [B, N_max]: the private row of every database slot; n_refs int32 [B]; force int32 [B]: nonzero = the appearance rule
+ * for this object this frame.  1 <= k <= N_max <= 1024.
+ * Both value arrays are computed every frame, whatever rule applies:
+ *   scores fp32 [B, N_max]: bit-identical to bd_match_select_rows' for the same arguments (-inf for a slot past n_refs[b] and for a
+ *     row outside [0, R));
+ *   dist fp32 [B, N_max]: bit-identical to bd_pose_select_rows' dist for pred = prev_rows[:, 0:16], k = N_max and a `cand` table that
+ *     names slot i at position i < n_refs[b] and -1 beyond (+inf for an invalid slot).
+ * used int32 [B]: 1 when the pose rule chose, 0 when the appearance rule did.  The pose rule applies when rule ==
+ * BD_STREAM_SELECT_TRACK, force[b] == 0, prev ok == 1.0f and prev rms_px <= max_rms_px -- a comparison, so a NaN rms selects the
+ * appearance rule; the decision is uniform within the workgroup.
+ * sel int32 [B, k], src int32 [B * (k + 1)]: the chosen slots in ascending order, and their private rows followed by -(b + 1), fresh
+ * view b (the query): exactly what the kernel of the rule that applied writes -- bd_match_select_rows' sel / src (largest score,
+ * ties to the lower slot, -inf an ordinary value), or bd_pose_select_rows' fine_pos / src with fk = k (smaller distance, ties to the
+ * lower position, NaN last).  With fewer than k valid slots the remaining entries are -1 and 0x7fffffff.
+ * Checked before any launch: a NULL pointer BD_ERR_NULL (poses with rule != DINO, dist with poses given, included); an unknown rule,
+ * B <= 0, R < 0, N_max <= 0, N_max > 1024, k <= 0, k > N_max, L <= 0, D <= 0 BD_ERR_SHAPE. */
+#define BD_STREAM_SELECT_DINO 0
+#define BD_STREAM_SELECT_TRACK 1
+int bd_stream_select_rows(const float* sums, const float* counts, const float* poses, int R, const float* q_sums,
+                          const float* q_counts, const float* prev_rows, const int32_t* rows, const int32_t* n_refs,
+                          const int32_t* force, int B, int N_max, int L, int D, int k, int rule, float max_rms_px,
+                          float* scores, float* dist, int32_t* used, int32_t* sel, int32_t* src, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-path entry points
  * ---------------------------------------------------------------------------------------- */
