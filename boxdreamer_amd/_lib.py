@@ -165,10 +165,12 @@ EXPORTS = [
     "bd_solve_pnp_ransac_workspace_bytes", "bd_solve_pnp_ransac_wave", "bd_solve_pnp_ransac_host",
     "bd_round_sources", "bd_pose_select_rows",
     "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host", "bd_stream_select_rows",
+    "bd_stream_track_windows", "bd_stream_track_windows_host",
     "bd_gemm_plan", "bd_gemm_instance", "bd_attention_plan", "bd_attention_instance",
 ]
 STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
 STREAM_SELECT_DINO, STREAM_SELECT_TRACK = 0, 1         # BD_STREAM_SELECT_*: bd_stream_select_rows' rule
+STREAM_BOX_DETECTOR, STREAM_BOX_TRACKED, STREAM_BOX_HELD = 0, 1, 2     # BD_STREAM_BOX_*: bd_stream_track_windows' box_src
 
 _lib = None
 
@@ -270,6 +272,9 @@ def load() -> C.CDLL:
     lib.bd_stream_results.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, vp]
     lib.bd_stream_results_host.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i]
     lib.bd_stream_select_rows.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp, vp, vp, vp]
+    d = C.c_double
+    lib.bd_stream_track_windows.argtypes = [vp, vp, vp, vp, vp, vp, vp, d, i, i, i, f, d, d, vp, vp, vp, vp, vp, i, vp]
+    lib.bd_stream_track_windows_host.argtypes = [vp, vp, vp, vp, vp, vp, vp, d, i, i, i, f, d, d, vp, vp, vp, vp, vp, i]
     lib.bd_trace_begin.argtypes = [i]
     lib.bd_trace_end.argtypes = [C.POINTER(TraceRecord), i]
     if lib.bd_abi_version() != 9:

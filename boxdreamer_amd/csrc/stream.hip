@@ -10,6 +10,9 @@
 // arithmetic is written once (__host__ __device__) and runs on the host as bd_stream_*_host, the twin the tests compare the
 // kernels against.  Floating-point contraction is OFF in it: hipcc -O3 would turn a * b - c * d into an FMA, which rounds once
 // where torch's separate fp64 kernels round twice.
+//   * bd_stream_track_windows: a second form of the step's first node (PoseStream(track_boxes=True)): each object's box is the 3-D
+//     box projected with its own last pose (the last step's result row) while that pose is trusted, a detector box when one is
+//     offered and it is not, the last box otherwise; then the same window arithmetic.  Same layout, same twin (_host).
 //   * bd_stream_select_rows: between the encoder and the decoder of a step whose session owns a reference DATABASE per object
 //     (PoseStream(select_k=...)): which k views the decoder reads this frame, decided on the device and written as the decoder's
 //     source table, so the captured graph replays unchanged while the references change.  One workgroup per object; the arithmetic
@@ -55,6 +58,35 @@ __host__ __device__ inline void stream_window(const float* box, const float* K, 
     Kc[6] = K[6]; Kc[7] = K[7]; Kc[8] = K[8];
 }
 
+// one corner of the 3-D box (X [3]) through the pose p [16] and the full-frame intrinsics: Xc = ((r0 x + r1 y) + r2 z) + t, u = ((k00 xc +
+// k01 yc) + k02 zc) / zc, v = (k11 yc + k12 zc) / zc in fp64, rounded once; zc <= 0 gives NaN for both.  bd_stream_results' box slots
+// and bd_stream_track_windows' tracked box are this one function.
+__host__ __device__ inline void stream_project(const float* p, const float* X, double k00, double k01, double k02, double k11, double k12,
+                                               float* u, float* v) {
+#pragma clang fp contract(off)
+    const double x = X[0], y = X[1], z = X[2];
+    double c[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double a = (double)p[4 * r] * x, b = (double)p[4 * r + 1] * y, d = (double)p[4 * r + 2] * z;
+        const double ab = a + b;
+        const double abd = ab + d;
+        c[r] = abd + (double)p[4 * r + 3];
+    }
+    const double xc = c[0], yc = c[1], zc = c[2];
+    if (zc <= 0.0) {
+        *u = *v = __builtin_nanf("");
+    } else {
+        const double a = k00 * xc, b = k01 * yc, d = k02 * zc;
+        const double ab = a + b;
+        const double nu = ab + d;
+        const double e = k11 * yc, g = k12 * zc;
+        const double nv = e + g;
+        *u = (float)(nu / zc);
+        *v = (float)(nv / zc);
+    }
+}
+
 // one sample: pose [16], rms, kp [16], win [4], K [9] full frame, box [24] -> row [BD_STREAM_ROW_FLOATS]
 __host__ __device__ inline void stream_result(const float* pose, float rms, const float* kp, const int32_t* win, const float* K,
                                               const float* box, int out_size, float* row) {
@@ -90,32 +122,87 @@ __host__ __device__ inline void stream_result(const float* pose, float rms, cons
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         float u = 0.0f, v = 0.0f;
-        if (ok) {
-            const double x = box[3 * j], y = box[3 * j + 1], z = box[3 * j + 2];
-            double c[3];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const double a = (double)p[4 * r] * x, b = (double)p[4 * r + 1] * y, d = (double)p[4 * r + 2] * z;
-                const double ab = a + b;
-                const double abd = ab + d;
-                c[r] = abd + (double)p[4 * r + 3];
-            }
-            const double xc = c[0], yc = c[1], zc = c[2];
-            if (zc <= 0.0) {
-                u = v = __builtin_nanf("");
-            } else {
-                const double a = k00 * xc, b = k01 * yc, d = k02 * zc;
-                const double ab = a + b;
-                const double nu = ab + d;
-                const double e = k11 * yc, g = k12 * zc;
-                const double nv = e + g;
-                u = (float)(nu / zc);
-                v = (float)(nv / zc);
-            }
-        }
+        if (ok) stream_project(p, box + 3 * j, k00, k01, k02, k11, k12, &u, &v);
         row[50 + 2 * j] = u;
         row[51 + 2 * j] = v;
     }
+}
+
+// one object: whose box this step crops.  prev [BD_STREAM_ROW_FLOATS] the last step's row, box3 [24], K [9] full frame, det [4],
+// state [4] the box used last step -> out [4]; returns the source (BD_STREAM_BOX_*).  The tracked box is onepose's rule on the
+// projected corners (min / max of the fp32 values); it is taken while the last pose is trusted and the box is usable.
+__host__ __device__ inline int stream_track_box(const float* prev, const float* box3, const float* K, const float* det, int det_valid,
+                                                int force, const float* state, int frame_h, int frame_w, float max_rms_px,
+                                                double min_side_px, double max_side_px, float* out) {
+#pragma clang fp contract(off)
+    const double k00 = K[0], k01 = K[1], k02 = K[2], k11 = K[4], k12 = K[5];
+    float u0 = 0.0f, v0 = 0.0f, u1 = 0.0f, v1 = 0.0f;
+    bool finite = true;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float u, v;
+        stream_project(prev, box3 + 3 * j, k00, k01, k02, k11, k12, &u, &v);
+        finite = finite && u - u == 0.0f && v - v == 0.0f;
+        u0 = j == 0 || u < u0 ? u : u0;
+        u1 = j == 0 || u > u1 ? u : u1;
+        v0 = j == 0 || v < v0 ? v : v0;
+        v1 = j == 0 || v > v1 ? v : v1;
+    }
+    // usable: enough of it inside the frame, and not absurdly large (a pose that puts the object on the camera)
+    const double x0 = u0, y0 = v0, x1 = u1, y1 = v1, fw = (double)frame_w, fh = (double)frame_h;
+    const double cx0 = x0 > 0.0 ? x0 : 0.0, cy0 = y0 > 0.0 ? y0 : 0.0;
+    const double cx1 = x1 < fw ? x1 : fw, cy1 = y1 < fh ? y1 : fh;
+    const double vis_x = cx1 - cx0, vis_y = cy1 - cy0, ext_x = x1 - x0, ext_y = y1 - y0;
+    const bool valid = finite && vis_x >= min_side_px && vis_y >= min_side_px && ext_x <= max_side_px && ext_y <= max_side_px;
+    const bool trusted = prev[17] == 1.0f && prev[16] <= max_rms_px && force == 0 && valid;
+    if (trusted) {
+        out[0] = u0; out[1] = v0; out[2] = u1; out[3] = v1;
+        return BD_STREAM_BOX_TRACKED;
+    }
+    const bool from_det = det_valid != 0;
+    const float* src = from_det ? det : state;
+    const float b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];         // (read before `out` is written: out may be state)
+    out[0] = b0; out[1] = b1; out[2] = b2; out[3] = b3;
+    return from_det ? BD_STREAM_BOX_DETECTOR : BD_STREAM_BOX_HELD;
+}
+
+// one object of bd_stream_track_windows: the box, its window and crop intrinsics, and what is reported about it
+__host__ __device__ inline void stream_track_window(const float* prev, const float* box3, const float* K, const float* det, int det_valid,
+                                                    int force, float* state, double padding, int out_size, int frame_h, int frame_w,
+                                                    float max_rms_px, double min_side_px, double max_side_px, int32_t* win, float* Kc,
+                                                    int32_t* box_src, int32_t* keep, float* track) {
+#pragma clang fp contract(off)
+    float box[4];
+    const int src = stream_track_box(prev, box3, K, det, det_valid, force, state, frame_h, frame_w, max_rms_px, min_side_px, max_side_px, box);
+    stream_window(box, K, padding, out_size, win, Kc);
+    state[0] = box[0]; state[1] = box[1]; state[2] = box[2]; state[3] = box[3];
+    *box_src = src;
+    if (keep) {                                             // the object's own box, every int() towards zero; not squared
+        const double t0 = trunc((double)box[0]), t1 = trunc((double)box[1]), t2 = trunc((double)box[2]), t3 = trunc((double)box[3]);
+        const double lim = 2147483648.0;
+        const bool ok = sw_finite(t0) && sw_finite(t1) && sw_finite(t2) && sw_finite(t3) && t0 >= -lim && t0 < lim && t1 >= -lim && t1 < lim &&
+                        t2 >= -lim && t2 < lim && t3 >= -lim && t3 < lim;
+        keep[0] = ok ? (int32_t)t0 : 0; keep[1] = ok ? (int32_t)t1 : 0; keep[2] = ok ? (int32_t)t2 : 0; keep[3] = ok ? (int32_t)t3 : 0;
+    }
+    if (track) {
+        track[0] = box[0]; track[1] = box[1]; track[2] = box[2]; track[3] = box[3];
+        track[4] = (float)src;
+    }
+}
+
+__global__ __launch_bounds__(SW_LANES) void stream_track_windows_kernel(const float* __restrict__ prev_rows, const float* __restrict__ bbox_3d,
+                                                                        const float* __restrict__ K, const float* __restrict__ det_boxes,
+                                                                        const int32_t* __restrict__ det_valid, const int32_t* __restrict__ force,
+                                                                        float* state_box, double padding, int out_size, int frame_h,
+                                                                        int frame_w, float max_rms_px, double min_side_px, double max_side_px,
+                                                                        int32_t* __restrict__ windows, float* __restrict__ K_crop,
+                                                                        int32_t* __restrict__ box_src, int32_t* keep_boxes, float* track, int n) {
+    const int i = blockIdx.x * SW_LANES + threadIdx.x;
+    if (i >= n) return;
+    stream_track_window(prev_rows + (int64_t)i * BD_STREAM_ROW_FLOATS, bbox_3d + (int64_t)i * 24, K + (int64_t)i * 9, det_boxes + (int64_t)i * 4,
+                        det_valid[i], force[i], state_box + (int64_t)i * 4, padding, out_size, frame_h, frame_w, max_rms_px, min_side_px,
+                        max_side_px, windows + (int64_t)i * 4, K_crop + (int64_t)i * 9, box_src + i,
+                        keep_boxes ? keep_boxes + (int64_t)i * 4 : nullptr, track ? track + (int64_t)i * 5 : nullptr);
 }
 
 __global__ __launch_bounds__(SW_LANES) void stream_windows_kernel(const float* __restrict__ det_boxes, const float* __restrict__ K,
@@ -200,7 +287,45 @@ int results_args(const void* a, const void* b, const void* c, const void* d, con
     return BD_OK;
 }
 
+int track_windows_args(const void* prev_rows, const void* bbox_3d, const void* K, const void* det_boxes, const void* det_valid,
+                       const void* force, const void* state_box, const void* windows, const void* K_crop, const void* box_src, int out_size,
+                       int frame_h, int frame_w, double min_side_px, double max_side_px, int n) {
+    if (!prev_rows || !bbox_3d || !K || !det_boxes || !det_valid || !force || !state_box || !windows || !K_crop || !box_src) return BD_ERR_NULL;
+    if (n < 0 || n > SW_MAX_N || out_size < 1 || frame_h < 1 || frame_w < 1) return BD_ERR_SHAPE;
+    if (!(min_side_px > 0.0) || !(max_side_px > 0.0)) return BD_ERR_SHAPE;       // (a NaN fails both comparisons)
+    return BD_OK;
+}
+
 }  // namespace
+
+extern "C" int bd_stream_track_windows(const float* prev_rows, const float* bbox_3d, const float* K, const float* det_boxes,
+                                       const int32_t* det_valid, const int32_t* force, float* state_box, double padding, int out_size,
+                                       int frame_h, int frame_w, float max_rms_px, double min_side_px, double max_side_px, int32_t* windows,
+                                       float* K_crop, int32_t* box_src, int32_t* keep_boxes, float* track, int n, void* stream) {
+    const int rc = track_windows_args(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, windows, K_crop, box_src, out_size, frame_h,
+                                      frame_w, min_side_px, max_side_px, n);
+    if (rc != BD_OK || n == 0) return rc;
+    hipLaunchKernelGGL(stream_track_windows_kernel, dim3((n + SW_LANES - 1) / SW_LANES), dim3(SW_LANES), 0, (hipStream_t)stream, prev_rows,
+                       bbox_3d, K, det_boxes, det_valid, force, state_box, padding, out_size, frame_h, frame_w, max_rms_px, min_side_px,
+                       max_side_px, windows, K_crop, box_src, keep_boxes, track, n);
+    BD_CHECK_LAUNCH();
+    return BD_OK;
+}
+
+extern "C" int bd_stream_track_windows_host(const float* prev_rows, const float* bbox_3d, const float* K, const float* det_boxes,
+                                            const int32_t* det_valid, const int32_t* force, float* state_box, double padding, int out_size,
+                                            int frame_h, int frame_w, float max_rms_px, double min_side_px, double max_side_px,
+                                            int32_t* windows, float* K_crop, int32_t* box_src, int32_t* keep_boxes, float* track, int n) {
+    const int rc = track_windows_args(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, windows, K_crop, box_src, out_size, frame_h,
+                                      frame_w, min_side_px, max_side_px, n);
+    if (rc != BD_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        stream_track_window(prev_rows + (int64_t)i * BD_STREAM_ROW_FLOATS, bbox_3d + (int64_t)i * 24, K + (int64_t)i * 9,
+                            det_boxes + (int64_t)i * 4, det_valid[i], force[i], state_box + (int64_t)i * 4, padding, out_size, frame_h, frame_w,
+                            max_rms_px, min_side_px, max_side_px, windows + (int64_t)i * 4, K_crop + (int64_t)i * 9, box_src + i,
+                            keep_boxes ? keep_boxes + (int64_t)i * 4 : nullptr, track ? track + (int64_t)i * 5 : nullptr);
+    return BD_OK;
+}
 
 extern "C" int bd_stream_windows(const float* det_boxes, const float* K, double padding, int out_size, int32_t* windows, float* K_crop,
                                  int n, void* stream) {

@@ -486,6 +486,41 @@ def stream_windows(det_boxes, K, padding=0.1, out_size=224, windows=None, K_crop
     return windows, K_crop
 
 
+def stream_track_windows(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, padding=0.1, out_size=224, frame_shape=(480, 640),
+                         max_rms_px=float("inf"), min_side_px=8.0, max_side_px=None, windows=None, K_crop=None, box_src=None,
+                         keep_boxes=None, track=None):
+    """bd_stream_track_windows: one launch -> (windows int32 (n, 4), K_crop fp32 (n, 3, 3), box_src int32 (n,)); `state_box` fp32 (n, 4)
+    is read and UPDATED IN PLACE with the box used.  prev_rows fp32 (n, 66): the last step's result rows; bbox_3d fp32 (n, 8, 3); K fp32
+    (n, 3, 3) of the full frame; det_boxes fp32 (n, 4); det_valid / force int32 (n,); frame_shape (H, W); max_side_px None: 4 x
+    max(H, W).  keep_boxes int32 (n, 4) / track fp32 (n, 5): written when given (the truncated box; x0 y0 x1 y1 src).  The rule:
+    include/boxdreamer_hip.h."""
+    lib = _lib.load()
+    n = int(prev_rows.shape[0]) if isinstance(prev_rows, torch.Tensor) and prev_rows.dim() == 2 else -1
+    frame_h, frame_w = (int(x) for x in frame_shape)
+    max_side_px = 4.0 * max(frame_h, frame_w) if max_side_px is None else float(max_side_px)
+    _stream_dev(prev_rows, (n, _lib.STREAM_ROW_FLOATS), torch.float32, "prev_rows")
+    _stream_dev(bbox_3d, (n, 8, 3), torch.float32, "bbox_3d")
+    _stream_dev(K, (n, 3, 3), torch.float32, "K")
+    _stream_dev(det_boxes, (n, 4), torch.float32, "det_boxes")
+    _stream_dev(det_valid, (n,), torch.int32, "det_valid")
+    _stream_dev(force, (n,), torch.int32, "force")
+    _stream_dev(state_box, (n, 4), torch.float32, "state_box")
+    dev = prev_rows.device
+    windows = torch.empty((n, 4), dtype=torch.int32, device=dev) if windows is None else _stream_dev(windows, (n, 4), torch.int32, "windows")
+    K_crop = torch.empty((n, 3, 3), dtype=torch.float32, device=dev) if K_crop is None else _stream_dev(K_crop, (n, 3, 3), torch.float32, "K_crop")
+    box_src = torch.empty((n,), dtype=torch.int32, device=dev) if box_src is None else _stream_dev(box_src, (n,), torch.int32, "box_src")
+    if keep_boxes is not None:
+        _stream_dev(keep_boxes, (n, 4), torch.int32, "keep_boxes")
+    if track is not None:
+        _stream_dev(track, (n, 5), torch.float32, "track")
+    _lib.same_device(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, windows, K_crop, box_src, keep_boxes, track)
+    check(lib.bd_stream_track_windows(ptr(prev_rows), ptr(bbox_3d), ptr(K), ptr(det_boxes), ptr(det_valid), ptr(force), ptr(state_box),
+                                      float(padding), int(out_size), frame_h, frame_w, float(max_rms_px), float(min_side_px), max_side_px,
+                                      ptr(windows), ptr(K_crop), ptr(box_src), ptr(keep_boxes), ptr(track), n, stream()),
+          "bd_stream_track_windows")
+    return windows, K_crop, box_src
+
+
 def stream_results(poses, rms_px, kp_px, windows, K, bbox_3d, out_size=224, rows=None):
     """bd_stream_results: poses fp32 (n, 4, 4), rms_px fp32 (n,), kp_px fp32 (n, 8, 2), windows int32 (n, 4), K fp32 (n, 3, 3) of the
     full frame, bbox_3d fp32 (n, 8, 3) -> rows fp32 (n, 66) in ONE launch (the layout: include/boxdreamer_hip.h), written into `rows`
@@ -568,6 +603,32 @@ def stream_windows_host(det_boxes, K, padding=0.1, out_size=224):
     rc = lib.bd_stream_windows_host(b.ctypes.data, k.ctypes.data, float(padding), int(out_size), windows.ctypes.data, K_crop.ctypes.data, n)
     check(rc, "bd_stream_windows_host")
     return windows, K_crop
+
+
+def stream_track_windows_host(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, padding=0.1, out_size=224,
+                              frame_shape=(480, 640), max_rms_px=float("inf"), min_side_px=8.0, max_side_px=None, want_keep=False):
+    """bd_stream_track_windows_host: the same arithmetic on host arrays (numpy or CPU tensors) -> a dict of numpy arrays: windows int32
+    (n, 4), K_crop fp32 (n, 3, 3), state_box fp32 (n, 4) (the UPDATED boxes: the input is not touched), box_src int32 (n,), track fp32
+    (n, 5) and, with want_keep, keep_boxes int32 (n, 4).  Needs no GPU."""
+    import numpy as np
+    lib = _lib.load()
+    n = len(prev_rows)
+    frame_h, frame_w = (int(x) for x in frame_shape)
+    max_side_px = 4.0 * max(frame_h, frame_w) if max_side_px is None else float(max_side_px)
+    args = (_host32(prev_rows, (n, _lib.STREAM_ROW_FLOATS), np.float32), _host32(bbox_3d, (n, 8, 3), np.float32), _host32(K, (n, 3, 3), np.float32),
+            _host32(det_boxes, (n, 4), np.float32), _host32(det_valid, (n,), np.int32), _host32(force, (n,), np.int32))
+    state = _host32(state_box, (n, 4), np.float32).copy()
+    out = dict(windows=np.empty((n, 4), np.int32), K_crop=np.empty((n, 3, 3), np.float32), state_box=state, box_src=np.empty((n,), np.int32),
+               track=np.empty((n, 5), np.float32))
+    keep = np.empty((n, 4), np.int32) if want_keep else None
+    rc = lib.bd_stream_track_windows_host(*(a.ctypes.data for a in args), state.ctypes.data, float(padding), int(out_size), frame_h, frame_w,
+                                          float(max_rms_px), float(min_side_px), max_side_px, out["windows"].ctypes.data,
+                                          out["K_crop"].ctypes.data, out["box_src"].ctypes.data, keep.ctypes.data if want_keep else None,
+                                          out["track"].ctypes.data, n)
+    check(rc, "bd_stream_track_windows_host")
+    if want_keep:
+        out["keep_boxes"] = keep
+    return out
 
 
 def stream_results_host(poses, rms_px, kp_px, windows, K, bbox_3d, out_size=224):

@@ -34,6 +34,20 @@ that pose is trustworthy -- the last row's ok == 1 and its rms_px <= max_rms_px 
 after `reset()`, after a failed or poor solve, and for the objects `step(..., relocalise=...)` names.  A "track" step therefore
 DEPENDS on the previous step's result rows: that is the one thing such a session carries from frame to frame.
 
+With `track_boxes=True` a session needs no detector box per frame: the step's first node is bd_stream_track_windows, which takes
+each object's crop box from its OWN last pose -- the min / max of the 3-D box's 8 corners projected with the last result row's pose
+and this frame's K (the rule of the OnePose reproj_box files, src/datasets/onepose.py:437-455) -- while that pose is trusted (the
+rule above, `relocalise` included) and the box is usable (every corner in front of the camera, at least min_side_px of it inside the
+frame on both axes, at most max_side_px across), a detector box when one is offered and the pose is not trusted, and the last box
+otherwise:
+
+    s = PoseStream(model, bank, [rows.tolist()], bbox_3d, frame_shape=(480, 640), track_boxes=True, max_rms_px=4.0)
+    s.step(frame, det_box, K)                   # no pose yet: the detection
+    s.step(frame, None, K)                      # nobody has a detection: the box follows the last pose
+    x0, y0, x1, y1, src = s.track_host[0]       # the box this step used and its source (BOX_DETECTOR / BOX_TRACKED / BOX_HELD)
+
+One node for one node, decided inside the captured graph; the box lags the pose by one frame, which `padding` covers.
+
 Limits: an entry-token bank only; the same T for every sample; a fixed frame shape and frame count; the encoder and the decoder are
 frozen while the session lives (a larger eager batch, .to() or a checkpoint load raises; `del` the session first).
 """
@@ -164,6 +178,104 @@ def select_rows_host(scores, dist, prev_rows, force, n_refs, k, rule, max_rms_px
     return used, sel
 
 
+BOX_DETECTOR, BOX_TRACKED, BOX_HELD = _lib.STREAM_BOX_DETECTOR, _lib.STREAM_BOX_TRACKED, _lib.STREAM_BOX_HELD
+TRACK_FLOATS = 5            # the tail a tracking session reports per object: x0 y0 x1 y1 of the box it used, then its source
+
+
+def _flags(t, B: int, name: str) -> torch.Tensor:
+    """One integer or bool flag per tracked object (step()'s `det_valid`), validated like `relocalise`."""
+    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise ValueError(f"{name} must be integers or bools, got {t.dtype}")
+    if tuple(t.shape) != (B,):
+        raise ValueError(f"{name} must be ({B},) for this session of B = {B}: one flag per tracked object, got {tuple(t.shape)}")
+    return t
+
+
+def _step_boxes(track_boxes: bool, det_boxes, det_valid, keep_boxes, B: int):
+    """What step() refuses about who supplies the boxes, before anything is copied -> det_valid as a validated tensor, or None."""
+    if not track_boxes:
+        if det_boxes is None:
+            raise ValueError("det_boxes=None given to a session built without track_boxes: every step needs a box per tracked object")
+        if det_valid is not None:
+            raise ValueError("det_valid given to a session built without track_boxes: its boxes are always taken as given")
+        return None
+    if keep_boxes is not None:
+        raise ValueError("keep_boxes given to a session built with track_boxes: bd_stream_track_windows writes them from the box it uses")
+    if det_valid is None:
+        return None
+    if det_boxes is None:
+        raise ValueError("det_valid given without det_boxes: there is no detection to call valid")
+    return _flags(det_valid, B, "det_valid")
+
+
+def _track_limits(track_boxes: bool, max_rms_px, min_side_px, max_side_px, H: int, W: int):
+    """The constructor's track_boxes arguments -> (max_rms_px, min_side_px, max_side_px) as floats, validated."""
+    max_rms_px, min_side_px = float(max_rms_px), float(min_side_px)
+    max_side_px = 4.0 * max(H, W) if max_side_px is None else float(max_side_px)
+    if track_boxes:
+        if max_rms_px != max_rms_px:
+            raise ValueError("max_rms_px is NaN: no solve would ever be trusted; give a number or inf")
+        for name, v in (("min_side_px", min_side_px), ("max_side_px", max_side_px)):
+            if not v > 0.0:
+                raise ValueError(f"{name} = {v}: it must be a positive number of pixels (max_side_px=None: 4 x the longer frame side)")
+    return max_rms_px, min_side_px, max_side_px
+
+
+def track_windows_host(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state_box, frame_shape=(480, 640), max_rms_px=float("inf"),
+                       min_side_px=8.0, max_side_px=None):
+    """bd_stream_track_windows' decision and box on the host, in plain numpy (fp64 from the fp32 inputs, numpy contracts nothing):
+    prev_rows (n, 66), bbox_3d (n, 8, 3), K (n, 3, 3), det_boxes (n, 4), det_valid (n,), force (n,), state_box (n, 4) -> a dict of numpy
+    arrays: box fp32 (n, 4) the box each object uses, src int32 (n,) BOX_DETECTOR / BOX_TRACKED / BOX_HELD, keep int32 (n, 4) the box
+    truncated towards zero (zeros when not finite or outside int32), tracked fp32 (n, 4) the projected box whatever was decided, and
+    the reasons, bool (n,): finite, visible (clipped extent >= min_side_px), bounded (extent <= max_side_px), valid, trusted.
+      tracked  (min u, min v, max u, max v) of the 8 corners projected with prev_rows[:, 0:16] and K, each rounded to fp32; a corner
+               with zc <= 0 is NaN
+      trusted  prev ok == 1, prev rms_px <= max_rms_px (a NaN fails), force == 0, and the box finite, visible and bounded
+      box      tracked when trusted, else det_boxes where det_valid != 0, else state_box"""
+    f64 = np.float64
+    prev = np.asarray(torch.as_tensor(prev_rows).cpu(), dtype=np.float32)
+    n = len(prev)
+    prev = prev.reshape(n, _lib.STREAM_ROW_FLOATS)
+    X = np.asarray(torch.as_tensor(bbox_3d).cpu(), dtype=np.float32).reshape(n, 8, 3).astype(f64)
+    Kd = np.asarray(torch.as_tensor(K).cpu(), dtype=np.float32).reshape(n, 3, 3).astype(f64)
+    det = np.asarray(torch.as_tensor(det_boxes).cpu(), dtype=np.float32).reshape(n, 4)
+    det_valid = np.asarray(torch.as_tensor(det_valid).cpu()).reshape(n)
+    force = np.asarray(torch.as_tensor(force).cpu()).reshape(n)
+    state = np.asarray(torch.as_tensor(state_box).cpu(), dtype=np.float32).reshape(n, 4)
+    H, W = (int(v) for v in frame_shape)
+    max_side = f64(4.0 * max(H, W) if max_side_px is None else max_side_px)
+    P = prev[:, ROW_POSE].reshape(n, 4, 4).astype(f64)
+    x, y, z = X[..., 0], X[..., 1], X[..., 2]
+    with np.errstate(all="ignore"):
+        xc, yc, zc = (((P[:, r, 0:1] * x + P[:, r, 1:2] * y) + P[:, r, 2:3] * z) + P[:, r, 3:4] for r in range(3))
+        u = ((Kd[:, 0, 0:1] * xc + Kd[:, 0, 1:2] * yc) + Kd[:, 0, 2:3] * zc) / zc
+        v = (Kd[:, 1, 1:2] * yc + Kd[:, 1, 2:3] * zc) / zc
+        u = np.where(zc <= 0, np.nan, u).astype(np.float32)
+        v = np.where(zc <= 0, np.nan, v).astype(np.float32)
+        finite = np.isfinite(u).all(1) & np.isfinite(v).all(1)
+        lo_u, hi_u, lo_v, hi_v = u[:, 0], u[:, 0], v[:, 0], v[:, 0]
+        for j in range(1, 8):               # (the order of the comparisons is the kernel's: it decides nothing but the sign of a zero)
+            lo_u, hi_u = np.where(u[:, j] < lo_u, u[:, j], lo_u), np.where(u[:, j] > hi_u, u[:, j], hi_u)
+            lo_v, hi_v = np.where(v[:, j] < lo_v, v[:, j], lo_v), np.where(v[:, j] > hi_v, v[:, j], hi_v)
+        tracked = np.stack([lo_u, lo_v, hi_u, hi_v], 1).astype(np.float32)
+        t = tracked.astype(f64)
+        vis_x = np.minimum(t[:, 2], f64(W)) - np.maximum(t[:, 0], 0.0)
+        vis_y = np.minimum(t[:, 3], f64(H)) - np.maximum(t[:, 1], 0.0)
+        visible = finite & (vis_x >= f64(min_side_px)) & (vis_y >= f64(min_side_px))
+        bounded = finite & (t[:, 2] - t[:, 0] <= max_side) & (t[:, 3] - t[:, 1] <= max_side)
+        valid = finite & visible & bounded
+        trusted = (prev[:, ROW_OK] == 1.0) & (prev[:, ROW_RMS] <= np.float32(max_rms_px)) & (force == 0) & valid
+    offered = det_valid != 0
+    box = np.where(trusted[:, None], tracked, np.where(offered[:, None], det, state)).astype(np.float32)
+    src = np.where(trusted, BOX_TRACKED, np.where(offered, BOX_DETECTOR, BOX_HELD)).astype(np.int32)
+    with np.errstate(all="ignore"):
+        tr = np.trunc(box.astype(f64))
+        fits = (np.isfinite(tr) & (tr >= -2147483648.0) & (tr < 2147483648.0)).all(1)
+        keep = np.where(fits[:, None], np.where(np.isfinite(tr), tr, 0.0), 0.0).astype(np.int64).astype(np.int32)
+    return dict(box=box, src=src, keep=keep, tracked=tracked, finite=finite, visible=visible, bounded=bounded, valid=valid, trusted=trusted)
+
+
 class PoseStream:
     """One streaming session over an entry-token bank, its step captured as one HIP graph (the module docstring has the sequence).
 
@@ -185,11 +297,19 @@ class PoseStream:
     database rows' entry tokens, match summaries and poses are copied like the entry rows above.  After a step `sel` (B, select_k)
     database slots, ascending, `used` (B,) 1 = the pose rule chose, `scores` (B, N_max) and `dist` (B, N_max; None with "dino") are
     that step's device tensors as well; `ref_rows_of(sel)` names the bank rows.  With "track" a step depends on the previous step's
-    result rows (`rows`): the first step after construction and after `reset()` re-localises by appearance."""
+    result rows (`rows`): the first step after construction and after `reset()` re-localises by appearance.
+
+    track_boxes (False: bd_stream_windows on the boxes given, today's session): the first node is bd_stream_track_windows (the module
+    docstring has the rule); min_side_px, max_side_px (None: 4 x max(H, W)) bound the usable tracked box, max_rms_px the trusted pose
+    (shared with select="track": both kernels decide alike from the same row).  `rows` and the tail `track` (B, 5) = x0 y0 x1 y1 src
+    per object live in ONE flat device buffer, `rows_host` and `track_host` in one pinned buffer: still one D2H per step.  After a
+    step `state_box` (B, 4) and `box_src` (B,) are that step's device tensors too; with use_keep_boxes the kernel writes `keep_boxes`
+    (the box truncated towards zero, not squared).  Such a session also depends on the previous step's result rows."""
 
     def __init__(self, model, bank, ref_rows, bbox_3d, frame_shape, n_frames: int = 1, padding: float = 0.1,
                  crop_dtype: torch.dtype = torch.float32, use_keep_boxes: bool = False, capture_error_mode: str = "global",
-                 select_k=None, select: str = "dino", max_rms_px: float = float("inf")):
+                 select_k=None, select: str = "dino", max_rms_px: float = float("inf"), track_boxes: bool = False,
+                 min_side_px: float = 8.0, max_side_px=None):
         # ---- host-side refusals, before a device is needed
         if getattr(model, "training", False):
             raise ValueError("PoseStream needs the model in eval mode (model.eval()): the captured step is the evaluation path")
@@ -229,6 +349,8 @@ class PoseStream:
             raise ValueError(f"frame_shape = {(H, W)} and n_frames = {n_frames} must be positive")
         if crop_dtype not in (torch.float32, torch.float16, torch.bfloat16):
             raise ValueError(f"crop_dtype must be float32, float16 or bfloat16, got {crop_dtype}")
+        track_boxes = bool(track_boxes)
+        max_rms_px, min_side_px, max_side_px = _track_limits(track_boxes, max_rms_px, min_side_px, max_side_px, H, W)
         _lib.require_gpu()
         if decoder._signature() != model._calibrated_for and calibrate.applicable(encoder, decoder):
             raise RuntimeError("the model's precision self-check has not run for these decoder weights, and it cannot run inside a graph "
@@ -238,6 +360,7 @@ class PoseStream:
         self.B, self.T, self.H, self.W, self.n_frames = B, T, H, W, n_frames
         self.padding, self.out_size, self.use_keep_boxes = float(padding), int(decoder.img_size), bool(use_keep_boxes)
         self.select_k, self.select, self.max_rms_px = (None if select_k is None else int(select_k)), select, max_rms_px
+        self.track_boxes, self.min_side_px, self.max_side_px = track_boxes, min_side_px, max_side_px
 
         # ---- the private entry store and its source table: sample b's references, then -(b + 1): its query, in the last slot
         bank.ensure_fresh()
@@ -266,8 +389,9 @@ class PoseStream:
             self.dist = torch.zeros((B, n_max), dtype=torch.float32, device=dev) if select == "track" else None
             self.used = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.sel = torch.zeros((B, k), dtype=torch.int32, device=dev)
-            self.force = torch.zeros((B,), dtype=torch.int32, device=dev)
             self._src = torch.tensor([x for b, row in enumerate(rows) for x in [place[r] for r in row[:k]] + [-(b + 1)]], dtype=torch.int32).to(dev)
+        if select_k is not None or track_boxes:     # what a step carries from frame to frame is distrusted per object through `force`
+            self.force = torch.zeros((B,), dtype=torch.int32, device=dev)
             self._pin_force = torch.zeros((B,), dtype=torch.int32).pin_memory()
             self._pin_reset, self._reset_done, self._forced = None, None, False
         self._mask = torch.zeros((B, T), dtype=torch.bool, device=dev)
@@ -276,26 +400,41 @@ class PoseStream:
         # ---- static buffers
         S = self.out_size
         self.frames = torch.zeros((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
-        self._in_f = torch.zeros((B * 13,), dtype=torch.float32, device=dev)           # det_boxes, then K: one H2D per step
-        self.det_boxes, self.K = self._in_f[:B * 4].view(B, 4), self._in_f[B * 4:].view(B, 3, 3)
+        n_in = B * (14 if track_boxes else 13)      # det_boxes, then K (then det_valid, int32 in the same words): one H2D per step
+        self._in_f = torch.zeros((n_in,), dtype=torch.float32, device=dev)
+        self.det_boxes, self.K = self._in_f[:B * 4].view(B, 4), self._in_f[B * 4:B * 13].view(B, 3, 3)
         self.K.copy_(torch.eye(3, device=dev).expand(B, 3, 3))
-        self.det_boxes.copy_(torch.tensor([0.0, 0.0, float(min(H, W)), float(min(H, W))], device=dev).expand(B, 4))
+        self.det_boxes.copy_(self._default_box().expand(B, 4))
         self.frame_idx = (torch.arange(B, dtype=torch.int32) % n_frames).to(dev)
         self.keep_boxes = torch.tensor([0, 0, W - 1, H - 1], dtype=torch.int32).repeat(B, 1).to(dev) if self.use_keep_boxes else None
+        self.det_valid = self.state_box = self.box_src = self.track = self.track_host = None
         self.bbox_3d = bbox_3d.detach().to(dev).float().contiguous().clone()
         self.windows = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         self.K_crop = torch.zeros((B, 3, 3), dtype=torch.float32, device=dev)
         self.crops = torch.zeros((B, 3, S, S), dtype=crop_dtype, device=dev)
-        self.rows = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32, device=dev)
-        self.rows_host = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32).pin_memory()
+        n_rows = B * _lib.STREAM_ROW_FLOATS
+        if track_boxes:
+            # the result rows and the tail (x0 y0 x1 y1 src per object) in ONE flat buffer, on the device and pinned: still one D2H
+            self._out = torch.zeros((n_rows + B * TRACK_FLOATS,), dtype=torch.float32, device=dev)
+            self._out_host = torch.zeros((n_rows + B * TRACK_FLOATS,), dtype=torch.float32).pin_memory()
+            self.rows, self.track = self._out[:n_rows].view(B, _lib.STREAM_ROW_FLOATS), self._out[n_rows:].view(B, TRACK_FLOATS)
+            self.rows_host = self._out_host[:n_rows].view(B, _lib.STREAM_ROW_FLOATS)
+            self.track_host = self._out_host[n_rows:].view(B, TRACK_FLOATS)
+            self.det_valid = self._in_f[B * 13:].view(torch.int32)
+            self.state_box = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+            self.box_src = torch.zeros((B,), dtype=torch.int32, device=dev)
+        else:
+            self._out = self.rows = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32, device=dev)
+            self._out_host = self.rows_host = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32).pin_memory()
         # pinned staging of the small host inputs (a copy from pageable memory would wait for the stream)
-        self._pin_f = torch.zeros((B * 13,), dtype=torch.float32).pin_memory()
+        self._pin_f = torch.zeros((n_in,), dtype=torch.float32).pin_memory()
         self._pin_idx = torch.zeros((B,), dtype=torch.int32).pin_memory()
         self._pin_keep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
         self._done = torch.cuda.Event()
         self._pending = False
         self.replays = 0
-        self.host_syncs_per_step = [f"result rows: ONE D2H of {B * _lib.STREAM_ROW_FLOATS * 4} bytes into a pinned buffer, one wait for its event"]
+        what = "result rows and box tail" if track_boxes else "result rows"
+        self.host_syncs_per_step = [f"{what}: ONE D2H of {self._out.numel() * 4} bytes into a pinned buffer, one wait for its event"]
 
         # ---- warm up on a side stream (workspaces, packed weights: allocated outside the capture), then capture -- as graph.GraphedPath
         with torch.cuda.device(dev):
@@ -318,12 +457,28 @@ class PoseStream:
         self._pinned = [enc_model._ws, decoder._ws, list(enc_model._packed.values()), list(decoder._packed.values())]
         enc_model._frozen_by.add(self)
         decoder._frozen_by.add(self)
-        if select_k is not None:        # (the warm-up left its own result rows: the first step re-localises by appearance)
+        if select_k is not None or track_boxes:     # (the warm-up left its own result rows: the first step re-localises by appearance)
             self.rows.zero_()
+        if track_boxes:                 # ... and its own box: the first step holds the whole-frame default unless a detection is offered
+            self.state_box.copy_(self._default_box().expand(B, 4))
+            self.box_src.zero_()
+            self.track.zero_()
+            self.track[:, :4].copy_(self.state_box)
+
+    def _default_box(self) -> torch.Tensor:
+        side = float(min(self.H, self.W))
+        return torch.tensor([0.0, 0.0, side, side], device=self.frames.device)
 
     def _run(self):
         S = self.out_size
-        hip_ops.stream_windows(self.det_boxes, self.K, self.padding, S, self.windows, self.K_crop)
+        if self.track_boxes:
+            # the same first node, fed from the last step's result rows (read here, overwritten by bd_stream_results below)
+            hip_ops.stream_track_windows(self.rows, self.bbox_3d, self.K, self.det_boxes, self.det_valid, self.force, self.state_box,
+                                         self.padding, S, (self.H, self.W), self.max_rms_px, self.min_side_px, self.max_side_px,
+                                         windows=self.windows, K_crop=self.K_crop, box_src=self.box_src, keep_boxes=self.keep_boxes,
+                                         track=self.track)
+        else:
+            hip_ops.stream_windows(self.det_boxes, self.K, self.padding, S, self.windows, self.K_crop)
         crop_resize_frames(self.frames, self.windows, frame_idx=self.frame_idx, keep_boxes=self.keep_boxes, out_size=S, out=self.crops)
         fresh = self.encoder.predict(self.crops)
         if self.select_k is not None:
@@ -357,17 +512,23 @@ class PoseStream:
             raise ValueError(f"{name} must be {tuple(shape)} for this session of B = {self.B}, got {tuple(t.shape)}")
         return t
 
-    def step(self, frames, det_boxes, K, frame_idx=None, keep_boxes=None, wait: bool = True, relocalise=None) -> torch.Tensor:
+    def step(self, frames, det_boxes, K, frame_idx=None, keep_boxes=None, wait: bool = True, relocalise=None, det_valid=None) -> torch.Tensor:
         """One frame: frames uint8 (n_frames, H, W, 3) (or (H, W, 3) when n_frames == 1; a pinned host tensor is copied
         asynchronously, a device tensor on the device), det_boxes float (B, 4) x0 y0 x1 y1, K float (B, 3, 3) full-frame intrinsics
         (host or device), frame_idx integers (B,): the frame each sample reads (None: as in the last step; initially b % n_frames),
         keep_boxes integers (B, 4) when the session was built with use_keep_boxes (None: as in the last step; initially the whole
         frame), relocalise integers or bools (B,) for a session built with select_k: nonzero = choose this object's references by
-        appearance on THIS step, whatever its last pose (None: nobody).  Returns the pinned (B, 66) fp32 rows (the layout: include/boxdreamer_hip.h, bd_stream_results; ROW_* here) --
+        appearance on THIS step, whatever its last pose (None: nobody).  With track_boxes: det_boxes may be None (nobody has a
+        detection); det_valid integers or bools (B,), nonzero = det_boxes[b] is a detection (None: all ones when det_boxes is given,
+        all zeros otherwise); relocalise also means "distrust this object's last pose for its BOX on this step"; keep_boxes is refused
+        (the kernel writes them).  After the step `track_host` (B, 5) holds x0 y0 x1 y1 of the box each object used and its source
+        (BOX_DETECTOR / BOX_TRACKED / BOX_HELD), copied with the rows.  Returns the pinned (B, 66) fp32 rows (the layout: include/boxdreamer_hip.h, bd_stream_results; ROW_* here) --
         valid once the copy's event has completed: wait=True (the default) waits for it, wait=False leaves that to `wait()`."""
         B = self.B
+        det_valid = _step_boxes(self.track_boxes, det_boxes, det_valid, keep_boxes, B)
         frames = self._check_frames(frames)
-        self._check(det_boxes, (B, 4), True, "det_boxes")
+        if det_boxes is not None:
+            self._check(det_boxes, (B, 4), True, "det_boxes")
         self._check(K, (B, 3, 3), True, "K")
         if frame_idx is not None:
             self._check(frame_idx, (B,), False, "frame_idx")
@@ -376,19 +537,33 @@ class PoseStream:
                 raise ValueError("keep_boxes given to a session built with use_keep_boxes=False")
             self._check(keep_boxes, (B, 4), False, "keep_boxes")
         if relocalise is not None:
-            if self.select_k is None:
+            if self.select_k is None and not self.track_boxes:
                 raise ValueError("relocalise given to a session built without select_k: its references are fixed")
             relocalise = _relocalise(relocalise, B)
         if self._pending:               # (an un-waited step: its copies still read the pinned staging buffers)
             self._done.synchronize()
             self._pending = False
         self.frames.copy_(frames, non_blocking=True)
-        if det_boxes.is_cuda or K.is_cuda:
-            self.det_boxes.copy_(det_boxes, non_blocking=True)
+        on_device = K.is_cuda or (det_boxes is not None and det_boxes.is_cuda) or (det_valid is not None and det_valid.is_cuda)
+        if on_device:
+            if det_boxes is not None:
+                self.det_boxes.copy_(det_boxes, non_blocking=True)
             self.K.copy_(K, non_blocking=True)
+            if self.track_boxes:
+                if det_valid is not None:
+                    self.det_valid.copy_(det_valid != 0, non_blocking=True)
+                else:
+                    self.det_valid.fill_(0 if det_boxes is None else 1)
         else:
-            self._pin_f[:B * 4].view(B, 4).copy_(det_boxes)
-            self._pin_f[B * 4:].view(B, 3, 3).copy_(K)
+            if det_boxes is not None:
+                self._pin_f[:B * 4].view(B, 4).copy_(det_boxes)
+            self._pin_f[B * 4:B * 13].view(B, 3, 3).copy_(K)
+            if self.track_boxes:
+                pin_valid = self._pin_f[B * 13:].view(torch.int32)
+                if det_valid is not None:
+                    pin_valid.copy_(det_valid != 0)
+                else:
+                    pin_valid.fill_(0 if det_boxes is None else 1)
             self._in_f.copy_(self._pin_f, non_blocking=True)
         for given, pin, static in ((frame_idx, self._pin_idx, self.frame_idx), (keep_boxes, self._pin_keep, self.keep_boxes)):
             if given is None:
@@ -405,11 +580,11 @@ class PoseStream:
                 self._pin_force.copy_(relocalise != 0)
                 self.force.copy_(self._pin_force, non_blocking=True)
             self._forced = True
-        elif self.select_k is not None and self._forced:        # (the flags hold for one step)
+        elif self.force is not None and self._forced:           # (the flags hold for one step)
             self.force.zero_()
             self._forced = False
         self.graph.replay()
-        self.rows_host.copy_(self.rows, non_blocking=True)
+        self._out_host.copy_(self._out, non_blocking=True)
         self._done.record()
         self._pending = True
         self.replays += 1
@@ -424,12 +599,14 @@ class PoseStream:
             self._pending = False
         return self.rows_host
 
-    # -- a session that selects (select_k)
+    # -- a session that carries its last poses from frame to frame (select_k, track_boxes)
     def reset(self, poses=None) -> None:
         """Forget the last poses (enqueued on the current stream, nothing waits).  None: the result rows become zero, so the next step
         re-localises by appearance.  poses float (B, 4, 4), host or device: they become the last poses with ok = 1 and rms_px = 0 -- a
-        session resumed from a known pose, whose next "track" step ranks by distance to them."""
-        if self.select_k is None:
+        session resumed from a known pose, whose next "track" step ranks by distance to them.  With track_boxes: after reset() the
+        next step takes a detection or holds the last box (`state_box` is left alone); after reset(poses) its box is bbox_3d projected
+        with those poses and that step's K."""
+        if self.select_k is None and not self.track_boxes:
             raise ValueError("reset() on a session built without select_k: nothing is carried from frame to frame there")
         if poses is None:
             self.rows.zero_()

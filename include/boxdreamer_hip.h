@@ -641,6 +641,44 @@ int bd_stream_results(const float* poses, const float* rms_px, const float* kp_p
 int bd_stream_results_host(const float* poses, const float* rms_px, const float* kp_px, const int32_t* windows, const float* K,
                            const float* bbox_3d, int out_size, float* rows, int n);
 
+/* bd_stream_track_windows: a second form of the step's first node (stream.PoseStream(track_boxes=True)): every object's crop box comes
+ * from its OWN last pose while that pose is trusted, so a session needs no detector box per frame.  It replaces the reference demo's
+ * offline segmentation pass over the whole video (src/demo/demo.py:379-476, the box/ files its loop reads) by the rule the reference's
+ * OnePose data derives its boxes with (src/datasets/onepose.py:437-455: the min / max of the 8 projected corners of the 3-D box).  One
+ * object per lane, 64 lanes per workgroup, like bd_stream_windows; the _host form runs the same __host__ __device__ arithmetic.
+ * prev_rows fp32 [n, BD_STREAM_ROW_FLOATS]: the LAST step's result rows (read before this step's bd_stream_results overwrites them);
+ * bbox_3d fp32 [n, 8, 3]; K fp32 [n, 3, 3] of this frame; det_boxes fp32 [n, 4]; det_valid int32 [n]: nonzero = a detection is
+ * offered; force int32 [n]: nonzero = distrust this object's last pose on this step; state_box fp32 [n, 4]: the box used last step,
+ * READ AND WRITTEN (an object touches its own four floats only).
+ *   projection  the 8 corners through prev_rows[b][0:16] and K[b], the arithmetic of the row's box slots [50, 66) (one function
+ *               serves both); a corner with zc <= 0 is NaN;
+ *   tracked box (min u, min v, max u, max v) of those fp32 values;
+ *   valid       all 16 values finite, and in fp64: min(max, frame) - max(min, 0) >= min_side_px on both axes (the extent clipped to
+ *               [0, frame_w] x [0, frame_h]), max - min <= max_side_px on both axes (the unclipped extent);
+ *   trusted     prev ok == 1.0f, prev rms_px <= max_rms_px (a comparison: a NaN rms fails it), force[b] == 0 and valid -- the rule of
+ *               bd_stream_select_rows plus the geometry;
+ *   source      trusted: the tracked box, NOT clipped (the crop kernel pads with black), BD_STREAM_BOX_TRACKED; else det_valid[b] != 0:
+ *               det_boxes[b] as given, BD_STREAM_BOX_DETECTOR; else state_box[b], BD_STREAM_BOX_HELD.
+ * Written per object: windows int32 [n, 4] and K_crop fp32 [n, 3, 3] exactly as bd_stream_windows writes them for that box (a
+ * detector-sourced object gets its bits); state_box: the box; box_src int32 [n]: the source; keep_boxes int32 [n, 4] (may be NULL: not
+ * written): the four box components truncated towards zero in fp64 -- the object's own box, not squared (the reference's bbox_obj,
+ * src/datasets/base.py:550-552) -- all zeros when one of them is not finite or leaves int32; track fp32 [n, 5] (may be NULL: not
+ * written): x0 y0 x1 y1 of the box and the source as a float, the tail a session copies to the host with its result rows.
+ * Checked before any launch: a NULL pointer (but keep_boxes, track) BD_ERR_NULL; n < 0, n > 65535, out_size < 1, frame_h < 1,
+ * frame_w < 1, min_side_px or max_side_px not positive (a NaN included) BD_ERR_SHAPE; n == 0 returns BD_OK without a launch. */
+#define BD_STREAM_BOX_DETECTOR 0
+#define BD_STREAM_BOX_TRACKED 1
+#define BD_STREAM_BOX_HELD 2
+int bd_stream_track_windows(const float* prev_rows, const float* bbox_3d, const float* K, const float* det_boxes,
+                            const int32_t* det_valid, const int32_t* force, float* state_box, double padding, int out_size, int frame_h,
+                            int frame_w, float max_rms_px, double min_side_px, double max_side_px, int32_t* windows, float* K_crop,
+                            int32_t* box_src, int32_t* keep_boxes /* may be NULL */, float* track /* may be NULL */, int n, void* stream);
+int bd_stream_track_windows_host(const float* prev_rows, const float* bbox_3d, const float* K, const float* det_boxes,
+                                 const int32_t* det_valid, const int32_t* force, float* state_box, double padding, int out_size,
+                                 int frame_h, int frame_w, float max_rms_px, double min_side_px, double max_side_px, int32_t* windows,
+                                 float* K_crop, int32_t* box_src, int32_t* keep_boxes /* may be NULL */, float* track /* may be NULL */,
+                                 int n);
+
 /* bd_stream_select_rows: a streaming step's choice of references, on the device (stream.PoseStream(select_k=...)): each of the B
  * tracked objects owns a database of views, and every frame k of them are named in the decoder's source table by ONE launch, one
  * workgroup (4 waves) per object -- so a captured step replays unchanged while its references change.  Like bd_match_select_rows and
