@@ -65,7 +65,7 @@ def solve_poses_host(kp_px: np.ndarray, bbox_3d: np.ndarray, K: np.ndarray, work
         try:
             lib = _lib.load()
             kp32, p32, K32 = (np.ascontiguousarray(a, np.float32) for a in (kp_px, bbox_3d, K))
-            rc = lib.bd_solve_pnp_host(kp32.ctypes.data, p32.ctypes.data, K32.ctypes.data, n, kp32.shape[1], 30, out.ctypes.data,
+            rc = lib.bd_solve_pnp_host(kp32.ctypes.data, p32.ctypes.data, K32.ctypes.data, n, kp32.shape[1], pnp.LM_MAX_ITERS, out.ctypes.data,
                                        _host_workers() if workers is None else workers)
             if rc == 0:
                 return out
@@ -86,7 +86,7 @@ def solve_poses_host(kp_px: np.ndarray, bbox_3d: np.ndarray, K: np.ndarray, work
 PNP_DEVICE_FORMS = ("thread", "wave")
 
 
-def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tensor, iters: int = 30, form: str = "thread",
+def solve_poses_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: torch.Tensor, iters: int = pnp.LM_MAX_ITERS, form: str = "thread",
                        want_rms: bool = False):
     """kp_px [N,n,2], bbox_3d [N,n,3], K [N,3,3] on the GPU -> poses [N,4,4] on the GPU ([R|t], zeros on failure) -- the corners never
     leave the device ("next" row f3).  form="thread": `bd_solve_pnp`, one pose per thread in fp64.  form="wave": `bd_solve_pnp_wave`, one
@@ -151,7 +151,7 @@ def solve_poses_ransac_device(kp_px: torch.Tensor, bbox_3d: torch.Tensor, K: tor
     ws_bytes = int(lib.bd_solve_pnp_ransac_workspace_bytes(N, int(n_trials)))
     ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
     _lib.check(lib.bd_solve_pnp_ransac_wave(_lib.ptr(kp), _lib.ptr(b3), _lib.ptr(Kd), _lib.ptr(picks), N, R, int(n_trials), float(reproj_err),
-                                            float(confidence), 5, 30, _lib.ptr(poses), _lib.ptr(inl), _lib.ptr(rms), _lib.ptr(info),
+                                            float(confidence), 5, pnp.LM_MAX_ITERS, _lib.ptr(poses), _lib.ptr(inl), _lib.ptr(rms), _lib.ptr(info),
                                             _lib.ptr(ws), ws_bytes, _lib.stream()), "bd_solve_pnp_ransac_wave")
     return poses, inl.bool().reshape(N, R, 8), rms, info
 

@@ -430,7 +430,11 @@ int bd_render_corner_heatmaps(const float* corners, int n_groups, int group, int
  * the algorithm of cv2.solvePnP(SOLVEPNP_ITERATIVE) for non-planar points as restated in boxdreamer_amd/pnp.py
  * (replaces the per-sample host loop of src/models/utils/box_utils.py:139-199).  kp_px: fp32 [n_poses, n_points, 2] pixel
  * coordinates; pts3: fp32 [n_poses, n_points, 3]; K: fp32 [n_poses, 3, 3]; poses: fp32 [n_poses, 4, 4] = [R|t; 0 0 0 1],
- * all zeros where the solve fails.  6 <= n_points <= 64.
+ * all zeros where the solve fails -- a non-finite input, a degenerate DLT, or a pose that leaves a point at or behind the camera
+ * plane, or an iteration that has not converged at its cap.  6 <= n_points <= 64.  iters >= 100 is a CAP on the LM iterations (the
+ * callers pass 400): the iteration stops where the decrease its linearisation promises falls below 1e-12 of the error under weak damping
+ * (about ten iterations on clean corners), and a solve that reaches the cap without that has no pose.  iters < 100 is a BUDGET: the
+ * iterate is returned as it stands (0: the DLT start alone).
  * (One wavefront per pose instead of one thread: bd_solve_pnp_wave below.) */
 int bd_solve_pnp(const float* kp_px, const float* pts3, const float* K, int n_poses, int n_points, int iters,
                  float* poses, void* stream);
@@ -458,7 +462,7 @@ int bd_solve_pnp_host(const float* kp_px /*[host]*/, const float* pts3 /*[host]*
  *   pnp_ransac_final_kernel  one wavefront per sample: the selection of boxdreamer_amd/pnp.py solve_pnp_ransac in batches of 32 trials
  *                            (a batch's best = highest count, ties to the lowest index; it replaces the running best on a higher count
  *                            or an equal count with a lower error sum; need = ceil(log(1 - confidence) / log(max(1 - w^6, 1e-300)))
- *                            at inlier ratio w; stop at trials >= min(need, n_trials) or w >= 1), then the solve (final_iters; 30 in the
+ *                            at inlier ratio w; stop at trials >= min(need, n_trials) or w >= 1), then the solve (final_iters, a cap; 400 in the
  *                            host scheme) of the best hypothesis' inliers compacted in index order -- of ALL observations when the best count
  *                            is below 6, the inliers cover fewer than 6 distinct corners, an observation is not finite, or that solve fails.
  * No atomics, no workgroup waits for another, every sum in index order: a sample's bits depend neither on n_samples nor on its row.

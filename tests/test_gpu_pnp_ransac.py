@@ -45,13 +45,14 @@ def same_bits(a, b):
 
 
 def wave_on_the_mask(c, inl):
-    """bd_solve_pnp_wave per sample on the observations the mask keeps, in index order, the box corners tiled to match."""
+    """bd_solve_pnp_wave per sample on the observations the mask keeps, in index order, the box corners tiled to match, under the
+    iteration cap of the RANSAC's final solve (solve_poses_ransac_device passes pnp.LM_MAX_ITERS)."""
     R = c["rounds"]
     poses, rms = np.zeros((N, 4, 4), np.float32), np.zeros((N,), np.float32)
     for s in range(N):
         m = inl[s].astype(bool)
         kp, p3 = c["kp"][s].reshape(-1, 2)[m], np.tile(c["box"][s], (R, 1))[m]
-        p, r = solve_poses_device(f32(kp[None]), f32(p3[None]), f32(c["K"][s:s + 1]), iters=30, form="wave", want_rms=True)
+        p, r = solve_poses_device(f32(kp[None]), f32(p3[None]), f32(c["K"][s:s + 1]), iters=pnp.LM_MAX_ITERS, form="wave", want_rms=True)
         poses[s], rms[s] = p[0].cpu().numpy(), r[0].item()
     return poses, rms
 
