@@ -15,8 +15,10 @@
 // nearly planar box, a box 15 px across) against an independent fp64 minimiser of the pixel error.  In the well-posed regimes every form
 // reaches that minimum and the forms agree to 1e-4 (measured: ~1e-7, the fp32 output).  In the hard ones (thin, noise5, noise8, far) a
 // returned pose is stationary and in front of the camera, and up to 5 % may sit in another local minimum of the DLT start.  The forms
-// are the same rules throughout -- the stop rule (lm_converged), the start's repairs (the proper rotation after a sign flip,
-// depth_clear), the accept test -- but NOT the same bits: the 12 x 12 null vector comes from a cyclic Jacobi sweep here, a round-robin
+// are the same rules throughout, and the native forms share their text -- the DLT start with its repairs (dlt_start: the proper rotation
+// after a sign flip, depth_clear) and the LM rule (lm_propose, lm_accept, lm_finish: the stop rule lm_converged, the accept test, the
+// front test); the drivers (solve_one_pose, pnp_wave_solve) differ in the 12 x 12 eigen-solver and in how the per-point sums are spread
+// over lanes -- but NOT the same bits: the 12 x 12 null vector comes from a cyclic Jacobi sweep here, a round-robin
 // one in the wave form and LAPACK's SVD in numpy, and a last-bit difference at an accept / reject decision is amplified in the hard
 // regimes, where two forms may then settle in different minima.  (Before these tests the forms DID part systematically there: the
 // sign of the null vector, which each eigen-solver chooses freely, decided whether the "points in front" repair produced a proper
@@ -100,7 +102,8 @@ __host__ __device__ void rodrigues(const double* rv, double* R) {
         }
 }
 
-__host__ __device__ void rvec_from_R(const double* R, double* rv) {
+// (no dynamic index, here and in solve6: in the wave kernels, which have no scratch, the arrays stay in registers)
+__host__ __device__ inline void rvec_from_R(const double* R, double* rv) {
     double c = (R[0] + R[4] + R[8] - 1.0) / 2.0;
     c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
     const double th = acos(c);
@@ -109,10 +112,11 @@ __host__ __device__ void rvec_from_R(const double* R, double* rv) {
         double A[9];
         for (int i = 0; i < 9; ++i) A[i] = (R[i] + (i % 4 == 0 ? 1.0 : 0.0)) / 2.0;
         int k = 0;
-        if (A[4] > A[k * 4]) k = 1;
-        if (A[8] > A[k * 4]) k = 2;
-        const double d = sqrt(A[k * 4] > 1e-12 ? A[k * 4] : 1e-12);
-        for (int i = 0; i < 3; ++i) rv[i] = A[i * 3 + k] / d * th;
+        double dk = A[0];
+        if (A[4] > dk) { k = 1; dk = A[4]; }
+        if (A[8] > dk) { k = 2; dk = A[8]; }
+        const double d = sqrt(dk > 1e-12 ? dk : 1e-12);
+        for (int i = 0; i < 3; ++i) rv[i] = (k == 0 ? A[i * 3] : (k == 1 ? A[i * 3 + 1] : A[i * 3 + 2])) / d * th;
         return;
     }
     const double f = th / (2.0 * sin(th));
@@ -137,24 +141,34 @@ __host__ __device__ bool residuals(const double* x, const double* p3, const doub
     return ok;
 }
 
-// solve the 6 x 6 system H d = g (partial pivoting); false if singular
-__host__ __device__ bool solve6(double* H, double* g, double* d) {
+// solve the 6 x 6 system H d = g (partial pivoting; the pivot row is swapped in through selects); false if singular
+__host__ __device__ inline bool solve6(double (&H)[36], double (&g)[6], double (&d)[6]) {
+#pragma unroll
     for (int c = 0; c < 6; ++c) {
         int piv = c;
-        for (int r = c + 1; r < 6; ++r) if (fabs(H[r * 6 + c]) > fabs(H[piv * 6 + c])) piv = r;
-        if (fabs(H[piv * 6 + c]) < 1e-300) return false;
-        if (piv != c) {
-            for (int k = 0; k < 6; ++k) { const double t = H[c * 6 + k]; H[c * 6 + k] = H[piv * 6 + k]; H[piv * 6 + k] = t; }
-            const double t = g[c]; g[c] = g[piv]; g[piv] = t;
+        double best = fabs(H[c * 6 + c]);
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) if (fabs(H[r * 6 + c]) > best) { piv = r; best = fabs(H[r * 6 + c]); }
+        if (best < 1e-300) return false;
+#pragma unroll
+        for (int r = c + 1; r < 6; ++r) {
+            const bool sw = piv == r;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) { const double a = H[c * 6 + k], b = H[r * 6 + k]; H[c * 6 + k] = sw ? b : a; H[r * 6 + k] = sw ? a : b; }
+            const double a = g[c], b = g[r]; g[c] = sw ? b : a; g[r] = sw ? a : b;
         }
+#pragma unroll
         for (int r = c + 1; r < 6; ++r) {
             const double f = H[r * 6 + c] / H[c * 6 + c];
+#pragma unroll
             for (int k = c; k < 6; ++k) H[r * 6 + k] -= f * H[c * 6 + k];
             g[r] -= f * g[c];
         }
     }
+#pragma unroll
     for (int r = 5; r >= 0; --r) {
         double s = g[r];
+#pragma unroll
         for (int k = r + 1; k < 6; ++k) s -= H[r * 6 + k] * d[k];
         d[r] = s / H[r * 6 + r];
     }
@@ -180,12 +194,152 @@ __host__ __device__ inline bool lm_converged(double pred, double e0) { return pr
 constexpr int LM_STRICT_ITERS = 100;
 __host__ __device__ inline bool lm_unfinished(bool converged, int iters) { return !converged && iters >= LM_STRICT_ITERS; }
 
+// The Levenberg-Marquardt rule of every form, once.  A driver owns the loop over `iters` and how the sums are produced -- serial loops
+// in the thread form, phases over the lanes in the wave form: per iteration H = J^T J, g = -J^T r and e0 = |r|^2 at L.x go to
+// lm_propose; where that answers LM_TRY the driver evaluates e1 = |r|^2 at L.xn and lm_accept takes or rejects the step; after the
+// loop lm_finish says whether there is a pose.  Every decision goes through run.uniform() where it is taken: in the wave form that makes
+// it a scalar branch (decided on lane values it cost 2 % of a launch that runs to the cap); the thread form passes OneLane.
+struct LmState {
+    double x[6], xn[6];               // the iterate (rvec, t) and the candidate of the last lm_propose
+    double lam = 1e-3;
+    bool converged = false;
+};
+enum LmNext { LM_TRY, LM_AGAIN, LM_STOP };      // evaluate L.xn; go round again at the same x; leave the loop
+struct OneLane { __host__ __device__ bool uniform(bool b) const { return b; } };      // the thread form's `run`: a pose is one lane's
+
+// H and g are destroyed.  The damping scales with the diagonal (floored at 1e-12, so a zero column of J is damped too).
+template <class Run> __host__ __device__ inline LmNext lm_propose(const Run& run, LmState& L, double (&H)[36], double (&g)[6], double e0) {
+    double g0[6], D[6], step[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) { g0[a] = g[a]; D[a] = H[a * 6 + a] + 1e-12; H[a * 6 + a] += L.lam * D[a]; }
+    if (!run.uniform(solve6(H, g, step))) return LM_STOP;                  // singular: not converged
+    double pred = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { L.xn[k] = L.x[k] + step[k]; pred += step[k] * (g0[k] + L.lam * D[k] * step[k]); }
+    if (!run.uniform(lm_converged(pred, e0))) return LM_TRY;
+    if (L.lam <= 1e-3) { L.converged = true; return LM_STOP; }
+    L.lam = 1e-3;
+    return LM_AGAIN;
+}
+
+// (a non-finite residual at xn makes e1 inf or NaN, and the step is rejected)
+template <class Run> __host__ __device__ inline bool lm_accept(const Run& run, LmState& L, double e0, double e1) {
+    if (!run.uniform(e1 < e0)) { L.lam *= 10.0; return false; }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) L.x[k] = L.xn[k];
+    L.lam = L.lam * 0.3 > 1e-9 ? L.lam * 0.3 : 1e-9;
+    return true;
+}
+
+// R = the rotation of L.x.  False: no pose -- a minimum was asked for and not reached (lm_unfinished), or a point lies at or behind the
+// camera plane (zeros, like a NaN corner).  pts: point i at pts[i * stride .. + 2].
+template <class Run> __host__ __device__ inline bool lm_finish(const Run& run, const LmState& L, int iters, const double* pts, int stride, int n, double (&R)[9]) {
+    if (run.uniform(lm_unfinished(L.converged, iters))) return false;
+    rodrigues(L.x, R);
+    bool front = true;
+    for (int i = 0; i < n; ++i) {                              // (no early exit: the loads of a wave's 64 points overlap)
+        const double z = R[6] * pts[i * stride] + R[7] * pts[i * stride + 1] + R[8] * pts[i * stride + 2] + L.x[5];
+        front = front && z > 0.0;
+    }
+    return run.uniform(front);
+}
+
 // The DLT start's translation t, given d = max over the points of -(R p)_z: the nearest point lies at depth t_z - d.  Where that is not
 // positive, t is stretched along its own direction (the box centre keeps its pixel) to t_z = 2 d; a t_z <= 0 is replaced by 2 d.
 __host__ __device__ inline void depth_clear(double* t, double d) {
     if (!(d > 0.0) || t[2] > d) return;
     if (t[2] > 0.0) { const double s = 2.0 * d / t[2]; t[0] *= s; t[1] *= s; t[2] *= s; }
     else t[2] = 2.0 * d;
+}
+
+// The DLT start of every form: x = (rvec, t) from the null vector P (3 x 4, row-major) of the DLT system, the points' mean and the
+// points (point i at pts[i * stride .. + 2]); false where P[:, :3] has no rank 3.  Every index is static but the one over the points.
+__host__ __device__ inline bool dlt_start(const double (&P)[12], const double (&mean)[3], const double* pts, int stride, int n, double (&x)[6]) {
+    // ---- nearest rotation to M = P[:, :3]: M = U S V^T, R = U V^T (through the eigen-decomposition of M^T M)
+    double M[9], MtM[9], V[9], s2[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) M[i * 3 + j] = P[i * 4 + j];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s += M[k * 3 + i] * M[k * 3 + j];
+            MtM[i * 3 + j] = s;
+        }
+    jacobi_eig<3>(MtM, V, s2);
+    auto order = [&](int a, int b) {                           // descending singular values (numpy's order), as compare-and-swaps
+        if (s2[b] > s2[a]) {
+            const double t = s2[a]; s2[a] = s2[b]; s2[b] = t;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { const double u = V[i * 3 + a]; V[i * 3 + a] = V[i * 3 + b]; V[i * 3 + b] = u; }
+        }
+    };
+    order(0, 1); order(0, 2); order(1, 2);
+    double sig[3], U[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sig[c] = sqrt(s2[c] > 0 ? s2[c] : 0.0);
+    if (!(sig[2] > 0.0)) return false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s += M[i * 3 + k] * V[k * 3 + c];
+            U[i * 3 + c] = s / sig[c];
+        }
+    double R[9], t[3];
+    auto UVt = [&]() {
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s += U[i * 3 + c] * V[j * 3 + c];
+                R[i * 3 + j] = s;
+            }
+    };
+    auto negate_R = [&]() {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) R[i] = -R[i];
+    };
+    UVt();
+    // ---- sign fixes
+    double scale = (sig[0] + sig[1] + sig[2]) / 3.0;
+    if (det3(R) < 0) { negate_R(); scale = -scale; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = P[i * 4 + 3] / scale;
+    const double zc = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + t[2];
+    if (zc < 0) {                                              // points must be in front of the camera
+        negate_R();
+#pragma unroll
+        for (int i = 0; i < 3; ++i) t[i] = -t[i];
+        // -R is improper: the nearest PROPER rotation to the negated M is -(U' V^T), U' = U with its last column negated, where
+        // det(U V^T) was +1, and U' V^T where it was -1 (the sign of the null vector P, which the eigen-solver is free to choose)
+        if (det3(R) < 0) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) U[i * 3 + 2] = -U[i * 3 + 2];
+            UVt();
+            if (det3(R) < 0) negate_R();
+        }
+    }
+    {   // a start with a point at or behind the camera plane (noisy corners of a far or flat box) sits in the basin of a mirrored pose
+        // that LM cannot leave: move it out along its own viewing ray until the nearest point is as deep as the model is (depth_clear)
+        double d = -1e300;
+        for (int i = 0; i < n; ++i) {
+            const double q = -(R[6] * pts[i * stride] + R[7] * pts[i * stride + 1] + R[8] * pts[i * stride + 2]);
+            d = q > d ? q : d;
+        }
+        depth_clear(t, d);
+    }
+    rvec_from_R(R, x);
+    x[3] = t[0]; x[4] = t[1]; x[5] = t[2];
+    return true;
 }
 
 // One pose: kp [n, 2] pixels, pts3 [n, 3], Kp [3, 3] -> out [4, 4] = [R|t; 0 0 0 1], all zeros where the solve fails.  The same code
@@ -221,74 +375,17 @@ __host__ __device__ void solve_one_pose(const float* kp, const float* pts3, cons
     for (int i = 1; i < 12; ++i) if (w[i] < w[kmin]) kmin = i;
     double P[12];
     for (int i = 0; i < 12; ++i) P[i] = V[i * 12 + kmin];
-    // ---- nearest rotation to M = P[:, :3]: M = U S V^T, R = U V^T (through the eigen-decomposition of M^T M)
-    double M[9], MtM[9], V3[9], s2[3];
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) M[i * 3 + j] = P[i * 4 + j];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double s = 0.0;
-            for (int k = 0; k < 3; ++k) s += M[k * 3 + i] * M[k * 3 + j];
-            MtM[i * 3 + j] = s;
-        }
-    jacobi_eig<3>(MtM, V3, s2);
-    int ord[3] = {0, 1, 2};                                   // descending singular values (numpy's order)
-    for (int a = 0; a < 2; ++a) for (int b = a + 1; b < 3; ++b) if (s2[ord[b]] > s2[ord[a]]) { const int t = ord[a]; ord[a] = ord[b]; ord[b] = t; }
-    double sig[3], U[9], Vs[9];
-    for (int c = 0; c < 3; ++c) {
-        sig[c] = sqrt(s2[ord[c]] > 0 ? s2[ord[c]] : 0.0);
-        for (int i = 0; i < 3; ++i) Vs[i * 3 + c] = V3[i * 3 + ord[c]];
-    }
-    if (!(sig[2] > 0.0)) return;
-    for (int c = 0; c < 3; ++c)
-        for (int i = 0; i < 3; ++i) {
-            double s = 0.0;
-            for (int k = 0; k < 3; ++k) s += M[i * 3 + k] * Vs[k * 3 + c];
-            U[i * 3 + c] = s / sig[c];
-        }
-    double R[9], t[3];
-    auto UVt = [&]() {
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-                for (int c = 0; c < 3; ++c) s += U[i * 3 + c] * Vs[j * 3 + c];
-                R[i * 3 + j] = s;
-            }
-    };
-    UVt();
-    double scale = (sig[0] + sig[1] + sig[2]) / 3.0;
-    if (det3(R) < 0) { for (int i = 0; i < 9; ++i) R[i] = -R[i]; scale = -scale; }
-    for (int i = 0; i < 3; ++i) t[i] = P[i * 4 + 3] / scale;
-    const double zc = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + t[2];
-    if (zc < 0) {                                             // points must be in front of the camera
-        for (int i = 0; i < 9; ++i) R[i] = -R[i];
-        for (int i = 0; i < 3; ++i) t[i] = -t[i];
-        // -R is improper: the nearest PROPER rotation to the negated M is -(U' V^T), U' = U with its last column negated, where
-        // det(U V^T) was +1, and U' V^T where it was -1 (the sign of the null vector P, which the eigen-solver is free to choose)
-        if (det3(R) < 0) {
-            for (int i = 0; i < 3; ++i) U[i * 3 + 2] = -U[i * 3 + 2];
-            UVt();
-            if (det3(R) < 0) for (int i = 0; i < 9; ++i) R[i] = -R[i];
-        }
-    }
-    {   // a start with a point at or behind the camera plane (noisy corners of a far or flat box) sits in the basin of a mirrored pose
-        // that LM cannot leave: move it out along its own viewing ray until the nearest point is as deep as the model is (depth_clear)
-        double d = -1e300;
-        for (int i = 0; i < n; ++i) { const double q = -(R[6] * p3[i * 3] + R[7] * p3[i * 3 + 1] + R[8] * p3[i * 3 + 2]); d = q > d ? q : d; }
-        depth_clear(t, d);
-    }
-    // ---- Levenberg-Marquardt on (rvec, t)
-    double x[6], r[MAXPTS * 2], rn[MAXPTS * 2], J[MAXPTS * 2 * 6];
-    rvec_from_R(R, x);
-    x[3] = t[0]; x[4] = t[1]; x[5] = t[2];
+    LmState L;
+    if (!dlt_start(P, mean, p3, 3, n, L.x)) return;
+    // ---- Levenberg-Marquardt on (rvec, t): J, J^T J, g and the errors in serial loops, all of them again in every iteration
+    double r[MAXPTS * 2], rn[MAXPTS * 2], J[MAXPTS * 2 * 6];
     const double fgm = sqrt(fabs(fx * fy)), wx = fgm > 0 ? fabs(fx) / fgm : 1.0, wy = fgm > 0 ? fabs(fy) / fgm : 1.0;
-    if (!residuals(x, p3, p2n, n, r, wx, wy)) return;
-    double lam = 1e-3;
+    if (!residuals(L.x, p3, p2n, n, r, wx, wy)) return;
     const int m = 2 * n;
-    bool converged = false;
     for (int it = 0; it < iters; ++it) {
         for (int j = 0; j < 6; ++j) {
             double xd[6];
-            for (int k = 0; k < 6; ++k) xd[k] = x[k];
+            for (int k = 0; k < 6; ++k) xd[k] = L.x[k];
             xd[j] += 1e-6;
             residuals(xd, p3, p2n, n, rn, wx, wy);
             for (int i = 0; i < m; ++i) {
@@ -296,7 +393,7 @@ __host__ __device__ void solve_one_pose(const float* kp, const float* pts3, cons
                 J[i * 6 + j] = finite_d(d) ? d : 0.0;
             }
         }
-        double H[36], g[6], step[6];
+        double H[36], g[6], e0 = 0.0, e1 = 0.0;
         for (int a = 0; a < 6; ++a) {
             double s = 0.0;
             for (int i = 0; i < m; ++i) s += J[i * 6 + a] * r[i];
@@ -307,34 +404,20 @@ __host__ __device__ void solve_one_pose(const float* kp, const float* pts3, cons
                 H[a * 6 + b] = h;
             }
         }
-        double g0[6], D[6];
-        for (int a = 0; a < 6; ++a) { g0[a] = g[a]; D[a] = H[a * 6 + a] + 1e-12; H[a * 6 + a] += lam * D[a]; }
-        if (!solve6(H, g, step)) break;
-        double xn[6], e0 = 0.0, e1 = 0.0, pred = 0.0;
-        for (int k = 0; k < 6; ++k) { xn[k] = x[k] + step[k]; pred += step[k] * (g0[k] + lam * D[k] * step[k]); }
         for (int i = 0; i < m; ++i) e0 += r[i] * r[i];
-        if (lm_converged(pred, e0)) {                         // the stop rule (see lm_converged)
-            if (lam <= 1e-3) { converged = true; break; }
-            lam = 1e-3;
-            continue;
-        }
-        const bool fin = residuals(xn, p3, p2n, n, rn, wx, wy);
+        const LmNext next = lm_propose(OneLane(), L, H, g, e0);
+        if (next == LM_STOP) break;
+        if (next == LM_AGAIN) continue;
+        residuals(L.xn, p3, p2n, n, rn, wx, wy);
         for (int i = 0; i < m; ++i) e1 += rn[i] * rn[i];
-        if (fin && e1 < e0) {
-            for (int k = 0; k < 6; ++k) x[k] = xn[k];
+        if (lm_accept(OneLane(), L, e0, e1))
             for (int i = 0; i < m; ++i) r[i] = rn[i];
-            lam = lam * 0.3 > 1e-9 ? lam * 0.3 : 1e-9;
-        } else {
-            lam *= 10.0;
-        }
     }
-    if (lm_unfinished(converged, iters)) return;              // a minimum was asked for and not reached: no pose
-    rodrigues(x, R);
-    for (int i = 0; i < n; ++i)                               // a point at or behind the camera plane: no pose (zeros), like a NaN corner
-        if (!(R[6] * p3[i * 3] + R[7] * p3[i * 3 + 1] + R[8] * p3[i * 3 + 2] + x[5] > 0.0)) return;
+    double R[9];
+    if (!lm_finish(OneLane(), L, iters, p3, 3, n, R)) return;
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) out[i * 4 + j] = (float)R[i * 3 + j];
-        out[i * 4 + 3] = (float)x[3 + i];
+        out[i * 4 + 3] = (float)L.x[3 + i];
     }
     out[15] = 1.f;
 }
@@ -348,14 +431,14 @@ __global__ __launch_bounds__(64) void pnp_kernel(const float* __restrict__ kp, c
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------
-// The wave form: ONE wavefront (64 lanes) per pose, solve_one_pose's algorithm step for step in fp64.  The solver is written as a
+// The wave form: ONE wavefront (64 lanes) per pose, solve_one_pose's algorithm in fp64 around the same dlt_start and LM rule.  The solver is written as a
 // DRIVER (pnp_wave_solve) around PHASES.  A phase is a function of (lane, shared state): it reads what earlier phases left in the
 // shared state and writes locations no other lane of the same phase reads; `run(phase)` executes it on all 64 lanes between two
 // barriers.  Driver code between the phases is executed by every lane on the same shared values in the same order, so every lane holds
 // the same bits; the values that decide a branch or a loop exit go through run.uniform() (v_readfirstlane) on top of that.  Nothing is
 // indexed dynamically outside the shared state (LDS): the kernel has no scratch.  Every sum runs in index order without atomics, and a
 // workgroup is one pose, so a pose's bits do not depend on the batch.  On the host the same driver runs with a runner that loops over
-// the 64 lanes (tools/pnp_wave_hostcheck.cpp: the index arithmetic under the address / undefined-behaviour sanitizers, no GPU).
+// the 64 lanes (LoopRun; tools/pnp_wave_hostcheck.cpp: the index arithmetic under the address / undefined-behaviour sanitizers, no GPU).
 struct WaveState {
     double p4[MAXPTS * 4];            // (X, Y, Z, 1) per point
     double p2n[MAXPTS * 2];           // normalised image coordinates
@@ -381,60 +464,6 @@ template <int N> __host__ __device__ inline void tri_entry(int e, int& i, int& j
     for (int k = 0; k < N - 1; ++k)
         if (e >= N - i) { e -= N - i; ++i; }
     j = i + e;
-}
-
-__host__ __device__ inline void rvec_from_R_static(const double* R, double* rv) {      // rvec_from_R without a dynamic index
-    double c = (R[0] + R[4] + R[8] - 1.0) / 2.0;
-    c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
-    const double th = acos(c);
-    if (th < 1e-8) { rv[0] = rv[1] = rv[2] = 0.0; return; }
-    if (3.14159265358979323846 - th < 1e-4) {
-        double A[9];
-        for (int i = 0; i < 9; ++i) A[i] = (R[i] + (i % 4 == 0 ? 1.0 : 0.0)) / 2.0;
-        int k = 0;
-        double dk = A[0];
-        if (A[4] > dk) { k = 1; dk = A[4]; }
-        if (A[8] > dk) { k = 2; dk = A[8]; }
-        const double d = sqrt(dk > 1e-12 ? dk : 1e-12);
-        for (int i = 0; i < 3; ++i) rv[i] = (k == 0 ? A[i * 3] : (k == 1 ? A[i * 3 + 1] : A[i * 3 + 2])) / d * th;
-        return;
-    }
-    const double f = th / (2.0 * sin(th));
-    rv[0] = (R[7] - R[5]) * f; rv[1] = (R[2] - R[6]) * f; rv[2] = (R[3] - R[1]) * f;
-}
-
-// solve6 with every index static (the pivot row is swapped in through selects): H, g, d stay in registers
-__host__ __device__ inline bool solve6_static(double (&H)[36], double (&g)[6], double (&d)[6]) {
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        int piv = c;
-        double best = fabs(H[c * 6 + c]);
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) if (fabs(H[r * 6 + c]) > best) { piv = r; best = fabs(H[r * 6 + c]); }
-        if (best < 1e-300) return false;
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            const bool sw = piv == r;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) { const double a = H[c * 6 + k], b = H[r * 6 + k]; H[c * 6 + k] = sw ? b : a; H[r * 6 + k] = sw ? a : b; }
-            const double a = g[c], b = g[r]; g[c] = sw ? b : a; g[r] = sw ? a : b;
-        }
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            const double f = H[r * 6 + c] / H[c * 6 + c];
-#pragma unroll
-            for (int k = c; k < 6; ++k) H[r * 6 + k] -= f * H[c * 6 + k];
-            g[r] -= f * g[c];
-        }
-    }
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {
-        double s = g[r];
-#pragma unroll
-        for (int k = r + 1; k < 6; ++k) s -= H[r * 6 + k] * d[k];
-        d[r] = s / H[r * 6 + r];
-    }
-    return true;
 }
 
 // One pose by one "wave" of 64 lanes.  Returns false where solve_one_pose leaves zeros; on success S.out holds the 4 x 4 pose and
@@ -525,91 +554,11 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
     double P[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) P[i] = S.V[cur][i * 12 + kmin];
-    // ---- 3. nearest rotation to M = P[:, :3] (every lane, in registers)
-    double M[9], MtM[9], V3[9], s2[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) M[i * 3 + j] = P[i * 4 + j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s += M[k * 3 + i] * M[k * 3 + j];
-            MtM[i * 3 + j] = s;
-        }
-    jacobi_eig<3>(MtM, V3, s2);
-    auto order = [&](int a, int b) {                           // descending: solve_one_pose's `ord` sort as compare-and-swaps
-        if (s2[b] > s2[a]) {
-            const double t = s2[a]; s2[a] = s2[b]; s2[b] = t;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { const double u = V3[i * 3 + a]; V3[i * 3 + a] = V3[i * 3 + b]; V3[i * 3 + b] = u; }
-        }
-    };
-    order(0, 1); order(0, 2); order(1, 2);
-    double sig[3], U[9];
-    const double* Vs = V3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sig[c] = sqrt(s2[c] > 0 ? s2[c] : 0.0);
-    if (!run.uniform(sig[2] > 0.0)) return false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s += M[i * 3 + k] * Vs[k * 3 + c];
-            U[i * 3 + c] = s / sig[c];
-        }
-    double R[9], t[3];
-    auto UVt = [&]() {
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) s += U[i * 3 + c] * Vs[j * 3 + c];
-                R[i * 3 + j] = s;
-            }
-    };
-    UVt();
-    // ---- 4. sign fixes
-    double scale = (sig[0] + sig[1] + sig[2]) / 3.0;
-    if (det3(R) < 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = -R[i];
-        scale = -scale;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t[i] = P[i * 4 + 3] / scale;
-    const double zc = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + t[2];
-    if (zc < 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = -R[i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) t[i] = -t[i];
-        if (det3(R) < 0) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) U[i * 3 + 2] = -U[i * 3 + 2];
-            UVt();
-            if (det3(R) < 0) {                                 // (solve_one_pose: the proper rotation nearest to the negated M)
-#pragma unroll
-                for (int i = 0; i < 9; ++i) R[i] = -R[i];
-            }
-        }
-    }
-    {   // (solve_one_pose: a start with a point at or behind the camera plane moves out along its viewing ray)
-        double d = -1e300;
-        for (int i = 0; i < n; ++i) { const double q = -(R[6] * S.p4[i * 4] + R[7] * S.p4[i * 4 + 1] + R[8] * S.p4[i * 4 + 2]); d = q > d ? q : d; }
-        depth_clear(t, d);
-    }
-    // ---- 5. / 6. Levenberg-Marquardt on (rvec, t)
-    double x[6];
-    rvec_from_R_static(R, x);
-    x[3] = t[0]; x[4] = t[1]; x[5] = t[2];
+    // ---- 3. / 4. the DLT start (every lane, in registers)
+    LmState L;
+    if (!run.uniform(dlt_start(P, mean, S.p4, 4, n, L.x))) return false;
+    // ---- 5. / 6. Levenberg-Marquardt on (rvec, t): J, J^T J and g in phases over the lanes, kept while x stays; e0 carried along
+    double R[9];
     const double fgm = sqrt(fabs(fx * fy)), wx = fgm > 0 ? fabs(fx) / fgm : 1.0, wy = fgm > 0 ? fabs(fy) / fgm : 1.0;
     int rb = 0;
     double tr[3];
@@ -623,22 +572,20 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
             S.r[buf][2 * lane + 1] = (pcy / pcz - S.p2n[2 * lane + 1]) * wy;
         });
     };
-    rodrigues(x, R);
-    tr[0] = x[3]; tr[1] = x[4]; tr[2] = x[5];
+    rodrigues(L.x, R);
+    tr[0] = L.x[3]; tr[1] = L.x[4]; tr[2] = L.x[5];
     residuals_into(rb);
     double e0 = 0.0;
     bool fin = true;
     for (int i = 0; i < m; ++i) { const double v = S.r[rb][i]; fin = fin && finite_d(v); e0 += v * v; }
     if (!run.uniform(fin)) return false;
-    double lam = 1e-3;
     bool fresh = true;                                         // x moved: J, J^T J and g are rebuilt (a rejected step keeps them)
-    bool converged = false;
     for (int it = 0; it < iters; ++it) {
         if (fresh) {
             run([&](int lane) {                                // lanes 0 .. 5: [R | t] of x + h e_lane
                 double xd[6], Rd[9];
 #pragma unroll
-                for (int k = 0; k < 6; ++k) xd[k] = x[k] + (k == lane ? 1e-6 : 0.0);
+                for (int k = 0; k < 6; ++k) xd[k] = L.x[k] + (k == lane ? 1e-6 : 0.0);
                 rodrigues(xd, Rd);
                 if (lane >= 6) return;
 #pragma unroll
@@ -675,7 +622,7 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
             });
             fresh = false;
         }
-        double H[36], g[6], stp[6];
+        double H[36], g[6], e1 = 0.0;
         {
             int e = 0;
 #pragma unroll
@@ -683,40 +630,27 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
 #pragma unroll
                 for (int b = a; b < 6; ++b, ++e) { H[a * 6 + b] = S.Hg[e]; H[b * 6 + a] = S.Hg[e]; }
         }
-        double g0[6], D[6];
 #pragma unroll
-        for (int a = 0; a < 6; ++a) { g[a] = g0[a] = S.Hg[21 + a]; D[a] = H[a * 6 + a] + 1e-12; H[a * 6 + a] += lam * D[a]; }
-        if (!run.uniform(solve6_static(H, g, stp))) break;
-        double xn[6], e1 = 0.0, pred = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { xn[k] = x[k] + stp[k]; pred += stp[k] * (g0[k] + lam * D[k] * stp[k]); }
-        if (run.uniform(lm_converged(pred, e0))) {             // the stop rule (see lm_converged)
-            if (lam <= 1e-3) { converged = true; break; }
-            lam = 1e-3;
-            continue;
-        }
-        rodrigues(xn, R);
-        tr[0] = xn[3]; tr[1] = xn[4]; tr[2] = xn[5];
+        for (int a = 0; a < 6; ++a) g[a] = S.Hg[21 + a];
+        const LmNext next = lm_propose(run, L, H, g, e0);
+        if (next == LM_STOP) break;
+        if (next == LM_AGAIN) continue;
+        rodrigues(L.xn, R);
+        tr[0] = L.xn[3]; tr[1] = L.xn[4]; tr[2] = L.xn[5];
         residuals_into(rb ^ 1);
-        for (int i = 0; i < m; ++i) e1 += S.r[rb ^ 1][i] * S.r[rb ^ 1][i];      // (a non-finite residual makes e1 < e0 false)
-        if (run.uniform(e1 < e0)) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) x[k] = xn[k];
+        for (int i = 0; i < m; ++i) e1 += S.r[rb ^ 1][i] * S.r[rb ^ 1][i];
+        if (lm_accept(run, L, e0, e1)) {
             rb ^= 1;
             e0 = e1;
-            lam = lam * 0.3 > 1e-9 ? lam * 0.3 : 1e-9;
             fresh = true;
-        } else {
-            lam *= 10.0;
         }
     }
-    if (run.uniform(lm_unfinished(converged, iters))) return false;      // a minimum was asked for and not reached: no pose
-    rodrigues(x, R);
+    if (!lm_finish(run, L, iters, S.p4, 4, n, R)) return false;
     if (Rt64) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) Rt64[i] = R[i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) Rt64[9 + i] = x[3 + i];
+        for (int i = 0; i < 3; ++i) Rt64[9 + i] = L.x[3 + i];
     }
     // ---- the pose, and its pixel reprojection error: lane = point, summed in index order
     run([&](int lane) {
@@ -725,7 +659,7 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
             for (int i = 0; i < 3; ++i) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) S.out[i * 4 + j] = (float)R[i * 3 + j];
-                S.out[i * 4 + 3] = (float)x[3 + i];
+                S.out[i * 4 + 3] = (float)L.x[3 + i];
                 S.out[12 + i] = 0.f;
             }
             S.out[15] = 1.f;
@@ -735,19 +669,15 @@ __host__ __device__ inline bool pnp_wave_solve(const Run& run, WaveState& S, con
 #pragma unroll
         for (int i = 0; i < 9; ++i) Q[i] = (double)(float)R[i];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) tq[i] = (double)(float)x[3 + i];
+        for (int i = 0; i < 3; ++i) tq[i] = (double)(float)L.x[3 + i];
         const double X = S.p4[lane * 4], Y = S.p4[lane * 4 + 1], Z = S.p4[lane * 4 + 2];
         const double pcx = Q[0] * X + Q[1] * Y + Q[2] * Z + tq[0], pcy = Q[3] * X + Q[4] * Y + Q[5] * Z + tq[1],
                      pcz = Q[6] * X + Q[7] * Y + Q[8] * Z + tq[2];
         const double du = (double)kp[lane * 2] - (fx * (pcx / pcz) + cx), dv = (double)kp[lane * 2 + 1] - (fy * (pcy / pcz) + cy);
-        S.r[rb ^ 1][lane] = du * du + dv * dv;
-        S.r[rb][lane] = R[6] * X + R[7] * Y + R[8] * Z + x[5];  // depth under the fp64 pose (the residuals at x are no longer needed)
+        S.r[0][lane] = du * du + dv * dv;                      // (the residuals are no longer needed)
     });
-    bool front = true;                                         // a point at or behind the camera plane: no pose, like a NaN corner
-    for (int i = 0; i < n; ++i) front = front && S.r[rb][i] > 0.0;
-    if (!run.uniform(front)) return false;
     double ss = 0.0;
-    for (int i = 0; i < n; ++i) ss += S.r[rb ^ 1][i];
+    for (int i = 0; i < n; ++i) ss += S.r[0][i];
     *rms_out = sqrt(ss / n);
     return true;
 }

@@ -1,6 +1,6 @@
 // Host check of the wave form of the PnP solver (boxdreamer_amd/csrc/pnp.hip: pnp_wave_solve): the driver and its phases are
-// __host__ __device__, so the 64 lanes of a "wave" can be run in a plain loop on the CPU, phase by phase, against solve_one_pose (the
-// host form).  Built with the address and undefined-behaviour sanitizers this finds an index error in the shared state without a GPU.
+// __host__ __device__, so the 64 lanes of a "wave" can be run in a plain loop on the CPU (LoopRun), phase by phase, against
+// solve_one_pose (the host form).  Built with the address and undefined-behaviour sanitizers this finds an index error in the shared state without a GPU.
 // A stand-alone program: never load it into Python.
 //
 //   hipcc -x hip --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined \
@@ -18,11 +18,6 @@
 #include <random>
 
 namespace {
-
-struct HostRun {
-    template <class F> void operator()(F f) const { for (int lane = 0; lane < 64; ++lane) f(lane); }
-    bool uniform(bool b) const { return b; }
-};
 
 struct Case { std::vector<float> kp, p3, K; int n; };
 
@@ -70,7 +65,7 @@ void run_case(const Case& c, int iters, Worst& w, const char* what) {
     solve_one_pose(c.kp.data(), c.p3.data(), c.K.data(), c.n, iters, ref);
     static WaveState S;
     double rms = 0.0;
-    const bool ok = pnp_wave_solve(HostRun(), S, c.kp.data(), c.p3.data(), c.K.data(), c.n, iters, &rms);
+    const bool ok = pnp_wave_solve(LoopRun(), S, c.kp.data(), c.p3.data(), c.K.data(), c.n, iters, &rms);
     for (int i = 0; i < 16; ++i) got[i] = ok ? S.out[i] : 0.f;
     const bool ref_ok = ref[15] == 1.f;
     if (ok != ref_ok) { printf("  VERDICT differs (%s): wave %d host %d\n", what, (int)ok, (int)ref_ok); ++w.bad; return; }
