@@ -9,7 +9,39 @@ from __future__ import annotations
 
 import torch
 
-from . import hip_ops
+from . import _lib, hip_ops
+
+
+def capture(owner, run, encoder, decoder, dev: torch.device, capture_error_mode: str = "global"):
+    """Warm `run` up, capture one more call and freeze both modules for `owner`, which keeps the graph -> (graph, that call's static outputs)."""
+    # sub-batch lanes (the modules' `hip_lanes`): the library's side streams / events exist before the capture starts
+    with torch.cuda.device(dev.index if dev.index is not None else torch.cuda.current_device()):
+        _lib.check(_lib.load().bd_lanes_prepare(), "bd_lanes_prepare")
+    # warm-up on a side stream (allocates workspaces / packs weights outside the capture), then capture
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            run()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    graph = torch.cuda.CUDAGraph()
+    # capture_error_mode: torch's default ("global") makes unsafe CUDA calls of OTHER host threads -- an allocation, say -- invalidate
+    # this capture; a process whose other threads keep working on the device passes "thread_local" (the library's own side streams
+    # are per host thread: include/boxdreamer_hip.h, Sub-batch lanes)
+    with torch.cuda.graph(graph, capture_error_mode=capture_error_mode):
+        out = run()
+    # The captured launches hold RAW device pointers into memory the modules own (workspaces allocated during the
+    # warm-up above, packed weights).  (1) Keep those tensors alive on the owner, so nothing the modules do later can
+    # turn a replay into a use-after-free; (2) mark the modules frozen (weak reference), so an operation that would
+    # re-allocate or re-pack them -- a larger eager batch, .to(), a checkpoint load -- raises instead of leaving the
+    # graph replaying on stale weights.  Deleting the owner lifts the freeze.
+    enc_model = getattr(encoder, "model", encoder)
+    owner._pinned = [enc_model._ws, decoder._ws, list(enc_model._packed.values()), list(decoder._packed.values())]
+    # every live graph on these modules freezes them (a second owner must not lift the first one's freeze)
+    enc_model._frozen_by.add(owner)
+    decoder._frozen_by.add(owner)
+    return graph, out
 
 
 class GraphedPath:
@@ -22,34 +54,7 @@ class GraphedPath:
         self.mask = torch.zeros((B, T), dtype=torch.bool, device=dev)
         self.mask[:, T - 1] = True
         self.want_idx = want_idx
-        # sub-batch lanes (the modules' `hip_lanes`): the library's side streams / events exist before the capture starts
-        from . import _lib
-        with torch.cuda.device(dev.index if dev.index is not None else torch.cuda.current_device()):
-            _lib.check(_lib.load().bd_lanes_prepare(), "bd_lanes_prepare")
-        # warm-up on a side stream (allocates workspaces / packs weights outside the capture), then capture
-        s = torch.cuda.Stream(device=dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._run()
-        torch.cuda.current_stream(dev).wait_stream(s)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        # capture_error_mode: torch's default ("global") makes unsafe CUDA calls of OTHER host threads -- an allocation, say -- invalidate
-        # this capture; a process whose other threads keep working on the device passes "thread_local" (the library's own side streams
-        # are per host thread: include/boxdreamer_hip.h, Sub-batch lanes)
-        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
-            self.out = self._run()
-        # The captured launches hold RAW device pointers into memory the modules own (workspaces allocated during the
-        # warm-up above, packed weights).  (1) Keep those tensors alive on this object, so nothing the modules do later can
-        # turn a replay into a use-after-free; (2) mark the modules frozen (weak reference), so an operation that would
-        # re-allocate or re-pack them -- a larger eager batch, .to(), a checkpoint load -- raises instead of leaving the
-        # graph replaying on stale weights.  Deleting the GraphedPath lifts the freeze.
-        enc_model = getattr(encoder, "model", encoder)
-        self._pinned = [enc_model._ws, decoder._ws, list(enc_model._packed.values()), list(decoder._packed.values())]
-        # every live graph on these modules freezes them (a second GraphedPath must not lift the first one's freeze)
-        enc_model._frozen_by.add(self)
-        decoder._frozen_by.add(self)
+        self.graph, self.out = capture(self, self._run, encoder, decoder, dev, capture_error_mode)
 
     def _run(self):
         # (BETR.forward skips its one-hot mask check -- a device sync -- by itself while the stream is capturing; the

@@ -54,17 +54,26 @@ frozen while the session lives (a larger eager batch, .to() or a checkpoint load
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import _lib, calibrate, hip_ops
+from . import _lib, calibrate, graph, hip_ops
 from .betr import BETR
 from .box_utils import solve_poses_device
 from .preprocess import crop_resize_frames
 
 ROW_POSE, ROW_RMS, ROW_OK = slice(0, 16), 16, 17
 ROW_CORNERS_CROP, ROW_CORNERS_FRAME, ROW_BOX_FRAME = slice(18, 34), slice(34, 50), slice(50, 66)
+
+
+def _host_lists(ref_rows, refusal: str):
+    """`ref_rows` as nested host lists -> one list per tracked object, or ValueError(refusal); tensors and entries are the caller's to check."""
+    try:
+        return [list(r) for r in ref_rows]
+    except TypeError:
+        raise ValueError(refusal) from None
 
 
 def _ref_rows(ref_rows, bank_len: int):
@@ -74,10 +83,7 @@ def _ref_rows(ref_rows, bank_len: int):
             raise ValueError(f"ref_rows must be (B, T - 1) host integers, got shape {tuple(ref_rows.shape)}")
         B, R = int(ref_rows.shape[0]), int(ref_rows.shape[1])
     else:
-        try:
-            ref_rows = [list(r) for r in ref_rows]
-        except TypeError:
-            raise ValueError("ref_rows must be (B, T - 1) host integers: one list of bank rows per tracked object") from None
+        ref_rows = _host_lists(ref_rows, "ref_rows must be (B, T - 1) host integers: one list of bank rows per tracked object")
         B, R = len(ref_rows), (len(ref_rows[0]) if ref_rows else 0)
     if B < 1:
         raise ValueError("ref_rows names no sample: a pose stream tracks B >= 1 objects")
@@ -99,14 +105,12 @@ MAX_DATABASE = 1024         # slots one bd_stream_select_rows workgroup ranks
 def _ref_database(ref_rows, bank_len: int, k):
     """`ref_rows` of a session that selects (host ints: B lists of bank rows, lengths may differ) -> (B lists, n_refs, N_max), validated
     against the bank's length and `select_k`."""
+    refusal = "ref_rows must be host integers: one list of bank rows (its database) per tracked object"
     if isinstance(ref_rows, torch.Tensor):
         if ref_rows.device.type != "cpu" or ref_rows.dtype.is_floating_point or ref_rows.dtype == torch.bool or ref_rows.dim() != 2:
-            raise ValueError("ref_rows must be host integers: one list of bank rows (its database) per tracked object")
+            raise ValueError(refusal)
         ref_rows = ref_rows.tolist()
-    try:
-        rows = [list(r) for r in ref_rows]
-    except TypeError:
-        raise ValueError("ref_rows must be host integers: one list of bank rows (its database) per tracked object") from None
+    rows = _host_lists(ref_rows, refusal)
     if len(rows) < 1:
         raise ValueError("ref_rows names no sample: a pose stream tracks B >= 1 objects")
     if any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) for row in rows for r in row):
@@ -127,14 +131,18 @@ def _ref_database(ref_rows, bank_len: int, k):
     return rows, n_refs, max(n_refs)
 
 
-def _relocalise(relocalise, B: int) -> torch.Tensor:
-    """step()'s `relocalise` -> an integer or bool tensor of shape (B,) (host or device), validated without reading it."""
-    t = relocalise if isinstance(relocalise, torch.Tensor) else torch.as_tensor(relocalise)
+def _flags(t, B: int, name: str) -> torch.Tensor:
+    """step()'s `relocalise` / `det_valid`, one integer or bool flag per tracked object -> a (B,) tensor, host or device, never read here."""
+    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
     if t.dtype.is_floating_point or t.dtype.is_complex:
-        raise ValueError(f"relocalise must be integers or bools, got {t.dtype}")
+        raise ValueError(f"{name} must be integers or bools, got {t.dtype}")
     if tuple(t.shape) != (B,):
-        raise ValueError(f"relocalise must be ({B},) for this session of B = {B}: one flag per tracked object, got {tuple(t.shape)}")
+        raise ValueError(f"{name} must be ({B},) for this session of B = {B}: one flag per tracked object, got {tuple(t.shape)}")
     return t
+
+
+def _relocalise(relocalise, B: int) -> torch.Tensor:
+    return _flags(relocalise, B, "relocalise")
 
 
 def _rank_key(v: float, slot: int):
@@ -180,16 +188,6 @@ def select_rows_host(scores, dist, prev_rows, force, n_refs, k, rule, max_rms_px
 
 BOX_DETECTOR, BOX_TRACKED, BOX_HELD = _lib.STREAM_BOX_DETECTOR, _lib.STREAM_BOX_TRACKED, _lib.STREAM_BOX_HELD
 TRACK_FLOATS = 5            # the tail a tracking session reports per object: x0 y0 x1 y1 of the box it used, then its source
-
-
-def _flags(t, B: int, name: str) -> torch.Tensor:
-    """One integer or bool flag per tracked object (step()'s `det_valid`), validated like `relocalise`."""
-    t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
-    if t.dtype.is_floating_point or t.dtype.is_complex:
-        raise ValueError(f"{name} must be integers or bools, got {t.dtype}")
-    if tuple(t.shape) != (B,):
-        raise ValueError(f"{name} must be ({B},) for this session of B = {B}: one flag per tracked object, got {tuple(t.shape)}")
-    return t
 
 
 def _step_boxes(track_boxes: bool, det_boxes, det_valid, keep_boxes, B: int):
@@ -276,6 +274,90 @@ def track_windows_host(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state
     return dict(box=box, src=src, keep=keep, tracked=tracked, finite=finite, visible=visible, bounded=bounded, valid=valid, trusted=trusted)
 
 
+_Plan = namedtuple("_Plan", "rows B T n_refs n_max H W n_frames select_k select max_rms_px min_side_px max_side_px track_boxes "
+                            "use_keep_boxes padding crop_dtype")
+
+
+def _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_dtype, use_keep_boxes, select_k, select, max_rms_px,
+          track_boxes, min_side_px, max_side_px) -> _Plan:
+    """What a session is, decided from the constructor's arguments on the host: every refusal that needs no device, then the record."""
+    if getattr(model, "training", False):
+        raise ValueError("PoseStream needs the model in eval mode (model.eval()): the captured step is the evaluation path")
+    decoder, encoder = getattr(model, "decoder", None), getattr(model, "rgb_encoder", None)
+    if not isinstance(decoder, BETR):
+        raise ValueError("PoseStream needs a BoxDreamer with the BETR decoder")
+    if bank is None or not getattr(bank, "has_entry_tokens", False):
+        raise ValueError("PoseStream runs over a reference bank that keeps decoder-entry tokens: build it with "
+                         "RefFeatureBank(encoder, decoder=model.decoder)")
+    if bank.encoder is not encoder:
+        raise ValueError("the reference bank was built on another encoder than this model's rgb_encoder")
+    if bank.decoder is not decoder:
+        raise ValueError("the reference bank keeps the entry tokens of another decoder than this model's")
+    if select not in SELECT_RULES:
+        raise ValueError(f"unknown select {select!r}: choose from {sorted(SELECT_RULES)}")
+    if select_k is None:
+        rows, B, T = _ref_rows(ref_rows, len(bank))
+        n_refs = n_max = None
+    else:
+        if not getattr(bank, "has_match_summaries", False):
+            raise ValueError("a selecting PoseStream scores the database by appearance and the reference bank keeps no match "
+                             "summaries: build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05)")
+        if select == "track" and not getattr(bank, "has_poses", False):
+            raise ValueError('select="track" ranks the database by distance to the last pose and the reference bank keeps no poses: '
+                             "build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05, keep_poses=True) "
+                             "and add(images, bbox_feat=..., poses=...)")
+        max_rms_px = float(max_rms_px)
+        if max_rms_px != max_rms_px:
+            raise ValueError("max_rms_px is NaN: no solve would ever be trusted; give a number or inf")
+        rows, n_refs, n_max = _ref_database(ref_rows, len(bank), select_k)
+        B, T, select_k = len(rows), int(select_k) + 1, int(select_k)
+    if not isinstance(bbox_3d, torch.Tensor) or tuple(bbox_3d.shape) != (B, 8, 3):
+        raise ValueError(f"bbox_3d must be a tensor of shape {(B, 8, 3)}, got {tuple(getattr(bbox_3d, 'shape', ()))}")
+    H, W = (int(x) for x in frame_shape)
+    n_frames = int(n_frames)
+    if H < 1 or W < 1 or n_frames < 1:
+        raise ValueError(f"frame_shape = {(H, W)} and n_frames = {n_frames} must be positive")
+    if crop_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"crop_dtype must be float32, float16 or bfloat16, got {crop_dtype}")
+    track_boxes = bool(track_boxes)
+    max_rms_px, min_side_px, max_side_px = _track_limits(track_boxes, max_rms_px, min_side_px, max_side_px, H, W)
+    return _Plan(rows, B, T, n_refs, n_max, H, W, n_frames, select_k, select, max_rms_px, min_side_px, max_side_px, track_boxes,
+                 bool(use_keep_boxes), float(padding), crop_dtype)
+
+
+def _layout(B: int, track_boxes: bool):
+    """A session's two flat buffers, each as its ordered fields (name, shape, dtype) of 4-byte words -> (input, output).  ONE H2D carries
+    the input buffer, ONE D2H the output buffer; a tracking session's flags and box tail (x0 y0 x1 y1 src per object) ride along."""
+    ins = [("det_boxes", (B, 4), torch.float32), ("K", (B, 3, 3), torch.float32)]
+    outs = [("rows", (B, _lib.STREAM_ROW_FLOATS), torch.float32)]
+    if track_boxes:
+        ins.append(("det_valid", (B,), torch.int32))
+        outs.append(("track", (B, TRACK_FLOATS), torch.float32))
+    return ins, outs
+
+
+def _cut(fields, **where):
+    """One flat zeroed buffer (`where`: torch.zeros' device / pin_memory) -> (the buffer, {name: its view}), the fields in the order given."""
+    flat = torch.zeros((sum(math.prod(shape) for _, shape, _ in fields),), dtype=torch.float32, **where)
+    views, at = {}, 0
+    for name, shape, dtype in fields:
+        views[name] = flat[at:at + math.prod(shape)].view(dtype).view(shape)
+        at += math.prod(shape)
+    return flat, views
+
+
+def _put(dev, pin, src, upload: bool = True) -> None:
+    """step()'s staging rule, `src` into the static device tensor `dev`: a device source is copied on the device; a host source goes into
+    the pinned twin `pin` (a copy from pageable memory would wait for the stream) and on in one non-blocking H2D (upload=False: the
+    caller's own H2D of a whole buffer follows).  pin=None: straight into `dev` wherever the source lives."""
+    if src.is_cuda or pin is None:
+        dev.copy_(src, non_blocking=True)
+    else:
+        pin.copy_(src)
+        if upload:
+            dev.copy_(pin, non_blocking=True)
+
+
 class PoseStream:
     """One streaming session over an entry-token bank, its step captured as one HIP graph (the module docstring has the sequence).
 
@@ -285,189 +367,122 @@ class PoseStream:
     uint8 frames; n_frames: frames per step.  padding: square_bbox's.  crop_dtype: dtype of the encoder's input crops.
     use_keep_boxes: take per-sample object boxes for background masking (bd_crop_resize_frames' keep_boxes).
 
-    The referenced entry rows are COPIED into a private store at construction: afterwards the bank may grow, be cleared or be
-    refreshed without affecting the session.  After a step, `heat`, `corners_px`, `poses`, `rms_px`, `windows`, `K_crop` and `rows`
-    are the static device tensors of that step (the next step overwrites them).
+    After a step, `heat`, `corners_px`, `poses`, `rms_px`, `windows`, `K_crop` and `rows` are the static device tensors of that step
+    (the next step overwrites them).
 
     select_k (None: the fixed references above, today's session launch for launch and buffer for buffer): `ref_rows` is then a list
     of B lists of bank rows, each object's DATABASE -- lengths may differ, at most 1024, objects may share rows -- and every step
     decodes against the select_k <= min(length) views bd_stream_select_rows chooses (T = select_k + 1).  select: "dino" (by
     appearance; the bank keeps match summaries: match_threshold=0.05) or "track" (by distance to the last frame's pose while its
-    ok == 1 and its rms_px <= max_rms_px, by appearance otherwise; the bank also keeps poses: keep_poses=True).  The distinct
-    database rows' entry tokens, match summaries and poses are copied like the entry rows above.  After a step `sel` (B, select_k)
-    database slots, ascending, `used` (B,) 1 = the pose rule chose, `scores` (B, N_max) and `dist` (B, N_max; None with "dino") are
-    that step's device tensors as well; `ref_rows_of(sel)` names the bank rows.  With "track" a step depends on the previous step's
-    result rows (`rows`): the first step after construction and after `reset()` re-localises by appearance.
+    ok == 1 and its rms_px <= max_rms_px, by appearance otherwise; the bank also keeps poses: keep_poses=True).  After a step `sel`
+    (B, select_k) database slots, ascending, `used` (B,) 1 = the pose rule chose, `scores` (B, N_max) and `dist` (B, N_max; None with
+    "dino") are that step's device tensors as well; `ref_rows_of(sel)` names the bank rows.  With "track" a step depends on the
+    previous step's result rows (`rows`): the first step after construction and after `reset()` re-localises by appearance.
 
     track_boxes (False: bd_stream_windows on the boxes given, today's session): the first node is bd_stream_track_windows (the module
     docstring has the rule); min_side_px, max_side_px (None: 4 x max(H, W)) bound the usable tracked box, max_rms_px the trusted pose
-    (shared with select="track": both kernels decide alike from the same row).  `rows` and the tail `track` (B, 5) = x0 y0 x1 y1 src
-    per object live in ONE flat device buffer, `rows_host` and `track_host` in one pinned buffer: still one D2H per step.  After a
-    step `state_box` (B, 4) and `box_src` (B,) are that step's device tensors too; with use_keep_boxes the kernel writes `keep_boxes`
-    (the box truncated towards zero, not squared).  Such a session also depends on the previous step's result rows."""
+    (shared with select="track": both kernels decide alike from the same row).  The tail `track` (B, 5) = x0 y0 x1 y1 src per object
+    follows `rows` in the step's one D2H, into `track_host` (_layout).  After a step `state_box` (B, 4) and `box_src` (B,) are that
+    step's device tensors too; with use_keep_boxes the kernel writes `keep_boxes` (the box truncated towards zero, not squared).  Such
+    a session also depends on the previous step's result rows."""
 
     def __init__(self, model, bank, ref_rows, bbox_3d, frame_shape, n_frames: int = 1, padding: float = 0.1,
                  crop_dtype: torch.dtype = torch.float32, use_keep_boxes: bool = False, capture_error_mode: str = "global",
                  select_k=None, select: str = "dino", max_rms_px: float = float("inf"), track_boxes: bool = False,
                  min_side_px: float = 8.0, max_side_px=None):
-        # ---- host-side refusals, before a device is needed
-        if getattr(model, "training", False):
-            raise ValueError("PoseStream needs the model in eval mode (model.eval()): the captured step is the evaluation path")
-        decoder, encoder = getattr(model, "decoder", None), getattr(model, "rgb_encoder", None)
-        if not isinstance(decoder, BETR):
-            raise ValueError("PoseStream needs a BoxDreamer with the BETR decoder")
-        if bank is None or not getattr(bank, "has_entry_tokens", False):
-            raise ValueError("PoseStream runs over a reference bank that keeps decoder-entry tokens: build it with "
-                             "RefFeatureBank(encoder, decoder=model.decoder)")
-        if bank.encoder is not encoder:
-            raise ValueError("the reference bank was built on another encoder than this model's rgb_encoder")
-        if bank.decoder is not decoder:
-            raise ValueError("the reference bank keeps the entry tokens of another decoder than this model's")
-        if select not in SELECT_RULES:
-            raise ValueError(f"unknown select {select!r}: choose from {sorted(SELECT_RULES)}")
-        if select_k is None:
-            rows, B, T = _ref_rows(ref_rows, len(bank))
-            n_refs = n_max = None
-        else:
-            if not getattr(bank, "has_match_summaries", False):
-                raise ValueError("a selecting PoseStream scores the database by appearance and the reference bank keeps no match "
-                                 "summaries: build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05)")
-            if select == "track" and not getattr(bank, "has_poses", False):
-                raise ValueError('select="track" ranks the database by distance to the last pose and the reference bank keeps no poses: '
-                                 "build it with RefFeatureBank(encoder, decoder=model.decoder, match_threshold=0.05, keep_poses=True) "
-                                 "and add(images, bbox_feat=..., poses=...)")
-            max_rms_px = float(max_rms_px)
-            if max_rms_px != max_rms_px:
-                raise ValueError("max_rms_px is NaN: no solve would ever be trusted; give a number or inf")
-            rows, n_refs, n_max = _ref_database(ref_rows, len(bank), select_k)
-            B, T = len(rows), int(select_k) + 1
-        if not isinstance(bbox_3d, torch.Tensor) or tuple(bbox_3d.shape) != (B, 8, 3):
-            raise ValueError(f"bbox_3d must be a tensor of shape {(B, 8, 3)}, got {tuple(getattr(bbox_3d, 'shape', ()))}")
-        H, W = (int(x) for x in frame_shape)
-        n_frames = int(n_frames)
-        if H < 1 or W < 1 or n_frames < 1:
-            raise ValueError(f"frame_shape = {(H, W)} and n_frames = {n_frames} must be positive")
-        if crop_dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise ValueError(f"crop_dtype must be float32, float16 or bfloat16, got {crop_dtype}")
-        track_boxes = bool(track_boxes)
-        max_rms_px, min_side_px, max_side_px = _track_limits(track_boxes, max_rms_px, min_side_px, max_side_px, H, W)
+        p = _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_dtype, use_keep_boxes, select_k, select, max_rms_px,
+                  track_boxes, min_side_px, max_side_px)
         _lib.require_gpu()
-        if decoder._signature() != model._calibrated_for and calibrate.applicable(encoder, decoder):
+        self.model, self.encoder, self.decoder = model, model.rgb_encoder, model.decoder
+        if self.decoder._signature() != model._calibrated_for and calibrate.applicable(self.encoder, self.decoder):
             raise RuntimeError("the model's precision self-check has not run for these decoder weights, and it cannot run inside a graph "
                                "capture: run one forward (or model.calibrate(data)) first, or call model.mark_calibrated() to keep the "
                                "promotion state that is in place")
-        self.model, self.encoder, self.decoder = model, encoder, decoder
-        self.B, self.T, self.H, self.W, self.n_frames = B, T, H, W, n_frames
-        self.padding, self.out_size, self.use_keep_boxes = float(padding), int(decoder.img_size), bool(use_keep_boxes)
-        self.select_k, self.select, self.max_rms_px = (None if select_k is None else int(select_k)), select, max_rms_px
-        self.track_boxes, self.min_side_px, self.max_side_px = track_boxes, min_side_px, max_side_px
+        self.B, self.T, self.H, self.W, self.n_frames = p.B, p.T, p.H, p.W, p.n_frames
+        self.padding, self.out_size, self.use_keep_boxes = p.padding, int(self.decoder.img_size), p.use_keep_boxes
+        self.select_k, self.select, self.max_rms_px = p.select_k, p.select, p.max_rms_px
+        self.track_boxes, self.min_side_px, self.max_side_px = p.track_boxes, p.min_side_px, p.max_side_px
+        self._make_stores(bank, p.rows, p.n_refs, p.n_max)
+        self._make_buffers(bbox_3d, p.crop_dtype)
+        self._capture(capture_error_mode)
 
-        # ---- the private entry store and its source table: sample b's references, then -(b + 1): its query, in the last slot
+    def _make_stores(self, bank, rows, n_refs, n_max) -> None:
+        """The referenced entry rows -- with select_k the distinct database rows, and their match summaries and poses -- are COPIED into
+        a private store: afterwards the bank may grow, be cleared or be refreshed without affecting the session.  The source table:
+        sample b's references, then -(b + 1): its query, in the last slot."""
+        B, T, k = self.B, self.T, self.select_k
         bank.ensure_fresh()
-        store = bank.entry_tokens
-        dev = store.device
+        dev = bank.entry_tokens.device
         distinct = sorted({r for row in rows for r in row})
         place = {r: i for i, r in enumerate(distinct)}
         take = torch.tensor(distinct, dtype=torch.int64).to(dev)
-        self._entry = store.index_select(0, take).contiguous()
+        self._entry = bank.entry_tokens.index_select(0, take).contiguous()
         self.sel = self.used = self.scores = self.dist = self.force = None
-        if select_k is None:
-            src = [x for b, row in enumerate(rows) for x in [place[r] for r in row] + [-(b + 1)]]
-            self._src = torch.tensor(src, dtype=torch.int32).to(dev)
-        else:
+        src = [x for b, row in enumerate(rows) for x in [place[r] for r in row[:k]] + [-(b + 1)]]      # (a database: its first k views)
+        self._src = torch.tensor(src, dtype=torch.int32).to(dev)
+        if k is not None:
             # the database in private row space: one `place` map serves the entry tokens, the match summaries and the poses
-            k = self.select_k
             self._database = rows
             self._msums, self._mcounts = bank._msums.index_select(0, take).contiguous(), bank._mcounts.index_select(0, take).contiguous()
-            self._poses = bank.poses.index_select(0, take).contiguous() if select == "track" else None
+            self._poses = bank.poses.index_select(0, take).contiguous() if self.select == "track" else None
             self._match = (float(bank.match_threshold), int(bank.tokens_per_view))
             self._db_rows = torch.tensor([[place[r] for r in row] + [-1] * (n_max - len(row)) for row in rows], dtype=torch.int32).to(dev)
             self._n_refs = torch.tensor(n_refs, dtype=torch.int32).to(dev)
             self._q_sums = torch.zeros((B, int(bank.feature_dim)), dtype=torch.float32, device=dev)
             self._q_counts = torch.zeros((B,), dtype=torch.float32, device=dev)
             self.scores = torch.zeros((B, n_max), dtype=torch.float32, device=dev)
-            self.dist = torch.zeros((B, n_max), dtype=torch.float32, device=dev) if select == "track" else None
+            self.dist = torch.zeros((B, n_max), dtype=torch.float32, device=dev) if self.select == "track" else None
             self.used = torch.zeros((B,), dtype=torch.int32, device=dev)
             self.sel = torch.zeros((B, k), dtype=torch.int32, device=dev)
-            self._src = torch.tensor([x for b, row in enumerate(rows) for x in [place[r] for r in row[:k]] + [-(b + 1)]], dtype=torch.int32).to(dev)
-        if select_k is not None or track_boxes:     # what a step carries from frame to frame is distrusted per object through `force`
-            self.force = torch.zeros((B,), dtype=torch.int32, device=dev)
-            self._pin_force = torch.zeros((B,), dtype=torch.int32).pin_memory()
-            self._pin_reset, self._reset_done, self._forced = None, None, False
         self._mask = torch.zeros((B, T), dtype=torch.bool, device=dev)
         self._mask[:, T - 1] = True
 
-        # ---- static buffers
-        S = self.out_size
-        self.frames = torch.zeros((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
-        n_in = B * (14 if track_boxes else 13)      # det_boxes, then K (then det_valid, int32 in the same words): one H2D per step
-        self._in_f = torch.zeros((n_in,), dtype=torch.float32, device=dev)
-        self.det_boxes, self.K = self._in_f[:B * 4].view(B, 4), self._in_f[B * 4:B * 13].view(B, 3, 3)
+    def _make_buffers(self, bbox_3d, crop_dtype) -> None:
+        """The static device buffers of a step and the pinned twins of those the host fills (_layout has the two flat ones)."""
+        B, S, H, W, dev = self.B, self.out_size, self.H, self.W, self._entry.device
+        ins, outs = _layout(B, self.track_boxes)
+        self.frames = torch.zeros((self.n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+        (self._in_f, self._in), (self._pin_f, self._pin) = _cut(ins, device=dev), _cut(ins, pin_memory=True)
+        (self._out, out), (self._out_host, host) = _cut(outs, device=dev), _cut(outs, pin_memory=True)
+        self.det_boxes, self.K, self.det_valid = self._in["det_boxes"], self._in["K"], self._in.get("det_valid")
+        self.rows, self.track, self.rows_host, self.track_host = out["rows"], out.get("track"), host["rows"], host.get("track")
         self.K.copy_(torch.eye(3, device=dev).expand(B, 3, 3))
-        self.det_boxes.copy_(self._default_box().expand(B, 4))
-        self.frame_idx = (torch.arange(B, dtype=torch.int32) % n_frames).to(dev)
+        self._default_box = torch.tensor([0.0, 0.0, float(min(H, W)), float(min(H, W))], device=dev).expand(B, 4)
+        self.det_boxes.copy_(self._default_box)
+        self.frame_idx = (torch.arange(B, dtype=torch.int32) % self.n_frames).to(dev)
         self.keep_boxes = torch.tensor([0, 0, W - 1, H - 1], dtype=torch.int32).repeat(B, 1).to(dev) if self.use_keep_boxes else None
-        self.det_valid = self.state_box = self.box_src = self.track = self.track_host = None
+        self._pin_idx = torch.zeros((B,), dtype=torch.int32).pin_memory()
+        self._pin_keep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
+        self.state_box = self.box_src = None
+        if self.track_boxes:
+            self.state_box = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+            self.box_src = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if self.select_k is not None or self.track_boxes:   # what a step carries from frame to frame is distrusted per object through `force`
+            self.force = torch.zeros((B,), dtype=torch.int32, device=dev)
+            self._pin_force = torch.zeros((B,), dtype=torch.int32).pin_memory()
+            self._pin_reset, self._reset_done, self._forced = None, None, False
         self.bbox_3d = bbox_3d.detach().to(dev).float().contiguous().clone()
         self.windows = torch.zeros((B, 4), dtype=torch.int32, device=dev)
         self.K_crop = torch.zeros((B, 3, 3), dtype=torch.float32, device=dev)
         self.crops = torch.zeros((B, 3, S, S), dtype=crop_dtype, device=dev)
-        n_rows = B * _lib.STREAM_ROW_FLOATS
-        if track_boxes:
-            # the result rows and the tail (x0 y0 x1 y1 src per object) in ONE flat buffer, on the device and pinned: still one D2H
-            self._out = torch.zeros((n_rows + B * TRACK_FLOATS,), dtype=torch.float32, device=dev)
-            self._out_host = torch.zeros((n_rows + B * TRACK_FLOATS,), dtype=torch.float32).pin_memory()
-            self.rows, self.track = self._out[:n_rows].view(B, _lib.STREAM_ROW_FLOATS), self._out[n_rows:].view(B, TRACK_FLOATS)
-            self.rows_host = self._out_host[:n_rows].view(B, _lib.STREAM_ROW_FLOATS)
-            self.track_host = self._out_host[n_rows:].view(B, TRACK_FLOATS)
-            self.det_valid = self._in_f[B * 13:].view(torch.int32)
-            self.state_box = torch.zeros((B, 4), dtype=torch.float32, device=dev)
-            self.box_src = torch.zeros((B,), dtype=torch.int32, device=dev)
-        else:
-            self._out = self.rows = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32, device=dev)
-            self._out_host = self.rows_host = torch.zeros((B, _lib.STREAM_ROW_FLOATS), dtype=torch.float32).pin_memory()
-        # pinned staging of the small host inputs (a copy from pageable memory would wait for the stream)
-        self._pin_f = torch.zeros((n_in,), dtype=torch.float32).pin_memory()
-        self._pin_idx = torch.zeros((B,), dtype=torch.int32).pin_memory()
-        self._pin_keep = torch.zeros((B, 4), dtype=torch.int32).pin_memory()
         self._done = torch.cuda.Event()
         self._pending = False
         self.replays = 0
-        what = "result rows and box tail" if track_boxes else "result rows"
+        what = "result rows and box tail" if self.track_boxes else "result rows"
         self.host_syncs_per_step = [f"{what}: ONE D2H of {self._out.numel() * 4} bytes into a pinned buffer, one wait for its event"]
 
-        # ---- warm up on a side stream (workspaces, packed weights: allocated outside the capture), then capture -- as graph.GraphedPath
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().bd_lanes_prepare(), "bd_lanes_prepare")
-        mask_error = decoder.mask_error
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                self._run()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        decoder.mask_error = mask_error                 # (the warm-up's verdict on the session's own mask is nobody's business)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode=capture_error_mode):
-            self.heat, self.corners_px, self.poses, self.rms_px = self._run()
-        # the captured launches hold raw pointers into the modules' workspaces and packed weights: keep those alive and freeze the
-        # modules, as graph.GraphedPath does; deleting the session lifts the freeze
-        enc_model = getattr(encoder, "model", encoder)
-        self._pinned = [enc_model._ws, decoder._ws, list(enc_model._packed.values()), list(decoder._packed.values())]
-        enc_model._frozen_by.add(self)
-        decoder._frozen_by.add(self)
-        if select_k is not None or track_boxes:     # (the warm-up left its own result rows: the first step re-localises by appearance)
+    def _capture(self, mode: str) -> None:
+        """Warm up and capture the step (graph.capture), then put back what the warm-up's runs left in the carried state."""
+        mask_error = self.decoder.mask_error
+        self.graph, (self.heat, self.corners_px, self.poses, self.rms_px) = graph.capture(self, self._run, self.encoder, self.decoder, self.frames.device, mode)
+        self.decoder.mask_error = mask_error            # (the warm-up's verdict on the session's own mask is nobody's business)
+        if self.force is not None:      # (the warm-up left its own result rows: the first step re-localises by appearance)
             self.rows.zero_()
-        if track_boxes:                 # ... and its own box: the first step holds the whole-frame default unless a detection is offered
-            self.state_box.copy_(self._default_box().expand(B, 4))
+        if self.track_boxes:            # ... and its own box: the first step holds the whole-frame default unless a detection is offered
+            self.state_box.copy_(self._default_box)
             self.box_src.zero_()
             self.track.zero_()
             self.track[:, :4].copy_(self.state_box)
-
-    def _default_box(self) -> torch.Tensor:
-        side = float(min(self.H, self.W))
-        return torch.tensor([0.0, 0.0, side, side], device=self.frames.device)
 
     def _run(self):
         S = self.out_size
@@ -540,45 +555,26 @@ class PoseStream:
             if self.select_k is None and not self.track_boxes:
                 raise ValueError("relocalise given to a session built without select_k: its references are fixed")
             relocalise = _relocalise(relocalise, B)
-        if self._pending:               # (an un-waited step: its copies still read the pinned staging buffers)
-            self._done.synchronize()
-            self._pending = False
+        self.wait()                     # (an un-waited step: its copies still read the pinned staging buffers)
         self.frames.copy_(frames, non_blocking=True)
         on_device = K.is_cuda or (det_boxes is not None and det_boxes.is_cuda) or (det_valid is not None and det_valid.is_cuda)
-        if on_device:
-            if det_boxes is not None:
-                self.det_boxes.copy_(det_boxes, non_blocking=True)
-            self.K.copy_(K, non_blocking=True)
-            if self.track_boxes:
-                if det_valid is not None:
-                    self.det_valid.copy_(det_valid != 0, non_blocking=True)
-                else:
-                    self.det_valid.fill_(0 if det_boxes is None else 1)
-        else:
-            if det_boxes is not None:
-                self._pin_f[:B * 4].view(B, 4).copy_(det_boxes)
-            self._pin_f[B * 4:B * 13].view(B, 3, 3).copy_(K)
-            if self.track_boxes:
-                pin_valid = self._pin_f[B * 13:].view(torch.int32)
-                if det_valid is not None:
-                    pin_valid.copy_(det_valid != 0)
-                else:
-                    pin_valid.fill_(0 if det_boxes is None else 1)
+        # all on the host: every field into the pinned twin (upload=False), then ONE H2D of the whole input buffer.  Any of them on the
+        # device: `pin` is empty, so _put() gets pin=None and copies each straight into its device field, a host tensor among them too
+        pin = {} if on_device else self._pin
+        flags = None if det_valid is None else det_valid != 0
+        for name, src in (("det_boxes", det_boxes), ("K", K), ("det_valid", flags)):
+            if src is not None:
+                _put(self._in[name], pin.get(name), src, upload=False)
+        if self.track_boxes and flags is None:
+            (self._in if on_device else self._pin)["det_valid"].fill_(0 if det_boxes is None else 1)
+        if not on_device:
             self._in_f.copy_(self._pin_f, non_blocking=True)
-        for given, pin, static in ((frame_idx, self._pin_idx, self.frame_idx), (keep_boxes, self._pin_keep, self.keep_boxes)):
-            if given is None:
-                continue
-            if given.is_cuda:
-                static.copy_(given, non_blocking=True)
-            else:
-                pin.copy_(given)
-                static.copy_(pin, non_blocking=True)
+        if frame_idx is not None:
+            _put(self.frame_idx, self._pin_idx, frame_idx)
+        if keep_boxes is not None:
+            _put(self.keep_boxes, self._pin_keep, keep_boxes)
         if relocalise is not None:
-            if relocalise.is_cuda:
-                self.force.copy_(relocalise != 0, non_blocking=True)
-            else:
-                self._pin_force.copy_(relocalise != 0)
-                self.force.copy_(self._pin_force, non_blocking=True)
+            _put(self.force, self._pin_force, relocalise != 0)
             self._forced = True
         elif self.force is not None and self._forced:           # (the flags hold for one step)
             self.force.zero_()
@@ -612,20 +608,18 @@ class PoseStream:
             self.rows.zero_()
             return
         self._check(poses, (self.B, 4, 4), True, "poses")
-        if poses.is_cuda:
-            self.rows.zero_()
-            self.rows[:, ROW_POSE].copy_(poses.reshape(self.B, 16), non_blocking=True)
-            self.rows[:, ROW_OK].fill_(1.0)
-            return
-        if self._pin_reset is None:
+        host = not poses.is_cuda
+        if host and self._pin_reset is None:
             self._pin_reset, self._reset_done = torch.zeros_like(self.rows_host).pin_memory(), torch.cuda.Event()
-        else:
+        elif host:
             self._reset_done.synchronize()          # (the last reset's copy still reads the staging buffer)
-        self._pin_reset.zero_()
-        self._pin_reset[:, ROW_POSE].copy_(poses.reshape(self.B, 16))
-        self._pin_reset[:, ROW_OK] = 1.0
-        self.rows.copy_(self._pin_reset, non_blocking=True)
-        self._reset_done.record()
+        rows = self._pin_reset if host else self.rows           # filled in place: the pinned staging buffer, or the device rows themselves
+        rows.zero_()
+        rows[:, ROW_POSE].copy_(poses.reshape(self.B, 16), non_blocking=True)
+        rows[:, ROW_OK].fill_(1.0)
+        if host:
+            self.rows.copy_(rows, non_blocking=True)
+            self._reset_done.record()
 
     def ref_rows_of(self, sel) -> list:
         """Database slots (B, k) -- `sel`, read back -- -> the bank rows they name, B lists; -1 stays -1."""

@@ -228,6 +228,71 @@ def test_selecting_session_that_tracks_equals_one_fed_its_boxes(hip):
     gc.collect()
 
 
+def test_step_inputs_from_host_or_device_land_alike(hip):
+    """Wherever a step's small inputs live -- all on the host, all on the device, or mixed -- the session's static buffers hold exactly
+    what was given before the replay, `force` holds for one step only, and the step's result does not depend on the residency."""
+    sh = _shared()
+    model, bank = sh["model"], sh["bank"]
+    B, T = 2, 3
+    bbox_3d = _box_3d(B, T)
+    kw = dict(frame_shape=(H, W), n_frames=2)
+    s = PoseStream(model, bank, CASES[(B, T)][0], bbox_3d, track_boxes=True, **kw)
+    frames, det, K, fidx = _inputs(B, T, 0)
+    valid = torch.tensor([1, 0], dtype=torch.int32)
+    zeros, ones = torch.zeros((B,), dtype=torch.int32), torch.ones((B,), dtype=torch.int32)
+
+    def landed(det_, K_, valid_, fidx_, force_, where):
+        assert _eq(s.det_boxes.cpu(), det_) and _eq(s.K.cpu(), K_), where
+        assert s.det_valid.dtype == torch.int32 and torch.equal(s.det_valid.cpu(), valid_), where
+        assert s.frame_idx.dtype == torch.int32 and torch.equal(s.frame_idx.cpu(), fidx_), where
+        assert s.force.dtype == torch.int32 and torch.equal(s.force.cpu(), force_), where
+
+    # all on the host (a pinned frame), then all on the device: the same inputs from reset() give the same rows
+    s.reset()
+    a = s.step(frames.pin_memory(), det, K, frame_idx=fidx, det_valid=valid).clone()
+    landed(det, K, valid, fidx, zeros, "host")
+    tail = s.track_host.clone()
+    s.reset()
+    b = s.step(frames.cuda(), det.cuda(), K.cuda(), frame_idx=fidx.cuda(), det_valid=valid.cuda())
+    landed(det, K, valid, fidx, zeros, "device")
+    assert np.array_equal(bits(a.numpy()), bits(b.numpy())) and _eq(s.track_host, tail)
+    # K on the device, the boxes and their flags on the host (bools: stored as 0 / 1)
+    det2, K2 = det + 1.25, K * 1.5
+    s.step(frames, det2, K2.cuda(), det_valid=torch.tensor([False, True]))
+    landed(det2, K2, torch.tensor([0, 1], dtype=torch.int32), fidx, zeros, "K on the device")
+    # frame_idx on the device; no det_valid: all ones with a detection, all zeros (and the boxes left alone) without one
+    fidx2 = torch.tensor([1, 0], dtype=torch.int32)
+    s.step(frames, det, K2, frame_idx=fidx2.cuda())
+    landed(det, K2, ones, fidx2, zeros, "frame_idx on the device")
+    s.step(frames, None, K)
+    landed(det, K, zeros, fidx2, zeros, "no detection, host")
+    s.step(frames, det2.cuda(), K)
+    landed(det2, K, ones, fidx2, zeros, "boxes on the device, no det_valid")
+    s.step(frames, None, K2.cuda())
+    landed(det2, K2, zeros, fidx2, zeros, "no detection, device")
+    # relocalise on the device, from the host, and then a step without it: the flags hold for one step
+    s.step(frames, det, K, relocalise=torch.tensor([0, 3]).cuda())
+    landed(det, K, ones, fidx2, torch.tensor([0, 1], dtype=torch.int32), "relocalise on the device")
+    s.step(frames, det, K, relocalise=[True, False])
+    landed(det, K, ones, fidx2, torch.tensor([1, 0], dtype=torch.int32), "relocalise on the host")
+    s.step(frames, det, K)
+    landed(det, K, ones, fidx2, zeros, "the step after relocalise")
+    assert s.replays == 10
+    del s
+    gc.collect()
+    # keep_boxes of a session that is given them, from the host and from the device
+    s = PoseStream(model, bank, CASES[(B, T)][0], bbox_3d, use_keep_boxes=True, **kw)
+    keep = torch.tensor([[0, 10, 60, 80], [70, 35, 127, 95]], dtype=torch.int32)
+    for given in (keep, (keep + 3).cuda()):
+        s.step(frames, det, K, frame_idx=fidx, keep_boxes=given)
+        assert s.keep_boxes.dtype == torch.int32 and torch.equal(s.keep_boxes.cpu(), given.cpu()), given.device
+        assert _eq(s.det_boxes.cpu(), det) and _eq(s.K.cpu(), K) and torch.equal(s.frame_idx.cpu(), fidx)
+    s.step(frames, det, K)                                      # (None: as in the last step)
+    assert torch.equal(s.keep_boxes.cpu(), keep + 3)
+    del s
+    gc.collect()
+
+
 def test_tracking_writes_the_keep_boxes_and_two_sessions_agree(hip):
     sh = _shared()
     model, bank = sh["model"], sh["bank"]

@@ -219,6 +219,36 @@ def test_argument_checks_run_before_any_launch():
     assert ctypes.sizeof(ctypes.c_float) * _lib.STREAM_ROW_FLOATS == 264
 
 
+@pytest.mark.parametrize("track_boxes", [False, True])
+@pytest.mark.parametrize("B", [1, 3])
+def test_flat_buffer_layout_is_contiguous_and_the_same_on_both_sides(B, track_boxes):
+    """stream._layout describes a session's flat input and output buffers once; stream._cut makes the device views and the pinned views
+    from it (two host buffers stand in for them here)."""
+    from boxdreamer_amd import stream
+    ins, outs = stream._layout(B, track_boxes)
+    assert [f[0] for f in ins] == ["det_boxes", "K"] + (["det_valid"] if track_boxes else [])
+    assert [f[0] for f in outs] == ["rows"] + (["track"] if track_boxes else [])
+    shapes = dict(det_boxes=(B, 4), K=(B, 3, 3), det_valid=(B,), rows=(B, 66), track=(B, 5))
+    for fields, words in ((ins, B * (14 if track_boxes else 13)), (outs, B * (71 if track_boxes else 66))):
+        assert sum(int(np.prod(shape)) for _, shape, _ in fields) == words
+        (dev, dev_views), (pin, pin_views) = stream._cut(fields, device="cpu"), stream._cut(fields)
+        assert dev.dtype == pin.dtype == torch.float32 and dev.shape == pin.shape == (words,) and dev.data_ptr() != pin.data_ptr()
+        assert list(dev_views) == list(pin_views) == [f[0] for f in fields]
+        at = 0
+        for name, shape, dtype in fields:
+            d, p = dev_views[name], pin_views[name]
+            assert dtype == (torch.int32 if name == "det_valid" else torch.float32) and dtype.itemsize == 4
+            assert d.dtype == p.dtype == dtype and tuple(d.shape) == tuple(p.shape) == tuple(shape) == shapes[name]
+            assert d.is_contiguous() and p.is_contiguous()
+            assert d.storage_offset() == p.storage_offset() == at                    # the next field starts where the last one ended
+            assert (d.data_ptr() - dev.data_ptr()) == (p.data_ptr() - pin.data_ptr()) == 4 * at and d.data_ptr() % 4 == 0
+            d.fill_(1)                                                              # a view of the flat buffer, and of its own words only
+            assert int((dev.view(torch.int32) != 0).sum()) == d.numel() and bool((dev[at:at + d.numel()].view(torch.int32) != 0).all())
+            dev.zero_()
+            at += d.numel()
+        assert at == words == dev.numel()
+
+
 def _host_model(depth=1):
     from boxdreamer_amd.model import BoxDreamer
     path = os.path.join(ROOT, "tests", "golden", "model_modules_config.json")
@@ -262,3 +292,7 @@ def test_constructor_refusals_that_need_no_device():
         _ref_rows([[0, -1]], 3)
     with pytest.raises(ValueError, match="nor a row of the bank"):
         _ref_rows([[0, 3]], 3)
+    for bad in (torch.zeros((1, 2)), torch.zeros((1, 2), dtype=torch.bool)):       # a tensor of another kind: the table's own refusal
+        with pytest.raises(TypeError, match="must be an integer tensor"):
+            _ref_rows(bad, 3)
+    assert _ref_rows(torch.tensor([[0, 2], [2, 1]]), 3) == ([[0, 2], [2, 1]], 2, 3)
