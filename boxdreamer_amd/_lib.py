@@ -167,7 +167,9 @@ EXPORTS = [
     "bd_stream_windows", "bd_stream_windows_host", "bd_stream_results", "bd_stream_results_host", "bd_stream_select_rows",
     "bd_stream_track_windows", "bd_stream_track_windows_host",
     "bd_gemm_plan", "bd_gemm_instance", "bd_attention_plan", "bd_attention_instance",
+    "bd_crop_resize_frames_fmt", "bd_frames_to_rgb_host",
 ]
+PIXEL_RGB, PIXEL_BGR, PIXEL_RGBA, PIXEL_BGRA, PIXEL_NV12 = 0, 1, 2, 3, 4      # BD_PIXEL_*: bd_crop_resize_frames_fmt's format
 STREAM_ROW_FLOATS = 66                                 # BD_STREAM_ROW_FLOATS: one sample's row of bd_stream_results
 STREAM_SELECT_DINO, STREAM_SELECT_TRACK = 0, 1         # BD_STREAM_SELECT_*: bd_stream_select_rows' rule
 STREAM_BOX_DETECTOR, STREAM_BOX_TRACKED, STREAM_BOX_HELD = 0, 1, 2     # BD_STREAM_BOX_*: bd_stream_track_windows' box_src
@@ -245,6 +247,8 @@ def load() -> C.CDLL:
     lib.bd_pose_metrics_workspace_bytes.restype = sz
     lib.bd_pose_metrics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, vp, sz, vp, vp]
     lib.bd_crop_resize_frames.argtypes = [vp, i, i, i, i64, i64, vp, vp, vp, i, i, vp, i, vp]
+    lib.bd_crop_resize_frames_fmt.argtypes = [vp, i, i, i, i64, i64, vp, vp, vp, i, i, vp, i, i, i64, i, i, i, i, i, i, vp]
+    lib.bd_frames_to_rgb_host.argtypes = [vp, i, i, i, i64, i64, i, i64, i, i, i, i, i, i, vp]
     lib.bd_attention_varlen.argtypes = [vp, i64, vp, i64, vp, i, i, i, i, i, i, f, vp, i, vp]
     lib.bd_query_substitute_varlen.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp]
     lib.bd_gather_query_rows_f32_varlen.argtypes = [vp, vp, vp, vp, i, i, i, vp]

@@ -13,7 +13,10 @@
 // the host may depend on a crop's scale).  It walks the source rows the band needs in chunks:
 //   1. stage   -- the chunk's source rows, clipped to the valid rectangle (crop ^ frame ^ keep box), are read as ALIGNED dwords (4 pixels
 //                 = 3 dwords per lane, the unaligned head handled with v_alignbyte, the tail by not loading dwords without a valid byte)
-//                 and written to LDS as one dword per pixel;
+//                 and written to LDS as one dword per pixel, R | G << 8 | B << 16.  This step alone knows the source format (FMT,
+//                 pixel_format.h): BGR swaps two bytes of that dword, RGBA / BGRA are one aligned dword per pixel, NV12 is four luma
+//                 pixels per aligned dword plus the chroma row y >> 1, converted here -- so a crop of any format is, bit for bit, the
+//                 RGB instance's crop of the converted frame, and only pixels under a crop are converted;
 //   2. horizontal -- one lane per (source row, output column): one LDS dword per tap feeds the three channels (v_cvt_f32_ubyteN), the
 //                 weight comes from a per-block LDS table [tap][column] (conflict-free across lanes) shared by every row and channel;
 //                 the fp32 row lands in LDS [row][channel][column];
@@ -26,6 +29,7 @@
 // Both are far outside the crops a 224 x 224 pose pipeline sees; they exist so that no box produces a wrong answer.
 // Deterministic: fixed summation order, no atomics, a crop's bits depend on its own box and frame only.
 #include "bd_common.h"
+#include "pixel_format.h"
 
 namespace {
 
@@ -80,12 +84,12 @@ template <class T> __device__ __forceinline__ void store1(T* dst, float v) {
     *dst = (T)v;
 }
 
-template <class T>
+template <class T, int FMT>
 __global__ __launch_bounds__(PP_THREADS) void crop_resize_kernel(const uint8_t* __restrict__ frames, int n_frames, int H, int W,
                                                                   int64_t row_stride, int64_t frame_stride,
                                                                   const int32_t* __restrict__ boxes, const int32_t* __restrict__ frame_idx,
                                                                   const int32_t* __restrict__ keep_boxes, int S, int R, int vec_ok,
-                                                                  T* __restrict__ out) {
+                                                                  T* __restrict__ out, int64_t chroma_off, YuvCoef coef) {
     __shared__ __attribute__((aligned(16))) float hbuf[PP_HBUF];
     __shared__ __attribute__((aligned(16))) uint32_t raw[PP_RAW];
     __shared__ float wtab[PP_WTAB];
@@ -158,20 +162,63 @@ __global__ __launch_bounds__(PP_THREADS) void crop_resize_kernel(const uint8_t* 
 
         for (long long jc = j_begin; jc < j_end; jc += CH) {
             const int nrows = (int)min((long long)CH, j_end - jc);
-            // 1. stage: aligned dwords, 4 pixels per lane and step
+            // 1. stage: aligned dwords, 4 pixels per lane and step; the one place where the source format shows
             if (!direct) {
                 for (int e = tid; e < nrows * units; e += PP_THREADS) {
                     const int k = e / units, u = e - k * units;
-                    const uint8_t* rp = fbase + (y0 + jc + k) * row_stride + vx0 * 3;
-                    const unsigned a = (unsigned)((uintptr_t)rp & 3);
-                    const uint32_t* ap = (const uint32_t*)(rp - a);
-                    const int ndw = (int)((a + (unsigned)nvx * 3u + 3u) >> 2);      // dwords that hold at least one valid byte
-                    uint32_t d[4];
+                    const long long yrow = y0 + jc + k;
+                    u128 px;
+                    if constexpr (FMT == PF_RGB || FMT == PF_BGR) {
+                        const uint8_t* rp = fbase + yrow * row_stride + vx0 * 3;
+                        const unsigned a = (unsigned)((uintptr_t)rp & 3);
+                        const uint32_t* ap = (const uint32_t*)(rp - a);
+                        const int ndw = (int)((a + (unsigned)nvx * 3u + 3u) >> 2);      // dwords that hold at least one valid byte
+                        uint32_t d[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) d[q] = (3 * u + q < ndw) ? ap[3 * u + q] : 0u;
-                    const uint32_t b0 = __builtin_amdgcn_alignbyte(d[1], d[0], a), b1 = __builtin_amdgcn_alignbyte(d[2], d[1], a),
-                                   b2 = __builtin_amdgcn_alignbyte(d[3], d[2], a);
-                    u128 px = {b0 & 0xffffffu, (b0 >> 24) | ((b1 & 0xffffu) << 8), (b1 >> 16) | ((b2 & 0xffu) << 16), b2 >> 8};
+                        for (int q = 0; q < 4; ++q) d[q] = (3 * u + q < ndw) ? ap[3 * u + q] : 0u;
+                        const uint32_t b0 = __builtin_amdgcn_alignbyte(d[1], d[0], a), b1 = __builtin_amdgcn_alignbyte(d[2], d[1], a),
+                                       b2 = __builtin_amdgcn_alignbyte(d[3], d[2], a);
+                        px = u128{b0 & 0xffffffu, (b0 >> 24) | ((b1 & 0xffffu) << 8), (b1 >> 16) | ((b2 & 0xffu) << 16), b2 >> 8};
+                        if constexpr (FMT == PF_BGR) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) px[q] = pf_swap_rb(px[q]);
+                        }
+                    } else if constexpr (FMT == PF_RGBA || FMT == PF_BGRA) {
+                        // one dword per pixel; a base or stride off dword alignment makes it two halves of neighbouring dwords
+                        const uint8_t* rp = fbase + yrow * row_stride + vx0 * 4;
+                        const unsigned a = (unsigned)((uintptr_t)rp & 3);
+                        const uint32_t* ap = (const uint32_t*)(rp - a);
+                        const int ndw = (int)((a + (unsigned)nvx * 4u + 3u) >> 2);
+                        uint32_t d[5];
+#pragma unroll
+                        for (int q = 0; q < 5; ++q) d[q] = (4 * u + q < ndw) ? ap[4 * u + q] : 0u;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) px[q] = pf_packed_px<FMT>(__builtin_amdgcn_alignbyte(d[q + 1], d[q], a));
+                    } else {
+                        // NV12: four luma bytes are one dword; their chroma is bytes [4 u, 4 u + 4) of row yrow >> 1 counted from the
+                        // pair of the first valid pixel -- two more when that pixel is the second of its pair (vx0 odd)
+                        const uint8_t* rp = fbase + yrow * row_stride + vx0;
+                        const unsigned a = (unsigned)((uintptr_t)rp & 3);
+                        const uint32_t* ap = (const uint32_t*)(rp - a);
+                        const int ndw = (int)((a + (unsigned)nvx + 3u) >> 2);
+                        const uint32_t l0 = u < ndw ? ap[u] : 0u, l1 = u + 1 < ndw ? ap[u + 1] : 0u;
+                        const uint32_t yy = __builtin_amdgcn_alignbyte(l1, l0, a);
+                        const unsigned odd = (unsigned)(vx0 & 1);
+                        const uint8_t* cp = fbase + chroma_off + (yrow >> 1) * row_stride + (vx0 & ~1LL);
+                        const unsigned ca = (unsigned)((uintptr_t)cp & 3);
+                        const uint32_t* cap = (const uint32_t*)(cp - ca);
+                        const unsigned ncb = (unsigned)((((vx1 - 1) & ~1LL) + 2) - (vx0 & ~1LL));    // chroma bytes under the valid row
+                        const int ncdw = (int)((ca + ncb + 3u) >> 2);
+                        const uint32_t e0 = u < ncdw ? cap[u] : 0u, e1 = u + 1 < ncdw ? cap[u + 1] : 0u,
+                                       e2 = (u + 2 < ncdw && ca + 4u + 2u * odd > 8u) ? cap[u + 2] : 0u;
+                        const uint64_t c = (uint64_t)__builtin_amdgcn_alignbyte(e1, e0, ca) |
+                                           ((uint64_t)__builtin_amdgcn_alignbyte(e2, e1, ca) << 32);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const uint32_t uv = (uint32_t)(c >> (16u * ((odd + (unsigned)q) >> 1)));
+                            px[q] = pf_yuv_px((int)((yy >> (8 * q)) & 0xffu), (int)(uv & 0xffu), (int)((uv >> 8) & 0xffu), coef);
+                        }
+                    }
                     *(u128*)&raw[k * rawpitch + u * 4] = px;
                 }
             }
@@ -210,14 +257,13 @@ __global__ __launch_bounds__(PP_THREADS) void crop_resize_kernel(const uint8_t* 
                         }
                     }
                 } else {
-                    const uint8_t* rowp = fbase + (y0 + jc + k) * row_stride + (x0 + lo) * 3;
                     const double c = scale * ((double)i + 0.5), sum = xsum[i];
                     for (int t = t0; t < t1; ++t) {
                         const float w = use_tab ? wtab[t * S + i] : (float)(tap_weight(lo + t, c, support) / sum);
-                        const uint8_t* p = rowp + (int64_t)t * 3;
-                        cr = fmaf(w, (float)p[0], cr);
-                        cg = fmaf(w, (float)p[1], cg);
-                        cb = fmaf(w, (float)p[2], cb);
+                        const uint32_t px = pf_load_px<FMT>(fbase, row_stride, chroma_off, x0 + lo + t, y0 + jc + k, coef);
+                        cr = fmaf(w, (float)(px & 0xffu), cr);
+                        cg = fmaf(w, (float)((px >> 8) & 0xffu), cg);
+                        cb = fmaf(w, (float)((px >> 16) & 0xffu), cb);
                     }
                 }
                 float* h = hbuf + k * 3 * Sp + i;
@@ -259,32 +305,105 @@ __global__ __launch_bounds__(PP_THREADS) void crop_resize_kernel(const uint8_t* 
     }
 }
 
-template <class T>
-void launch(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride, const int32_t* boxes,
-            const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int S, void* out, hipStream_t s) {
+struct Frames {
+    const uint8_t* base;
+    int n, H, W;
+    int64_t row_stride, frame_stride, chroma_off;
+    YuvCoef coef;
+};
+
+template <class T, int FMT>
+void launch(const Frames& fr, const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int S, void* out,
+            hipStream_t s) {
     const int R = pp_band(S);
     const int vec_ok = (S % 4 == 0) && ((uintptr_t)out % 16 == 0);
-    hipLaunchKernelGGL(crop_resize_kernel<T>, dim3((S + R - 1) / R, n_crops), dim3(PP_THREADS), 0, s, frames, n_frames, H, W, row_stride,
-                       frame_stride, boxes, frame_idx, keep_boxes, S, R, vec_ok, (T*)out);
+    hipLaunchKernelGGL((crop_resize_kernel<T, FMT>), dim3((S + R - 1) / R, n_crops), dim3(PP_THREADS), 0, s, fr.base, fr.n, fr.H, fr.W,
+                       fr.row_stride, fr.frame_stride, boxes, frame_idx, keep_boxes, S, R, vec_ok, (T*)out, fr.chroma_off, fr.coef);
+}
+
+template <int FMT>
+void launch_dtype(const Frames& fr, const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int S,
+                  void* out, int out_dtype, hipStream_t s) {
+    if (out_dtype == BD_DTYPE_F32)
+        launch<float, FMT>(fr, boxes, frame_idx, keep_boxes, n_crops, S, out, s);
+    else if (out_dtype == BD_DTYPE_F16)
+        launch<_Float16, FMT>(fr, boxes, frame_idx, keep_boxes, n_crops, S, out, s);
+    else
+        launch<__bf16, FMT>(fr, boxes, frame_idx, keep_boxes, n_crops, S, out, s);
+}
+
+// what can be refused about a frame layout on the host: BD_OK, or the code both entries below and the host converter return
+int check_frames(const Frames& fr, int format) {
+    if (!fr.base) return BD_ERR_NULL;
+    if (format < PF_RGB || format > PF_NV12) return BD_ERR_DTYPE;
+    if (fr.n <= 0 || fr.H <= 0 || fr.W <= 0) return BD_ERR_SHAPE;
+    if (fr.row_stride < (int64_t)pf_bytes_per_pixel(format) * fr.W || fr.frame_stride < 0) return BD_ERR_SHAPE;
+    if (format == PF_NV12) {
+        if ((fr.H & 1) || (fr.W & 1) || fr.chroma_off < (int64_t)fr.H * fr.row_stride) return BD_ERR_SHAPE;
+        const int c[5] = {fr.coef.cy, fr.coef.crv, fr.coef.cgu, fr.coef.cgv, fr.coef.cbu};
+        for (int v : c)
+            if (v < 0 || v > PF_MAX_COEF) return BD_ERR_SHAPE;                  // (int32 holds every intermediate)
+        if (fr.coef.y_off < 0 || fr.coef.y_off > 255) return BD_ERR_SHAPE;
+    }
+    return BD_OK;
+}
+
+template <int FMT>
+void to_rgb_host(const Frames& fr, uint8_t* out) {
+    for (int n = 0; n < fr.n; ++n)
+        for (int y = 0; y < fr.H; ++y)
+            for (int x = 0; x < fr.W; ++x) {
+                const uint32_t px = pf_load_px<FMT>(fr.base + n * fr.frame_stride, fr.row_stride, fr.chroma_off, x, y, fr.coef);
+                uint8_t* o = out + (((int64_t)n * fr.H + y) * fr.W + x) * 3;
+                o[0] = (uint8_t)(px & 0xffu); o[1] = (uint8_t)((px >> 8) & 0xffu); o[2] = (uint8_t)((px >> 16) & 0xffu);
+            }
 }
 
 }  // namespace
 
-extern "C" int bd_crop_resize_frames(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
-                                     const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops,
-                                     int out_size, void* out, int out_dtype, void* stream) {
+extern "C" int bd_crop_resize_frames_fmt(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
+                                         const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops,
+                                         int out_size, void* out, int out_dtype, int format, int64_t chroma_offset, int cy, int crv,
+                                         int cgu, int cgv, int cbu, int y_off, void* stream) {
     if (!frames || !boxes || !out) return BD_ERR_NULL;
-    if (n_frames <= 0 || H <= 0 || W <= 0 || n_crops <= 0 || n_crops > 65535 || out_size <= 0 || out_size > PP_MAX_OUT) return BD_ERR_SHAPE;
-    if (row_stride < 3 * (int64_t)W || frame_stride < 0) return BD_ERR_SHAPE;
+    if (n_crops <= 0 || n_crops > 65535 || out_size <= 0 || out_size > PP_MAX_OUT) return BD_ERR_SHAPE;
+    const Frames fr = {frames, n_frames, H, W, row_stride, frame_stride, chroma_offset, {cy, crv, cgu, cgv, cbu, y_off}};
+    if (const int rc = check_frames(fr, format)) return rc;
     if (!frame_idx && n_crops > n_frames) return BD_ERR_SHAPE;                  // crop i reads frame i
     if (out_dtype != BD_DTYPE_F32 && out_dtype != BD_DTYPE_F16 && out_dtype != BD_DTYPE_BF16) return BD_ERR_DTYPE;
     hipStream_t s = (hipStream_t)stream;
-    if (out_dtype == BD_DTYPE_F32)
-        launch<float>(frames, n_frames, H, W, row_stride, frame_stride, boxes, frame_idx, keep_boxes, n_crops, out_size, out, s);
-    else if (out_dtype == BD_DTYPE_F16)
-        launch<_Float16>(frames, n_frames, H, W, row_stride, frame_stride, boxes, frame_idx, keep_boxes, n_crops, out_size, out, s);
-    else
-        launch<__bf16>(frames, n_frames, H, W, row_stride, frame_stride, boxes, frame_idx, keep_boxes, n_crops, out_size, out, s);
+    switch (format) {
+        case PF_RGB: launch_dtype<PF_RGB>(fr, boxes, frame_idx, keep_boxes, n_crops, out_size, out, out_dtype, s); break;
+        case PF_BGR: launch_dtype<PF_BGR>(fr, boxes, frame_idx, keep_boxes, n_crops, out_size, out, out_dtype, s); break;
+        case PF_RGBA: launch_dtype<PF_RGBA>(fr, boxes, frame_idx, keep_boxes, n_crops, out_size, out, out_dtype, s); break;
+        case PF_BGRA: launch_dtype<PF_BGRA>(fr, boxes, frame_idx, keep_boxes, n_crops, out_size, out, out_dtype, s); break;
+        default: launch_dtype<PF_NV12>(fr, boxes, frame_idx, keep_boxes, n_crops, out_size, out, out_dtype, s); break;
+    }
     BD_CHECK_LAUNCH();
     return BD_OK;
 }
+
+// the "rgb" case of the entry above: the same checks in the same order, the same kernel instance, the same launch
+extern "C" int bd_crop_resize_frames(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
+                                     const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops,
+                                     int out_size, void* out, int out_dtype, void* stream) {
+    return bd_crop_resize_frames_fmt(frames, n_frames, H, W, row_stride, frame_stride, boxes, frame_idx, keep_boxes, n_crops, out_size, out,
+                                     out_dtype, PF_RGB, 0, 0, 0, 0, 0, 0, 0, stream);
+}
+
+extern "C" int bd_frames_to_rgb_host(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
+                                     int format, int64_t chroma_offset, int cy, int crv, int cgu, int cgv, int cbu, int y_off,
+                                     uint8_t* out) {
+    if (!frames || !out) return BD_ERR_NULL;
+    const Frames fr = {frames, n_frames, H, W, row_stride, frame_stride, chroma_offset, {cy, crv, cgu, cgv, cbu, y_off}};
+    if (const int rc = check_frames(fr, format)) return rc;
+    switch (format) {
+        case PF_RGB: to_rgb_host<PF_RGB>(fr, out); break;
+        case PF_BGR: to_rgb_host<PF_BGR>(fr, out); break;
+        case PF_RGBA: to_rgb_host<PF_RGBA>(fr, out); break;
+        case PF_BGRA: to_rgb_host<PF_BGRA>(fr, out); break;
+        default: to_rgb_host<PF_NV12>(fr, out); break;
+    }
+    return BD_OK;
+}
+

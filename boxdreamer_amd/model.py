@@ -219,11 +219,11 @@ class BoxDreamer(nn.Module):
 
     def _images_from_frames(self, data) -> torch.Tensor:
         """`data["images"]` from raw frames (boxdreamer_amd/preprocess.py): uint8 `frames` [F, H, W, 3] + int32 `crop_boxes` [B, T, 4] on the
-        device, optionally `frame_idx` [B, T] (default: view i reads frame i), `keep_boxes` [B, T, 4] (background masking) and
-        `crop_size` (224) -> [B, T, 3, S, S] in bbox_feat's dtype, ONE launch on the current stream.  With `hip_graph` the launch stays
+        device, optionally `frame_idx` [B, T] (default: view i reads frame i), `keep_boxes` [B, T, 4] (background masking),
+        `frame_format` (the frames' layout when it is not packed RGB: "bgr", "rgba", "bgra", "nv12", or a dict) and `crop_size` (224) ->[B, T, 3, S, S] in bbox_feat's dtype, ONE launch on the current stream.  With `hip_graph` the launch stays
         outside the captured graph and writes straight into the graph's static image buffer when one exists for the shape (the replay's
         input copy of that tensor onto itself is a no-op); `data["images"]` then aliases that buffer until the next forward."""
-        from .preprocess import crop_resize_frames
+        from .preprocess import crop_resize_frames, resolve_format
         missing = [k for k in ("frames", "crop_boxes") if k not in data]
         if missing:
             raise KeyError(f"the batch dict needs 'images', or 'frames' + 'crop_boxes' to make them on the device (missing: {missing})")
@@ -239,8 +239,11 @@ class BoxDreamer(nn.Module):
         if (g is not None and tuple(g.images.shape) == (B, T, 3, S, S) and g.images.dtype == dtype
                 and g.images.device == data["frames"].device):
             out = g.images
+        # `frame_format` (absent: packed RGB, the call as it was): a name, or a dict frame_format / colorspace / range, of the layout
+        # the frames arrive in (preprocess.resolve_format); the kernel converts the pixels under the crops as it stages them
+        fmt = {} if data.get("frame_format") is None else {"frame_format": resolve_format(data["frame_format"])}
         return crop_resize_frames(data["frames"], boxes, frame_idx=data.get("frame_idx"), keep_boxes=data.get("keep_boxes"),
-                                  out_size=S, out=out, dtype=dtype)
+                                  out_size=S, out=out, dtype=dtype, **fmt)
 
     def forward(self, data):
         if "images" not in data:      # opt-in: raw uint8 frames + crop windows in place of the dataset's float crops

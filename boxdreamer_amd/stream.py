@@ -14,6 +14,8 @@ session -- B tracked objects, each with its T - 1 banked references, a fixed fra
     bd_stream_windows -> bd_crop_resize_frames -> encoder (the B query crops) -> BETR.forward_entry (private copy of the bank's
     rows) -> bd_decode_topk -> bd_solve_pnp_wave -> bd_stream_results
 
+(`frame_format=`: bd_crop_resize_frames_fmt in that place, on BGR, RGBA / BGRA or NV12 frames as the source delivers them.)
+
 `step()` copies the frame, the detector boxes and K into static buffers, replays the graph, enqueues ONE D2H of the result rows into
 a pinned buffer and waits for that copy's event.  Nothing is carried from frame to frame.
 
@@ -62,7 +64,7 @@ import torch
 from . import _lib, calibrate, graph, hip_ops
 from .betr import BETR
 from .box_utils import solve_poses_device
-from .preprocess import crop_resize_frames
+from .preprocess import crop_resize_frames, frame_shape_of, resolve_format
 
 ROW_POSE, ROW_RMS, ROW_OK = slice(0, 16), 16, 17
 ROW_CORNERS_CROP, ROW_CORNERS_FRAME, ROW_BOX_FRAME = slice(18, 34), slice(34, 50), slice(50, 66)
@@ -275,11 +277,11 @@ def track_windows_host(prev_rows, bbox_3d, K, det_boxes, det_valid, force, state
 
 
 _Plan = namedtuple("_Plan", "rows B T n_refs n_max H W n_frames select_k select max_rms_px min_side_px max_side_px track_boxes "
-                            "use_keep_boxes padding crop_dtype")
+                            "use_keep_boxes padding crop_dtype frame_format")
 
 
 def _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_dtype, use_keep_boxes, select_k, select, max_rms_px,
-          track_boxes, min_side_px, max_side_px) -> _Plan:
+          track_boxes, min_side_px, max_side_px, frame_format="rgb", colorspace=None, range=None) -> _Plan:
     """What a session is, decided from the constructor's arguments on the host: every refusal that needs no device, then the record."""
     if getattr(model, "training", False):
         raise ValueError("PoseStream needs the model in eval mode (model.eval()): the captured step is the evaluation path")
@@ -295,6 +297,7 @@ def _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_d
         raise ValueError("the reference bank keeps the entry tokens of another decoder than this model's")
     if select not in SELECT_RULES:
         raise ValueError(f"unknown select {select!r}: choose from {sorted(SELECT_RULES)}")
+    fmt = resolve_format(frame_format, colorspace, range)       # (an unknown name, a colorspace for frames that are not NV12: ValueError)
     if select_k is None:
         rows, B, T = _ref_rows(ref_rows, len(bank))
         n_refs = n_max = None
@@ -317,12 +320,13 @@ def _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_d
     n_frames = int(n_frames)
     if H < 1 or W < 1 or n_frames < 1:
         raise ValueError(f"frame_shape = {(H, W)} and n_frames = {n_frames} must be positive")
+    frame_shape_of(fmt, n_frames, H, W)                         # (NV12 with an odd side)
     if crop_dtype not in (torch.float32, torch.float16, torch.bfloat16):
         raise ValueError(f"crop_dtype must be float32, float16 or bfloat16, got {crop_dtype}")
     track_boxes = bool(track_boxes)
     max_rms_px, min_side_px, max_side_px = _track_limits(track_boxes, max_rms_px, min_side_px, max_side_px, H, W)
     return _Plan(rows, B, T, n_refs, n_max, H, W, n_frames, select_k, select, max_rms_px, min_side_px, max_side_px, track_boxes,
-                 bool(use_keep_boxes), float(padding), crop_dtype)
+                 bool(use_keep_boxes), float(padding), crop_dtype, fmt)
 
 
 def _layout(B: int, track_boxes: bool):
@@ -384,14 +388,22 @@ class PoseStream:
     (shared with select="track": both kernels decide alike from the same row).  The tail `track` (B, 5) = x0 y0 x1 y1 src per object
     follows `rows` in the step's one D2H, into `track_host` (_layout).  After a step `state_box` (B, 4) and `box_src` (B,) are that
     step's device tensors too; with use_keep_boxes the kernel writes `keep_boxes` (the box truncated towards zero, not squared).  Such
-    a session also depends on the previous step's result rows."""
+    a session also depends on the previous step's result rows.
+
+    frame_format ("rgb": packed RGB frames and bd_crop_resize_frames, today's session launch for launch and buffer for buffer): the
+    layout the frames arrive in -- "bgr" (n_frames, H, W, 3), "rgba" / "bgra" (n_frames, H, W, 4), "nv12" (n_frames, H + H / 2, W) with
+    even H and W, converted with colorspace ("bt601" / "bt709") and range ("limited" / "full"; None: "bt601", "limited"; they are
+    refused for another format).  The static frame buffer takes that shape and the captured crop node is bd_crop_resize_frames_fmt,
+    which converts the pixels under the crops as it stages them: every output equals, bit for bit, a default session's on
+    preprocess.frames_to_rgb(frames, ...).  It combines freely with select_k, track_boxes and use_keep_boxes: none of them looks at
+    pixels."""
 
     def __init__(self, model, bank, ref_rows, bbox_3d, frame_shape, n_frames: int = 1, padding: float = 0.1,
                  crop_dtype: torch.dtype = torch.float32, use_keep_boxes: bool = False, capture_error_mode: str = "global",
                  select_k=None, select: str = "dino", max_rms_px: float = float("inf"), track_boxes: bool = False,
-                 min_side_px: float = 8.0, max_side_px=None):
+                 min_side_px: float = 8.0, max_side_px=None, frame_format="rgb", colorspace=None, range=None):
         p = _plan(model, bank, ref_rows, bbox_3d, frame_shape, n_frames, padding, crop_dtype, use_keep_boxes, select_k, select, max_rms_px,
-                  track_boxes, min_side_px, max_side_px)
+                  track_boxes, min_side_px, max_side_px, frame_format, colorspace, range)
         _lib.require_gpu()
         self.model, self.encoder, self.decoder = model, model.rgb_encoder, model.decoder
         if self.decoder._signature() != model._calibrated_for and calibrate.applicable(self.encoder, self.decoder):
@@ -402,6 +414,7 @@ class PoseStream:
         self.padding, self.out_size, self.use_keep_boxes = p.padding, int(self.decoder.img_size), p.use_keep_boxes
         self.select_k, self.select, self.max_rms_px = p.select_k, p.select, p.max_rms_px
         self.track_boxes, self.min_side_px, self.max_side_px = p.track_boxes, p.min_side_px, p.max_side_px
+        self.frame_format = p.frame_format
         self._make_stores(bank, p.rows, p.n_refs, p.n_max)
         self._make_buffers(bbox_3d, p.crop_dtype)
         self._capture(capture_error_mode)
@@ -441,7 +454,7 @@ class PoseStream:
         """The static device buffers of a step and the pinned twins of those the host fills (_layout has the two flat ones)."""
         B, S, H, W, dev = self.B, self.out_size, self.H, self.W, self._entry.device
         ins, outs = _layout(B, self.track_boxes)
-        self.frames = torch.zeros((self.n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+        self.frames = torch.zeros(frame_shape_of(self.frame_format, self.n_frames, H, W), dtype=torch.uint8, device=dev)
         (self._in_f, self._in), (self._pin_f, self._pin) = _cut(ins, device=dev), _cut(ins, pin_memory=True)
         (self._out, out), (self._out_host, host) = _cut(outs, device=dev), _cut(outs, pin_memory=True)
         self.det_boxes, self.K, self.det_valid = self._in["det_boxes"], self._in["K"], self._in.get("det_valid")
@@ -494,7 +507,8 @@ class PoseStream:
                                          track=self.track)
         else:
             hip_ops.stream_windows(self.det_boxes, self.K, self.padding, S, self.windows, self.K_crop)
-        crop_resize_frames(self.frames, self.windows, frame_idx=self.frame_idx, keep_boxes=self.keep_boxes, out_size=S, out=self.crops)
+        crop_resize_frames(self.frames, self.windows, frame_idx=self.frame_idx, keep_boxes=self.keep_boxes, out_size=S, out=self.crops,
+                           frame_format=self.frame_format)
         fresh = self.encoder.predict(self.crops)
         if self.select_k is not None:
             # which k database views the decoder reads this frame: the query's summary, then ONE launch that reads the last step's
@@ -514,10 +528,11 @@ class PoseStream:
     def _check_frames(self, frames):
         if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
             raise ValueError(f"frames must be a uint8 tensor, got {getattr(frames, 'dtype', type(frames).__name__)}")
-        if frames.dim() == 3 and self.n_frames == 1:
+        if frames.dim() == self.frames.dim() - 1 and self.n_frames == 1:
             frames = frames[None]
         if tuple(frames.shape) != tuple(self.frames.shape):
-            raise ValueError(f"frames must be {tuple(self.frames.shape)} (the session's frame shape is fixed), got {tuple(frames.shape)}")
+            raise ValueError(f"frames must be {tuple(self.frames.shape)} (the session's frame shape is fixed; its frame_format is "
+                             f"{self.frame_format.name!r}), got {tuple(frames.shape)}")
         return frames
 
     def _check(self, t, shape, floating: bool, name: str):
@@ -528,7 +543,8 @@ class PoseStream:
         return t
 
     def step(self, frames, det_boxes, K, frame_idx=None, keep_boxes=None, wait: bool = True, relocalise=None, det_valid=None) -> torch.Tensor:
-        """One frame: frames uint8 (n_frames, H, W, 3) (or (H, W, 3) when n_frames == 1; a pinned host tensor is copied
+        """One frame: frames uint8 (n_frames, H, W, 3) (or (H, W, 3) when n_frames == 1; with a frame_format, that format's shape,
+        e.g. (n_frames, H * 3 / 2, W) or (H * 3 / 2, W) for "nv12"; a pinned host tensor is copied
         asynchronously, a device tensor on the device), det_boxes float (B, 4) x0 y0 x1 y1, K float (B, 3, 3) full-frame intrinsics
         (host or device), frame_idx integers (B,): the frame each sample reads (None: as in the last step; initially b % n_frames),
         keep_boxes integers (B, 4) when the session was built with use_keep_boxes (None: as in the last step; initially the whole

@@ -605,6 +605,41 @@ int bd_crop_resize_frames(const uint8_t* frames, int n_frames, int H, int W, int
                           const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int out_size,
                           void* out, int out_dtype, void* stream);
 
+/* The same crop + resize on frames in the layout a camera, a compositor or a video decoder delivers.  bd_crop_resize_frames is
+ * the BD_PIXEL_RGB case of this entry: the same kernel instance and launch.  Only the step that turns source bytes into pixels
+ * differs per format (csrc/pixel_format.h, shared with bd_frames_to_rgb_host); the filter behind it sees the same pixels, so the
+ * result is BIT FOR BIT bd_crop_resize_frames on the frame converted to packed RGB, and only pixels under a crop are converted.
+ *   BD_PIXEL_RGB / _BGR    uint8 [n_frames, H, W, 3], row_stride >= 3 W
+ *   BD_PIXEL_RGBA / _BGRA  uint8 [n_frames, H, W, 4], row_stride >= 4 W; the fourth byte is ignored
+ *   BD_PIXEL_NV12          H and W even; H rows of W luma bytes from the frame's first byte, then, chroma_offset bytes from the
+ *                          frame's first byte, H / 2 rows of W / 2 interleaved (U, V) pairs, both planes with row_stride >= W;
+ *                          chroma_offset >= H * row_stride (a decoder that pads the luma plane's height is read in place).
+ *                          Chroma is sampled nearest: pixel (x, y) uses pair (x >> 1, y >> 1).
+ * No alignment is required of the base, the strides or chroma_offset.  chroma_offset and the coefficients are read for NV12 only.
+ * NV12 -> RGB, int32, >> arithmetic:  y = Y - y_off, u = U - 128, v = V - 128,
+ *   R = clamp((cy y + crv v + 32768) >> 16, 0, 255), G = clamp((cy y - cgu u - cgv v + 32768) >> 16, 0, 255),
+ *   B = clamp((cy y + cbu u + 32768) >> 16, 0, 255)
+ * with coefficients floor(x 65536 + 0.5) of cy = 255/219 | 1, crv = 2 (1 - Kr) s, cbu = 2 (1 - Kb) s, cgu = 2 Kb (1 - Kb) / Kg s,
+ * cgv = 2 Kr (1 - Kr) / Kg s, s = 255/224 | 1 (limited | full range), Kg = 1 - Kr - Kb:
+ *                   cy     crv    cgu    cgv    cbu  y_off
+ *   BT.601 limited  76309 104597  25675  53279 132201  16        BT.601 full  65536  91881  22553  46802 116130  0
+ *   BT.709 limited  76309 117489  13975  34925 138438  16        BT.709 full  65536 103206  12276  30679 121609  0
+ * Before any launch, next to bd_crop_resize_frames' checks: an unknown format BD_ERR_DTYPE; row_stride below one row of the format,
+ * NV12 with odd H or W, chroma_offset < H * row_stride, a coefficient outside [0, 2^20] or y_off outside [0, 255] BD_ERR_SHAPE. */
+#define BD_PIXEL_RGB 0
+#define BD_PIXEL_BGR 1
+#define BD_PIXEL_RGBA 2
+#define BD_PIXEL_BGRA 3
+#define BD_PIXEL_NV12 4
+int bd_crop_resize_frames_fmt(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride,
+                              const int32_t* boxes, const int32_t* frame_idx, const int32_t* keep_boxes, int n_crops, int out_size,
+                              void* out, int out_dtype, int format, int64_t chroma_offset, int cy, int crv, int cgu, int cgv,
+                              int cbu, int y_off, void* stream);
+/* A whole frame of any format to packed RGB on HOST pointers, in the calling thread, with the kernel's per-pixel text: out uint8
+ * [n_frames, H, W, 3], contiguous.  The same layout checks and codes; needs no device. */
+int bd_frames_to_rgb_host(const uint8_t* frames, int n_frames, int H, int W, int64_t row_stride, int64_t frame_stride, int format,
+                          int64_t chroma_offset, int cy, int crv, int cgu, int cgv, int cbu, int y_off, uint8_t* out);
+
 /* The two ends of a streaming pose step (boxdreamer_amd/stream.py), one launch each, so that a captured step holds two graph nodes
  * where the facade enqueues a few dozen small torch kernels per frame.  Each is ceil(n / 64) wavefronts, one sample per lane: no
  * workspace, no atomics, no synchronisation.  The *_host forms run the SAME arithmetic (written once, __host__ __device__) on host
