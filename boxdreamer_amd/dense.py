@@ -334,8 +334,8 @@ def recover_pose_from_dense_bb8(query_rets, bbox_3d, K, pnp_on_device=False, n_t
 def process_multi_round(data, pose_feat, frames, camera_mask, rgb_feature, image_masks, decoder, dense_cfg,
                         bbox_representation="heatmap", pnp_on_device=False):
     """Decoder over sub-batches of the references (query appended to each), one PnP over all rounds' corners, optional
-    fine round on the references nearest to that pose.  Returns the decoder output of the fine round (tensor) or, without
-    it, the batch dict with the coarse prediction (as the reference does).  pnp_on_device: the model's setting; "wave" runs that PnP
+    fine round on the references nearest to that pose.  Returns the decoder output of the fine round or, without it, None: the
+    coarse prediction is then written into the batch dict (_write_coarse; the reference returns the dict).  pnp_on_device: the model's setting; "wave" runs that PnP
     on the device when there are at most 8 rounds (recover_pose_from_dense_bb8).  dense_cfg.ransac_trials (optional): its trial count,
     default 1000 (the reference's iterationsCount)."""
     B = frames.shape[0]
@@ -374,15 +374,25 @@ def process_multi_round(data, pose_feat, frames, camera_mask, rgb_feature, image
             data, neighbor_mask, pose_feat, frames, camera_mask, rgb_feature, image_masks)
         from . import features as _features
         return decoder(pose_feat.contiguous(), frames.contiguous(), camera_mask, _features.carry(rgb_feature, rgb_feature.contiguous()), None)
-    pred_poses = poses.clone()
-    data["pred_bbox"] = pose_feat.clone()
-    data["pred_bbox"][camera_mask] = query_rets[:, 0].to(pose_feat.dtype)
-    pred_poses[camera_mask] = query_poses.squeeze(1).to(pred_poses.dtype)
+    _write_coarse(data, camera_mask, pose_feat, query_rets, query_poses, pred_proj)     # (a boolean mask: each write waits for the device)
+    return None
+
+
+def _write_coarse(data, where, pose_feat, query_rets, query_poses, pred_proj) -> None:
+    """The coarse prediction of a multi-round decode without a fine level, into the batch dict at the query view `[where]`: camera_mask
+    (the reference's own write) or (arange(B), query_idx).  An entry-token bank's batch may carry no heat maps (pose_feat None): the
+    decoder's output then goes out as it does from BoxDreamer.forward, in pred_query_bbox."""
+    if pose_feat is not None:
+        data["pred_bbox"] = pose_feat.clone()
+        data["pred_bbox"][where] = query_rets[:, 0].to(pose_feat.dtype)
+    else:
+        data["pred_query_bbox"] = query_rets[:, 0]
+    pred_poses = data["poses"].clone()
+    pred_poses[where] = query_poses.squeeze(1).to(pred_poses.dtype)
     data["regression_boxes"] = data["bbox_proj_crop"].clone()
-    data["regression_boxes"][camera_mask] = pred_proj[:, 0].to(data["regression_boxes"].dtype)
+    data["regression_boxes"][where] = pred_proj[:, 0].to(data["regression_boxes"].dtype)
     data["pred_poses"] = pred_poses
     data["pred_intrinsics"] = data["intrinsics"].clone()
-    return data
 
 
 def _repeat_views(fresh, times: int):
@@ -405,7 +415,7 @@ def process_multi_round_bank(data, bank, fresh, rows, cand, ar, decoder, dense_c
     and the decoder runs on them from the bank: bank.gather for a feature bank (bbox_feat re-packed by integer indexing with the
     kernel's `view` table, zeros where it pads), BETR.forward_entry for an entry-token bank (the query's features repeated per
     round; bbox_feat may be absent).  recover_pose_from_dense_bb8 runs as it is.  Without dense_cfg.fine_level the coarse dict is
-    written as process_multi_round writes it and (data, None) returned.  With it ONE bd_pose_select_rows launch picks the fine_topk
+    written as process_multi_round writes it (_write_coarse) and (None, None) returned.  With it ONE bd_pose_select_rows launch picks the fine_topk
     kept references nearest to the coarse pose by the BANK's poses (the dict's are not read), the dict is re-packed to
     (B, fine_topk + 1) and (the fine round's decoder output, the new query_idx) returned; the dict gains dense_fine_slots
     (B, fine_topk) -- original reference slots, ascending -- and dense_fine_dist (B, k).  Nothing here waits for the device unless
@@ -457,15 +467,5 @@ def process_multi_round_bank(data, bank, fresh, rows, cand, ar, decoder, dense_c
         if entry:
             return decoder.forward_entry(bank.entry_tokens, len(bank), fsrc, fresh, data["camera_mask"], size), qi
         return decoder(data["bbox_feat"], data["images"], data["camera_mask"], bank.gather(fsrc, fresh, (B, fk + 1)), None), qi
-    pred_poses = data["poses"].clone()
-    if pose_feat is not None:
-        data["pred_bbox"] = pose_feat.clone()
-        data["pred_bbox"][ar, qi] = query_rets[:, 0].to(pose_feat.dtype)
-    else:       # an entry-token bank's batch may carry no heat maps: the decoder's output goes out as it does from BoxDreamer.forward
-        data["pred_query_bbox"] = query_rets[:, 0]
-    pred_poses[ar, qi] = query_poses.squeeze(1).to(pred_poses.dtype)
-    data["regression_boxes"] = data["bbox_proj_crop"].clone()
-    data["regression_boxes"][ar, qi] = pred_proj[:, 0].to(data["regression_boxes"].dtype)
-    data["pred_poses"] = pred_poses
-    data["pred_intrinsics"] = data["intrinsics"].clone()
-    return data, None
+    _write_coarse(data, (ar, qi), pose_feat, query_rets, query_poses, pred_proj)
+    return None, None

@@ -131,10 +131,9 @@ def test_original_images_repacked_on_the_host():
     model = _model(DENSE)
     org = [[f"v{t}b{b}" for b in range(2)] for t in range(6)]          # [T][B]
     data = {"original_images": org}
-    plan = (None, None, None, [5, 1], K)
-    model._slots_host = [[0, 2, 4], [0, 1, 3]]                         # as they come back with the corners' D2H
+    slots_host = [[0, 2, 4], [0, 1, 3]]                                # as they come back with the corners' D2H
     syncs = []
-    model._repack_original_images(data, plan, None, syncs)
+    model._repack_original_images(data, [5, 1], None, slots_host, syncs)
     assert data["original_images"] == [["v0b0", "v0b1"], ["v2b0", "v2b1"], ["v4b0", "v4b1"], ["v5b0", "v1b1"]] and syncs == []
 
 

@@ -71,21 +71,21 @@ def test_check_mode_lets_a_bank_with_poses_through_and_no_other():
         without = RefFeatureBank(model.rgb_encoder, match_threshold=0.05)
         without._n = 40
         with pytest.raises(NotImplementedError, match="multi_round") as e:
-            model._check_mode(dict(data, ref_bank=without, ref_rows=table), 2, 6, None, True)
+            model._check_mode(dict(data, ref_bank=without, ref_rows=table), None, True, True)
         assert "keep_poses=True" in str(e.value)
         with_poses = RefFeatureBank(model.rgb_encoder, match_threshold=0.05, keep_poses=True)
         with_poses._n = 40
-        bank, rows = model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), 2, 6, None, True)
+        bank, rows = model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), None, True, True)
         assert bank is with_poses and rows == table
     # ... and it still wants the DINO filter and the match summaries, as the banked dense mode does
     model.dense_cfg = dict(DENSE, filter_enable=False)
     with pytest.raises(NotImplementedError, match="DINO filter"):
-        model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), 2, 6, None, True)
+        model._check_mode(dict(data, ref_bank=with_poses, ref_rows=table), None, True, True)
     model.dense_cfg = dict(DENSE)
     no_sums = RefFeatureBank(model.rgb_encoder, keep_poses=True)
     no_sums._n = 40
     with pytest.raises(ValueError, match="match summaries"):
-        model._dense_bank_plan(no_sums, table, None, data["query_idx"], 2, 6)
+        model._dense_bank_plan(no_sums, table, [6, 6], data["query_idx"].tolist())
 
 
 def _rot(axis, angle):
