@@ -16,6 +16,8 @@
 //                      and the final 1/l are per-lane scalars.
 // K tile rows are padded by 16 B and the V^T image is XOR-swizzled so that each ds_read_b128 lane
 // group hits 16 distinct bank slots.  K/V tiles of 64 keys are register-prefetched one tile ahead.
+// The split-bf16 hd-64 instances stage differently (DMA below): K and V tiles go row-major into LDS by LDS-DMA, with no
+// staging registers, and the V^T fragments come from the transposing read ds_read_b64_tr_b16.
 // NS = 2 is the split-bf16 strict mode: Q, K, V, P each carry (hi, lo) and every product issues
 // hi*hi + hi*lo + lo*hi.
 #include "bd_common.h"
@@ -76,16 +78,45 @@ __device__ __forceinline__ int vswz(int d) { return ((d >> 1) ^ (d >> 4)) & 7; }
 __device__ __forceinline__ unsigned pack_lo16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }   // (a & 0xffff) | (b << 16)
 __device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // (a >> 16) | (b & 0xffff0000)
 
+// LDS-DMA and the transposing LDS read, as device functions: the kernel template is also instantiated for the host, which has
+// neither builtin.
+typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
+// 16 bytes per lane, global -> LDS with no register in between: lane l's piece lands at lds_dst + 16 l (lds_dst wave-uniform); a lane
+// whose voff is out of the descriptor's range fetches nothing.
+// The BUILTIN, where the GEMMs issue their DMA from inline asm (gemm_common.h: glds16): there a slab's DMA flies under the MFMAs of
+// the one before, and hipcc, which sees an LDS write it cannot place, would drain it with vmcnt(0) in front of the first fragment
+// read.  Here nothing is in flight while fragments are read -- the tile is issued after the barrier that ends the reads and waited
+// for in full before the next one -- so that conservative wait is the wait this kernel wants, and the key loop keeps its counted
+// lgkmcnt waits (checked in the ISA: lgkmcnt(6 / 4 / 2) over the K fragments).
+__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* lds_dst, int voff, int soff) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)lds_dst, 16, voff, soff, 0, 0);
+}
+// ds_read_b64_tr_b16: lane 4 q + p of a 16-lane group addresses row q, 16-bit columns 4 p .. 4 p + 3 of a 4 x 16 block; lane i of the
+// group gets column i, row q in element q.  EXEC must be all ones.
+__device__ __forceinline__ s16x4 lds_read_tr16(const unsigned char* a) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
+}
+
 // OUTSPLIT: single-pass f16 attention whose result is written as split-bf16 (hi, lo) planes -- the strict mode's
 // attention (its GEMMs stay split-bf16 x3): q/k are RMS-normalised and P is in [0, 1], so one f16 pass costs ~1e-4 on
 // the logits while the x3 attention kernel is register-bound at one wave per SIMD.
 template <class T, int NS, int HD, int NW, int OUTMODE = 0, bool VL = false>
-__global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_kernel(const AttnArgs p) {      // (HIP: 2nd argument = min waves per SIMD)
+__global__ __launch_bounds__(NW * 64, HD == 64 ? 3 : 2) void attn_kernel(const AttnArgs p) {      // (HIP: 2nd argument = min waves per SIMD)
     bd_saturating_conversions();      // fp8 / f16 results saturate (bd_common.h: RANGE)
     typedef typename Op16<T>::vec8 vec8;
+    // DMA: the split-bf16 hd-64 instances (DINOv2's strict attention).  With K / V register-prefetched they need 211 VGPRs = two waves per
+    // SIMD, 56 of them the next tile in flight.  Here both tiles go global -> LDS by LDS-DMA (no staging registers, no ds_write pass, no
+    // register transposition of V), which fits three waves per SIMD = four 3-wave workgroups per CU: the latency of a tile's loads is
+    // hidden by the other workgroups, not by a prefetch.  LDS images (128-byte rows, one row per key, 16-byte chunks XOR-swizzled on the
+    // GLOBAL side, because an LDS-DMA piece lands lane-linear: 1 KiB = 8 rows):
+    //   K: chunk c of row r at chunk c ^ ((r >> 1) & 7) -- the 16 rows of a ds_read_b128 lane group are 8 pairs (2 j, 2 j + 1) with
+    //      distinct (j & 7), and a pair shares one 256-byte bank row: 16 distinct bank slots (profiles/attn_dino_lds_dma.md);
+    //   V: chunk c of row r at chunk c ^ ((r & 2) << 1) -- a 32-lane half of ds_read_b64_tr_b16 reads 64 bytes of each of 4 consecutive
+    //      rows; rows r and r + 2 share the bank-row half, and the swizzle sends them to opposite 64-byte quarters of it.
+    constexpr bool DMA = NS == 2 && HD == 64;
     constexpr int NT = NW * 64;
     constexpr int DCH = HD / 8;                  // 16-byte chunks per K/V row
-    constexpr int KSTRIDE = HD * 2 + 16;         // padded K row (bytes)
+    constexpr int KSTRIDE = DMA ? HD * 2 : HD * 2 + 16;      // K row (bytes): padded where it is written by ds_write
     constexpr int K_BYTES = KT * KSTRIDE;
     constexpr int V_BYTES = HD * 128;            // V^T image: HD rows x 64 keys x 2 B
     constexpr int PLANE_BYTES = K_BYTES + V_BYTES;
@@ -153,7 +184,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     const int64_t plane = p.qkv_plane;
 
     // ---- Q fragments (B operand of S^T): lane (q, h) holds Q[q][ks*16 + h*8 .. +7]
-    const int q0 = qb * QB + wid * 32;                     // local query index (within the query range)
+    const int q0 = qb * QB + (NS == 2 && HD == 64 ? __builtin_amdgcn_readfirstlane(wid) : wid) * 32;      // local query index (within the query range)
     int qbase_row = p.q_view ? p.q_view[b] * q_len : p.q_off;
     if constexpr (VL) { if (p.q_view) { const int qv = p.q_view[b]; qbase_row = (qv < 0 ? 0 : (qv < vl_views ? qv : vl_views - 1)) * q_len; } }
     int qrow = q0 + lq; qrow = (qrow < q_len ? qrow : q_len - 1) + qbase_row;
@@ -207,6 +238,51 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
         }
     }
     const int row_bytes = __builtin_amdgcn_readfirstlane(ld * (int)sizeof(T));
+    // (DMA) one tile = 16 pieces of 1 KiB per plane (K then V, 8 rows each), piece i at byte i * 1024 of the plane, dealt round-robin to
+    // the waves.  Lane l of a piece fills physical chunk l & 7 of the piece's row l >> 3.  That row and the swizzled chunk are the per-lane
+    // offset; the piece's first row and the K / V column origin are the scalar offset.  Only pieces whose first row is a row of the
+    // sample are issued, so the scalar offset stays inside the descriptor; the rows of such a piece past the sequence end are out of
+    // range and their lanes fetch nothing.
+    const int wid_s = __builtin_amdgcn_readfirstlane(wid);
+    auto stage_dma = [&](const int kt) {
+        // the per-lane offsets are re-derived here, from an opaque lane id: hoisted out of the key loop they are six registers that
+        // the loop does not have (three waves per SIMD: 168)
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int dma_row = ln >> 3, dma_c = ln & 7, dma_row_off = dma_row * row_bytes;
+        // even K pieces; odd ones: ^ 64 (row bit 3 -> chunk bit 2).  The XOR reaches the chunk alone because the row part of the sum is
+        // a multiple of 128: row_bytes = 3 * heads * HD * sizeof(T) with HD == 64 here (the token row is the kernel's own ld, never an argument)
+        static_assert(!DMA || (HD * sizeof(T)) % 128 == 0, "the ^ 64 of odd K pieces needs 128-byte-multiple token rows");
+        const int dma_k_voff = dma_row_off + ((dma_c ^ (dma_row >> 1)) << 4);
+        const int dma_v_voff = dma_row_off + ((dma_c ^ ((dma_row & 2) << 1)) << 4);
+        const int tile_off = kt * KT * row_bytes + heads * HD * (int)sizeof(T), rows_left = seq - kt * KT;
+#pragma unroll
+        for (int j = 0; j < (16 + NW - 1) / NW; ++j) {
+            const int i = wid_s + NW * j, pc = i & 7;      // piece of the plane: 0..7 K, 8..15 V
+            if ((16 % NW == 0 || i < 16) && pc * 8 < rows_left) {
+                const bool is_v = i >> 3;
+                const int voff = is_v ? dma_v_voff : (pc & 1) ? (dma_k_voff ^ 64) : dma_k_voff;
+                const int soff = tile_off + pc * 8 * row_bytes + (is_v ? heads * HD * (int)sizeof(T) : 0);
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+                    lds_dma16(rsrc[s], lds + s * PLANE_BYTES + i * 1024, voff, soff);
+            }
+        }
+        // V rows past a ragged end: their P is exactly 0, but 0 * (whatever LDS held) must be 0 too.  Whole rows, so no swizzle.
+        const int valid = seq - kt * KT;
+        if (valid < KT) {
+            for (int c = valid * DCH + tid; c < KT * DCH; c += NT)
+#pragma unroll
+                for (int s = 0; s < NS; ++s) *(u128*)(lds + s * PLANE_BYTES + K_BYTES + c * 16) = (u128){0u, 0u, 0u, 0u};
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces have landed; the barrier that follows covers the others'
+    };
+    // (DMA) fragment addresses inside a plane.  K: row lq (+ 32 km), chunk (2 ks + lh) swizzled.  V^T by the transposing read: lane
+    // 4 q + p of a 16-lane group addresses row q of a 4-key block, columns 4 p .. 4 p + 3 of the group's 16 d, and receives column
+    // (lane & 15) of the 4 rows -- V[key0 + 0..3][d = 32 dm + lq], half of the A fragment of O^T.  dm flips chunk bit 2: address ^ 64.
+    const int tr_q = (lane >> 2) & 3, tr_p = lane & 3;
+    const unsigned kfrag_dma = (unsigned)(lq * 128 + ((lh ^ ((lq >> 1) & 7)) << 4));                      // ^ (ks << 5), + km * 4096
+    const unsigned vfrag_dma = (unsigned)(K_BYTES + (4 * lh + tr_q) * 128 + (((((lane >> 4) & 1) * 2 + (tr_p >> 1)) ^ ((tr_q & 2) << 1)) << 4) + (tr_p & 1) * 8);
     int k_voff[KCPT];
 #pragma unroll
     for (int i = 0; i < KCPT; ++i) k_voff[i] = ((int)kc_off[i] + heads * HD) * (int)sizeof(T);
@@ -251,8 +327,12 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     const float sc = p.scale_log2e;
 
     const int nt = (seq + KT - 1) / KT;
-    LOAD_TILE(0)
-    STORE_TILE(0)
+    if constexpr (DMA) {
+        stage_dma(0);
+    } else {
+        LOAD_TILE(0)
+        STORE_TILE(0)
+    }
     __syncthreads();
     AP(61)
     // One key tile.  Two instances: TAIL 0 = any tile (a ragged last one masks its scores), TAIL 2 = a ragged last tile of <= 16 keys
@@ -265,7 +345,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     auto tile = [&](const int kt, auto tail_c) {
         constexpr int TAIL = decltype(tail_c)::value;
         constexpr int KMN = TAIL == 2 ? 1 : 2, GN = TAIL == 2 ? 1 : 4;
-        if (kt + 1 < nt) { LOAD_TILE(kt + 1) }
+        if constexpr (!DMA) { if (kt + 1 < nt) { LOAD_TILE(kt + 1) } }
         const unsigned char* cur = lds + (NBUF == 2 ? (kt & 1) : 0) * BUF_BYTES;
         if (kt < 7) AP(kt * 8)
 
@@ -275,12 +355,25 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
         for (int km = 0; km < KMN; ++km) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[km][r] = 0.f;
+            // (DMA) all eight fragments of the M-tile are requested before its first MFMA: left to itself hipcc, at the 168-register cap,
+            // waits for every fragment right in front of the MFMAs that use it
+            vec8 kfa[DMA ? KS : 1][NS];
+            if constexpr (DMA) {
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                    for (int s = 0; s < NS; ++s)
+                        kfa[ks][s] = as_vec8<T>(*(const u128*)(cur + s * PLANE_BYTES + km * 32 * KSTRIDE + (kfrag_dma ^ (unsigned)(ks << 5))));
+                __builtin_amdgcn_sched_barrier(0);
+            }
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 vec8 kf[NS];
 #pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    kf[s] = as_vec8<T>(*(const u128*)(cur + s * PLANE_BYTES + (km * 32 + lq) * KSTRIDE + (ks * 2 + lh) * 16));
+                for (int s = 0; s < NS; ++s) {
+                    if constexpr (DMA) kf[s] = kfa[ks][s];
+                    else kf[s] = as_vec8<T>(*(const u128*)(cur + s * PLANE_BYTES + (km * 32 + lq) * KSTRIDE + (ks * 2 + lh) * 16));
+                }
                 if (NS == 2) {
                     sacc[km] = Op16<T>::mfma(kf[NS - 1], qf[0][ks], sacc[km]);
                     sacc[km] = Op16<T>::mfma(kf[0], qf[NS - 1][ks], sacc[km]);
@@ -297,8 +390,15 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
             for (int km = 0; km < KMN; ++km)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KT + km * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (key >= seq) sacc[km][r] = -INFINITY;
+                    if constexpr (DMA) {
+                        // the same test against ONE register: written per key, hipcc keeps the 22 key indices of the generic tile in
+                        // registers across the loop
+                        const int live = seq - kt * KT - 4 * lh;      // keys of this tile left for the lane's half
+                        if (km * 32 + (r & 3) + 8 * (r >> 2) >= live) sacc[km][r] = -INFINITY;
+                    } else {
+                        const int key = kt * KT + km * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        if (key >= seq) sacc[km][r] = -INFINITY;
+                    }
                 }
         }
 #pragma unroll
@@ -345,9 +445,16 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
                 const int d = dm * 32 + lq;
                 vec8 vf[NS];
 #pragma unroll
-                for (int s = 0; s < NS; ++s)
-                    vf[s] = as_vec8<T>(*(const u128*)(cur + s * PLANE_BYTES + K_BYTES + d * 128 +
-                                                        (((g * 2 + lh) ^ vswz(d)) << 4)));
+                for (int s = 0; s < NS; ++s) {
+                    if constexpr (DMA) {
+                        const unsigned char* a = cur + s * PLANE_BYTES + g * 16 * 128 + (vfrag_dma ^ (unsigned)(dm << 6));
+                        const s16x4 k03 = lds_read_tr16(a);                 // keys 16 g + 4 lh + 0..3
+                        const s16x4 k8b = lds_read_tr16(a + 8 * 128);       // keys 16 g + 8 + 4 lh + 0..3
+                        vf[s] = __builtin_bit_cast(vec8, __builtin_shufflevector(k03, k8b, 0, 1, 2, 3, 4, 5, 6, 7));
+                    } else {
+                        vf[s] = as_vec8<T>(*(const u128*)(cur + s * PLANE_BYTES + K_BYTES + d * 128 + (((g * 2 + lh) ^ vswz(d)) << 4)));
+                    }
+                }
                 if (NS == 2) {
                     oacc[dm] = Op16<T>::mfma(vf[NS - 1], pf[0], oacc[dm]);
                     oacc[dm] = Op16<T>::mfma(vf[0], pf[NS - 1], oacc[dm]);
@@ -359,7 +466,8 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
         if (kt < 7) AP(kt * 8 + 3)
         if (NBUF == 1) __syncthreads();                      // single buffer: everyone must be done reading first
         if (kt < 7) AP(kt * 8 + 4)
-        if (kt + 1 < nt) { STORE_TILE(NBUF == 2 ? ((kt + 1) & 1) : 0) }
+        if constexpr (DMA) { if (kt + 1 < nt) stage_dma(kt + 1); }
+        else if (kt + 1 < nt) { STORE_TILE(NBUF == 2 ? ((kt + 1) & 1) : 0) }
         if (kt < 7) AP(kt * 8 + 5)
         __syncthreads();
         if (kt < 7) AP(kt * 8 + 6)
@@ -373,7 +481,16 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
     AP(62)
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
-    const int q = q0 + lq;
+    // (DMA) the lane's query and key half are re-derived from an opaque lane id: kept alive from the prologue they are three registers
+    // spilled around the key loop
+    int elq = lq, elh = lh;
+    if constexpr (DMA) {
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        elq = ln & 31;
+        elh = ln >> 5;
+    }
+    const int q = q0 + elq;
     if (q < q_len) {
         if (OUTMODE == 2) {
             fp8e4* orow = (fp8e4*)p.out + (out_row0() + q) * (heads * HD) + head * HD;
@@ -384,7 +501,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
                     float v4[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v4[j] = oacc[dm][rq * 4 + j] * inv;
-                    store_cvt<fp8e4, 4>(orow + dm * 32 + 8 * rq + 4 * lh, v4);
+                    store_cvt<fp8e4, 4>(orow + dm * 32 + 8 * rq + 4 * elh, v4);
                 }
         } else if (OUTMODE == 3) {
             // F16C8 operand (the proj GEMM's A in the round-2 strict mode): f16 hi plane + k-permuted lo8 plane
@@ -396,7 +513,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
                     float v4[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v4[j] = oacc[dm][rq * 4 + j] * inv;
-                    f16c8_store4((f16c8*)p.out, p.out_plane, e0 + dm * 32 + 8 * rq + 4 * lh, v4);
+                    f16c8_store4((f16c8*)p.out, p.out_plane, e0 + dm * 32 + 8 * rq + 4 * elh, v4);
                 }
         } else if (OUTMODE == 1 || OUTMODE == 4) {
             // (hi, lo) planes of ANOTHER 16-bit type than the kernel's operands: 1 = split-bf16, 4 = split-f16 (BD_PREC_F16X3)
@@ -406,7 +523,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const int d0 = dm * 32 + 8 * rq + 4 * lh;
+                    const int d0 = dm * 32 + 8 * rq + 4 * elh;
                     typedef __attribute__((__vector_size__(4 * sizeof(OT)))) OT ovec4;
                     ovec4 hi, lo;
 #pragma unroll
@@ -425,7 +542,7 @@ __global__ __launch_bounds__(NW * 64, NS == 1 && HD == 64 ? 3 : 2) void attn_ker
             for (int dm = 0; dm < DM; ++dm)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const int d0 = dm * 32 + 8 * rq + 4 * lh;
+                    const int d0 = dm * 32 + 8 * rq + 4 * elh;
                     typedef __attribute__((__vector_size__(4 * sizeof(T)))) T vec4;
                     vec4 hi, lo;
 #pragma unroll
